@@ -15,10 +15,13 @@ local n/N-point transform, a twiddle, ONE all-to-all over RCCL and a local N-poi
 distribution its h_query shard is gathered in), every rank computes its partial sums, ONE all-gather of the 1.2 KB
 partial records over RCCL combines them and every rank finishes the proof.
 
-Prints one JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline      dominant kernel (the G1 bucket-accumulation pass) against the 8 TB/s HBM roofline
+Prints one JSON line on rank 0.  A plain run only sets up, warms up, times --steps proofs and reports the headline (value,
+ms_per_step, the per-phase timers of the timed steps).  --full adds, after the timed steps, everything that needs work of its own:
+  roofline      dominant kernel (the G1 bucket-accumulation pass) against the 8 TB/s HBM roofline (+ roofline_ntt)
   cpu_baseline  the CPU oracle (C++ restatement of ark-groth16's algorithm, NOT ark-groth16 itself) timed
-                on this box's host cores on a bounded sample (smaller k), rank 0, N = 1 only
+                on the host cores on a bounded sample (smaller k), rank 0, N = 1 only
+  value_incl_h2d, projected_scaling, pipelined (N = 1); collective_ms, configs4 (N > 1)
+--dump-outputs DIR writes the proof of the last timed step (what a caller of the prover receives) as .npy files.
 """
 import argparse
 import ctypes as C
@@ -263,6 +266,15 @@ def prove_step(p, dist, device):
     dist.all_gather(outs, t)  # RCCL over xGMI: ~1.2 KB per rank, one collective per proof
     parts = [PartialC.from_buffer_copy(o.cpu().numpy().tobytes()) for o in outs]
     return p.finalize(parts)
+
+
+def dump_proof(dirname, proof, L):
+    """the proof as np.save files a later build's can be compared with element for element: each u64 Montgomery limb as its two u32
+    words (little-endian), float64 holds them exactly; a: 2 x 2L, b: 4 x 2L (x.c0, x.c1, y.c0, y.c1), c: 2 x 2L"""
+    os.makedirs(dirname, exist_ok=True)
+    words = proof.view(np.uint32).astype(np.float64).reshape(-1, 2 * L)
+    for name, rows in (("a", words[:2]), ("b", words[2:6]), ("c", words[6:])):
+        np.save(os.path.join(dirname, f"proof_{name}.npy"), rows)
 
 
 def cpu_quota():
@@ -548,6 +560,93 @@ def self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
+def roofline_objects(p, args, world, last_tm, bucket_g1, bucket_g2, phase_acc):
+    """--full: the dominant kernel and the transforms against their bounds, from the timers of the timed steps (+ one run of
+    g16_diag_valu's issue-rate kernel)"""
+    # dominant kernel: the G1 bucket-accumulation pass (4 launches per proof).  Algorithmic bytes per launch =
+    # N * (96 B affine base + 32 B scalar) (SURVEY.md 8(d)), N = points in this rank's shard.
+    n_pts = p.ranges["a"][1] - p.ranges["a"][0]
+    base_bytes = 2 * FQ_LIMBS[args.curve] * 8
+    # (bucket-space shard: the rank folds 1 / world of the (point, window) entries of ALL points -- SURVEY 8(d): the sharded terms
+    # divide by the GPU count)
+    bucket_div = world if p.mode == "bucket" else 1
+    # The G1 MSMs that are ready together share ONE launch of the kernel (l, a, b_g1; h too in a sharded proof): a "launch" below is
+    # an actual launch (what rocprofv3 --stats averages over), its algorithmic bytes those of the MSMs it walks.
+    g1_points = (p.ranges["h"][1] - p.ranges["h"][0]) + (p.ranges["l"][1] - p.ranges["l"][0]) + 2 * n_pts   # h, l, a, b_g1 (r != 0)
+    g1_launches = max(1, int(round(last_tm.get("g1_pass_launches", 0))) or len([x for x in last_tm["bucket_ms"][:4] if x > 0]))
+    g1_ms_per_step = float(np.sum(bucket_g1)) / args.steps if bucket_g1 else float("nan")
+    alg_bytes = g1_points * (base_bytes + 32) // bucket_div // g1_launches
+    avg_ms = g1_ms_per_step / g1_launches
+    achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
+    # HBM bytes per launch from the PMC counters (separate rocprofv3 --pmc passes, committed under profiles/);
+    # only valid for the workload they were collected on
+    traffic, ntt_traffic, traffic_cal, traffic_src = None, None, None, None
+    try:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from tree_hash import kernel_source_sha16
+
+        pt = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+        wl = pt["workload"]
+        here, there = kernel_source_sha16(ROOT), pt.get("kernel_source_sha16")
+        if here != there:
+            # counters of another tree say nothing about this one's kernels: not reported (re-collect: tools/gpu_session.sh <tag> pmc)
+            traffic_src = (f"profiles/pmc_traffic.json was collected on kernel sources {there} (commit {pt.get('git_commit', '?')}), this run's "
+                           f"are {here}: traffic withheld")
+        elif wl["curve"] == args.curve and wl["log2_domain"] == args.log2 and wl["n_gpus"] == world:
+            traffic_src = (f"profiles/pmc_traffic.json: rocprofv3 --pmc passes of this workload on THIS tree (kernel sources {here}, commit "
+                           f"{pt.get('git_commit', '?')}); collected in their own run, not measured in this one")
+            traffic = pt["hbm_bytes_per_launch"]
+            ntt_traffic = pt.get("ntt_hbm_bytes_per_step")
+            cal = pt.get("calibration")
+            if cal:
+                traffic_cal = (f"FETCH_SIZE x {cal['fetch']['factor']:.3f} ({cal['fetch']['pattern']}), WRITE_SIZE x {cal['write']['factor']:.3f} "
+                               f"({cal['write']['pattern']}): factors of known-bytes kernels with the same access pattern run under the same "
+                               "--pmc passes (tools/calib.hip, DESIGN.md 4.5)")
+    except Exception:  # noqa: BLE001
+        pass
+    # the bound that actually applies (DESIGN.md 4.3): v_mad_u64_u32 issue.  Both sides of the fraction come from the library
+    # (g16_diag_valu): the multiply-adds of one mixed addition counted from the kernels' own constexpr tables, and the
+    # instruction's issue rate MEASURED on this GPU in this run (all CUs, 8 waves per SIMD, independent chains).
+    n_windows = int(last_tm.get("windows", 0))
+    valu = None
+    if n_windows:
+        dg = DiagC()
+        p.lib.check(p.lib.c.g16_diag_valu(p.ctx, C.byref(dg)))
+        mads = float(g1_points) * n_windows * dg.mads_per_add_g1 / bucket_div / g1_launches
+        valu = dict(kind="v_mad_u64_u32 issue (integer VALU)", mads_per_launch=mads, achieved_Tmad_s=mads / (avg_ms * 1e-3) / 1e12,
+                    measured_peak_Tmad_s=dg.mad_per_s / 1e12, frac=mads / (avg_ms * 1e-3) / dg.mad_per_s,
+                    peak_source="g16_diag_valu: mad_rate_kernel timed in this run", mads_per_mixed_add=dg.mads_per_add_g1,
+                    mads_per_field_product=dg.mads_per_product, limbs30=dg.limbs, window_bits=int(last_tm.get("window_bits", 0)),
+                    windows=n_windows, points_folded_per_launch=g1_points * n_windows // bucket_div // g1_launches,
+                    g2=dict(mads_per_mixed_add=dg.mads_per_add_g2, achieved_Tmad_s=float(n_pts) * n_windows * dg.mads_per_add_g2 / bucket_div /
+                            (float(np.mean(bucket_g2)) * 1e-3) / 1e12 if bucket_g2 and np.mean(bucket_g2) > 0 else None))
+    # second object for the transforms (SURVEY.md 8(d): 2 * 32 * n algorithmic bytes per NTT, seven per proof), from the
+    # HIP-event timers around them inside the witness map
+    ntt_ms = phase_acc.get("ntt_ms", 0.0) / args.steps
+    roofline_ntt = None
+    if ntt_ms > 0:
+        ntt_bytes = 7 * 2 * 32 * p.n
+        roofline_ntt = dict(bound="hbm", achieved=ntt_bytes / (ntt_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
+                            frac=ntt_bytes / (ntt_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, kernel="ntt30_* (7 radix-2 transforms of size n per proof)",
+                            ms_per_step=ntt_ms, algorithmic_bytes_per_step=ntt_bytes, traffic=ntt_traffic,
+                            note="instruction-bound in practice (DESIGN.md 4.2); ms_per_step includes the pointwise quotient "
+                                 "(a b - c) / Z, fused into the first sweep of the seventh transform since round 4 (it used to be a "
+                                 "0.18 ms kernel outside this timer); replicated on every rank when sharded")
+    roofline = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS, traffic=traffic,
+                    traffic_source=traffic_src,
+                    traffic_calibration=traffic_cal,
+                    binding_resource="integer VALU (v_mad_u64_u32 issue), not HBM: see valu_bound",
+                    valu_bound=valu,
+                    kernel="bucket_accumulate30_kernel (G1 Pippenger bucket pass)", launches_per_step=g1_launches,
+                    avg_launch_ms=avg_ms, algorithmic_bytes_per_launch=alg_bytes,
+                    msms_per_step=len(bucket_g1) // args.steps, per_msm_ms=g1_ms_per_step / max(1, len(bucket_g1) // args.steps),
+                    launch_note="the G1 MSMs that are ready together go as ONE launch (one tail instead of one per MSM): avg_launch_ms and "
+                                "algorithmic_bytes_per_launch are per ACTUAL launch (mean over launches of different size), per_msm_ms per MSM",
+                    note="integer-VALU bound in practice (10 Fq products per 128 B); see DESIGN.md",
+                    g2_bucket_avg_ms=float(np.mean(bucket_g2)))
+    return roofline, roofline_ntt
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -567,9 +666,9 @@ def main():
                          "rank ~10 s of HOST scalar work (Lagrange coefficients, the per-variable exponents), N ranks share one CPU quota, "
                          "and that untimed setup must not be what a driver's clock around an 8-rank run sees")
     ap.add_argument("--configs4", choices=["auto", "on", "off"], default=os.environ.get("G16_BENCH_CONFIGS4", "auto"),
-                    help="after the headline line's timed region, also time BASELINE.json configs[4] (2^24 constraints, BLS12-381, MSM bases "
-                         "sharded over the ranks) and report it as the `configs4` field of the same JSON line; auto = when --gpus is 8 "
-                         "and --log2 is the headline 22")
+                    help="with --full: after the headline line's timed region, also time BASELINE.json configs[4] (2^24 constraints, BLS12-381, "
+                         "MSM bases sharded over the ranks) and report it as the `configs4` field of the same JSON line; auto = when --gpus "
+                         "is 8 and --log2 is the headline 22")
     ap.add_argument("--configs4-log2", type=int, default=24, help=argparse.SUPPRESS)   # tests shrink it
     ap.add_argument("--shard-mode", choices=["auto", "base", "bucket"], default=os.environ.get("G16_BENCH_SHARD_MODE", "auto"),
                     help="N > 1: how the five MSMs are cut over the ranks -- base: contiguous ranges of the bases (1/N of the window tables per GPU); "
@@ -580,7 +679,19 @@ def main():
     ap.add_argument("--sim-shards", type=int, default=0,
                     help="DIAGNOSTIC, not a benchmark: time one rank's share of an N-way sharded proof on a single GPU "
                          "(shard 0 of N, no exchange); the JSON line is tagged and must not be read as throughput")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: roofline objects, CPU baseline, "
+                         "PCIe-inclusive rates, projected scaling, pipelined throughput (N = 1); collective timings, configs[4] (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the proof of the last timed step to DIR/proof_{a,b,c}.npy (rank 0): the u32 words of its affine "
+                         "Montgomery limbs as float64 (exact), shape (coordinates, words)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.configs4 == "on" and not args.full:
+        ap.error("--configs4 on needs --full")
+    if args.dump_outputs and args.sim_shards:
+        ap.error("--dump-outputs writes the headline proof; --sim-shards computes none")
     if args.cpu_log2 <= 0:
         args.cpu_log2 = args.log2
     key_was_auto = args.key == "auto"
@@ -728,12 +839,14 @@ def main():
         gathered = [torch.empty_like(pt) for _ in range(world)]
         dist.all_gather(gathered, pt)
         assert all(bool((x == gathered[0]).all()) for x in gathered), "ranks disagree on the proof"
+    if args.dump_outputs and rank == 0:
+        dump_proof(args.dump_outputs, proof, p.L)
 
     # the collectives of one sharded proof, each timed ALONE after the timed steps (same tensors, same process group, HIP events on the
     # current stream, max over ranks): the terms a measured N > 1 line can be compared with the one-GPU projection by -- the projection
     # holds everything but these
     collective_ms = None
-    if dist is not None and world > 1:
+    if dist is not None and world > 1 and args.full:
         collective_ms = {}
 
         def time_coll(fn, reps=5):
@@ -772,7 +885,7 @@ def main():
     # HBM-resident rate the bench contract asks for): the same proof with full_assignment uploaded inside the call, from
     # pageable and from pinned host memory.  Outside the timed region; single-GPU only.
     h2d = None
-    if dist is None:
+    if dist is None and args.full:
         h2d = {}
         z_pinned = torch.from_numpy(p.z_host.view(np.int64)).pin_memory()
         for name, hp in (("pageable", p.z_host.ctypes.data), ("pinned", z_pinned.data_ptr())):
@@ -789,93 +902,12 @@ def main():
 
     # BASELINE.json configs[4] beside the headline (the driver passes no --log2): the SAME code path at 2^24 constraints, timed
     # with the same barrier / max-over-ranks bracket, reported as a field -- the headline `value` stays the 2^22 strong-scaling one
-    want_c4 = dist is not None and (args.configs4 == "on" or (args.configs4 == "auto" and world == 8 and args.log2 == 22 and
-                                                                args.curve == "bls12_381"))
+    want_c4 = args.full and dist is not None and (args.configs4 == "on" or (args.configs4 == "auto" and world == 8 and args.log2 == 22 and
+                                                                              args.curve == "bls12_381"))
     out = None
     if rank == 0:
         ms_per_step = 1e3 * dt / args.steps
         value = p.nc * args.steps / dt
-        # dominant kernel: the G1 bucket-accumulation pass (4 launches per proof).  Algorithmic bytes per launch =
-        # N * (96 B affine base + 32 B scalar), N = points in this rank's shard.
-        n_pts = p.ranges["a"][1] - p.ranges["a"][0]
-        base_bytes = 2 * FQ_LIMBS[args.curve] * 8
-        # (bucket-space shard: the rank folds 1 / world of the (point, window) entries of ALL points -- SURVEY 8(d): the sharded terms
-        # divide by the GPU count)
-        bucket_div = world if p.mode == "bucket" else 1
-        # The G1 MSMs that are ready together share ONE launch of the kernel (l, a, b_g1; h too in a sharded proof): a "launch" below is
-        # an actual launch (what rocprofv3 --stats averages over), its algorithmic bytes those of the MSMs it walks.
-        g1_points = (p.ranges["h"][1] - p.ranges["h"][0]) + (p.ranges["l"][1] - p.ranges["l"][0]) + 2 * n_pts   # h, l, a, b_g1 (r != 0)
-        g1_launches = max(1, int(round(last_tm.get("g1_pass_launches", 0))) or len([x for x in last_tm["bucket_ms"][:4] if x > 0]))
-        g1_ms_per_step = float(np.sum(bucket_g1)) / args.steps if bucket_g1 else float("nan")
-        alg_bytes = g1_points * (base_bytes + 32) // bucket_div // g1_launches
-        avg_ms = g1_ms_per_step / g1_launches
-        achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
-        # HBM bytes per launch from the PMC counters (separate rocprofv3 --pmc passes, committed under profiles/);
-        # only valid for the workload they were collected on
-        traffic, ntt_traffic, traffic_cal, traffic_src = None, None, None, None
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            from tree_hash import kernel_source_sha16
-
-            pt = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-            wl = pt["workload"]
-            here, there = kernel_source_sha16(ROOT), pt.get("kernel_source_sha16")
-            if here != there:
-                # counters of another tree say nothing about this one's kernels: not reported (re-collect: tools/gpu_session.sh <tag> pmc)
-                traffic_src = (f"profiles/pmc_traffic.json was collected on kernel sources {there} (commit {pt.get('git_commit', '?')}), this run's "
-                               f"are {here}: traffic withheld")
-            elif wl["curve"] == args.curve and wl["log2_domain"] == args.log2 and wl["n_gpus"] == world:
-                traffic_src = (f"profiles/pmc_traffic.json: rocprofv3 --pmc passes of this workload on THIS tree (kernel sources {here}, commit "
-                               f"{pt.get('git_commit', '?')}); collected in their own run, not measured in this one")
-                traffic = pt["hbm_bytes_per_launch"]
-                ntt_traffic = pt.get("ntt_hbm_bytes_per_step")
-                cal = pt.get("calibration")
-                if cal:
-                    traffic_cal = (f"FETCH_SIZE x {cal['fetch']['factor']:.3f} ({cal['fetch']['pattern']}), WRITE_SIZE x {cal['write']['factor']:.3f} "
-                                   f"({cal['write']['pattern']}): factors of known-bytes kernels with the same access pattern run under the same "
-                                   "--pmc passes (tools/calib.hip, DESIGN.md 4.5)")
-        except Exception:  # noqa: BLE001
-            pass
-        # the bound that actually applies: v_mad_u64_u32 issue.  Both sides of the fraction come from the library
-        # (g16_diag_valu): the multiply-adds of one mixed addition counted from the kernels' own constexpr tables, and the
-        # instruction's issue rate MEASURED on this GPU in this run (all CUs, 8 waves per SIMD, independent chains).
-        n_windows = int(last_tm.get("windows", 0))
-        valu = None
-        if n_windows:
-            dg = DiagC()
-            p.lib.check(p.lib.c.g16_diag_valu(p.ctx, C.byref(dg)))
-            mads = float(g1_points) * n_windows * dg.mads_per_add_g1 / bucket_div / g1_launches
-            valu = dict(kind="v_mad_u64_u32 issue (integer VALU)", mads_per_launch=mads, achieved_Tmad_s=mads / (avg_ms * 1e-3) / 1e12,
-                        measured_peak_Tmad_s=dg.mad_per_s / 1e12, frac=mads / (avg_ms * 1e-3) / dg.mad_per_s,
-                        peak_source="g16_diag_valu: mad_rate_kernel timed in this run", mads_per_mixed_add=dg.mads_per_add_g1,
-                        mads_per_field_product=dg.mads_per_product, limbs30=dg.limbs, window_bits=int(last_tm.get("window_bits", 0)),
-                        windows=n_windows, points_folded_per_launch=g1_points * n_windows // bucket_div // g1_launches,
-                        g2=dict(mads_per_mixed_add=dg.mads_per_add_g2, achieved_Tmad_s=float(n_pts) * n_windows * dg.mads_per_add_g2 / bucket_div /
-                                (float(np.mean(bucket_g2)) * 1e-3) / 1e12 if bucket_g2 and np.mean(bucket_g2) > 0 else None))
-        # second object for the transforms (2 * 32 * n algorithmic bytes per NTT, seven per proof), from the
-        # HIP-event timers around them inside the witness map
-        ntt_ms = phase_acc.get("ntt_ms", 0.0) / args.steps
-        roofline_ntt = None
-        if ntt_ms > 0:
-            ntt_bytes = 7 * 2 * 32 * p.n
-            roofline_ntt = dict(bound="hbm", achieved=ntt_bytes / (ntt_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
-                                frac=ntt_bytes / (ntt_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, kernel="ntt30_* (7 radix-2 transforms of size n per proof)",
-                                ms_per_step=ntt_ms, algorithmic_bytes_per_step=ntt_bytes, traffic=ntt_traffic,
-                                note="instruction-bound in practice (DESIGN.md 4.2); ms_per_step includes the pointwise quotient "
-                                     "(a b - c) / Z, fused into the first sweep of the seventh transform since round 4 (it used to be a "
-                                     "0.18 ms kernel outside this timer); replicated on every rank when sharded")
-        roofline = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS, traffic=traffic,
-                        traffic_source=traffic_src,
-                        traffic_calibration=traffic_cal,
-                        binding_resource="integer VALU (v_mad_u64_u32 issue), not HBM: see valu_bound",
-                        valu_bound=valu,
-                        kernel="bucket_accumulate30_kernel (G1 Pippenger bucket pass)", launches_per_step=g1_launches,
-                        avg_launch_ms=avg_ms, algorithmic_bytes_per_launch=alg_bytes,
-                        msms_per_step=len(bucket_g1) // args.steps, per_msm_ms=g1_ms_per_step / max(1, len(bucket_g1) // args.steps),
-                        launch_note="the G1 MSMs that are ready together go as ONE launch (one tail instead of one per MSM): avg_launch_ms and "
-                                    "algorithmic_bytes_per_launch are per ACTUAL launch (mean over launches of different size), per_msm_ms per MSM",
-                        note="integer-VALU bound in practice (10 Fq products per 128 B); see DESIGN.md",
-                        g2_bucket_avg_ms=float(np.mean(bucket_g2)))
         out = {
             "metric": "R1CS constraints/sec (create_proof, BLS12-381)", "value": value, "unit": "constraints/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
@@ -888,7 +920,7 @@ def main():
                        "key_choice": ("auto: valid CRS on one GPU, synthetic bases with N > 1 ranks (bounds the untimed per-rank setup; any "
                                       "distinct points give the same prover work)") if key_was_auto else "--key",
                        "untimed_setup_s": round(t_setup, 2), "pk_load_s": round(p.pk_load_s, 3),
-                       "witness": "resident in HBM at entry (see value_incl_h2d for the PCIe-inclusive rates)",
+                       "witness": "resident in HBM at entry (--full: value_incl_h2d holds the PCIe-inclusive rates)",
                        "parallelism": ((f"msm-bucket-shard x{world} (whole window tables per GPU, buckets b mod {world} == rank)" if p.mode == "bucket"
                                         else f"msm-base-shard x{world}") +
                                        ((" + distributed witness map (3 all-to-all)" + (" + h all-gather" if p.mode == "bucket" else ""))
@@ -896,13 +928,15 @@ def main():
                        "shard_mode": p.mode if world > 1 else None, "shard_mode_reason": shard_why if world > 1 else None,
                        # how the key is held: window tables, or plain bases and WHY (a slower prover: c <= 16, more windows)
                        "pk": p.pk_info()},
-            "roofline": roofline, "roofline_ntt": roofline_ntt, "value_incl_h2d": h2d,
+            "phases_ms_per_step": {k_: round(v / args.steps, 3) for k_, v in phase_acc.items()},
+        }
+        if args.full:
+            out["roofline"], out["roofline_ntt"] = roofline_objects(p, args, world, last_tm, bucket_g1, bucket_g2, phase_acc)
+            out["value_incl_h2d"] = h2d
             # SURVEY.md 8(d) defines the metric with the witness on the HOST at entry; the bench contract defines `value` with the
             # inputs resident in HBM.  Both are reported: `value` above (resident), this one with the 32 B x num_variables upload
             # from pinned host memory inside every timed call.
-            "value_survey_8d": (h2d or {}).get("pinned", {}).get("value"),
-            "phases_ms_per_step": {k_: round(v / args.steps, 3) for k_, v in phase_acc.items()},
-        }
+            out["value_survey_8d"] = (h2d or {}).get("pinned", {}).get("value")
         if dist is not None:
             out["rccl_world"] = dist.get_world_size()
             out["collective_backend"] = "rccl (torch.distributed nccl)" if backend == "nccl" else backend
@@ -910,14 +944,14 @@ def main():
             out["distinct_devices"] = len({(r_["device"], r_["device_uuid_word"]) for r_ in ranks_seen})
             if collective_ms is not None:
                 out["collective_ms"] = collective_ms
-        if world == 1 and not args.no_projection:
+        if args.full and world == 1 and not args.no_projection:
             try:
                 out["projected_scaling"] = projected_scaling(p, ms_per_step, args.steps, dist_wm_ok)
                 chk = p.finalize([p.partial()])   # the key is whole again (rebind undone): same proof as before
                 out["projected_scaling"]["headline_proof_unchanged_after"] = bool((chk == proof).all())
             except Exception as e:  # noqa: BLE001
                 out["projected_scaling"] = {"error": repr(e)}
-        if world == 1 and not args.no_pipelined:
+        if args.full and world == 1 and not args.no_pipelined:
             try:
                 out["pipelined"] = pipelined_throughput(p, local_rank, max(args.steps, 10), proof)
                 out["value_pipelined"] = out["pipelined"]["value"]
@@ -927,7 +961,7 @@ def main():
             import hashlib
 
             out["proof_sha256"] = hashlib.sha256(proof.tobytes()).hexdigest()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.curve, args.cpu_log2, 1, args.cpu_threads, args.key,
                                                    reuse=p if args.cpu_log2 == args.log2 else None)

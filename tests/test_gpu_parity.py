@@ -531,13 +531,14 @@ def test_error_paths(env, orc, g):
 
 
 @pytest.mark.parametrize("launcher", ["self", "torchrun"])
-def test_bench_two_ranks_one_gpu(launcher):
+def test_bench_two_ranks_one_gpu(launcher, tmp_path):
     """bench.py's N > 1 path (sharded key, all-gather of partial records, finalize on every rank, max-over-ranks timing)
     with two ranks on the one visible GPU (gloo carries the exchange; RCCL refuses two ranks per device).  The bench
     itself asserts that all ranks produce the same proof; here we also require it to equal the single-rank proof.
     launcher = "self": exactly `python bench.py --gpus 2 ...` with NO launcher and no WORLD_SIZE in the environment (bench.py
     starts its own ranks); "torchrun": the contract's torch.distributed.run command line.  The configs[4] leg (a second, larger
-    instance timed after the headline one, reported as a field) runs here at 2^13 instead of 2^24."""
+    instance timed after the headline one, reported as a field) runs here at 2^13 instead of 2^24.  Both lines run with --full (the
+    collective timings, configs[4] and the projection are --full legs), and both dump their last proof (--dump-outputs, rank 0)."""
     import json
     import os
     import subprocess
@@ -547,7 +548,8 @@ def test_bench_two_ranks_one_gpu(launcher):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(G16_BENCH_BACKEND="gloo", G16_BENCH_FORCE_DEVICE0="1", G16_BENCH_PRINT_PROOF="1")
     port = 29000 + os.getpid() % 2000
-    tail = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--log2", "12", "--no-cpu-baseline", "--configs4", "on", "--configs4-log2", "13"]
+    tail = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--log2", "12", "--no-cpu-baseline", "--full", "--configs4", "on", "--configs4-log2", "13",
+            "--dump-outputs", str(tmp_path / "two")]
     # the two ways of cutting the MSMs over the ranks: "self" leaves the default (auto -> bucket-space shards: the whole key's tables
     # fit easily at this size), "torchrun" forces base-range shards
     want_mode = "bucket" if launcher == "self" else "base"
@@ -563,12 +565,14 @@ def test_bench_two_ranks_one_gpu(launcher):
     lines2 = [l for l in out2.stdout.splitlines() if l.startswith("{")]
     assert len(lines2) == 1, "exactly one JSON line, from rank 0"
     d2 = json.loads(lines2[-1])
-    base1 = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
-    out1 = subprocess.run(base1 + ["--log2", "12"], env=env, capture_output=True, text=True, timeout=600)
+    base1 = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"]
+    out1 = subprocess.run(base1 + ["--log2", "12", "--dump-outputs", str(tmp_path / "one")], env=env, capture_output=True, text=True, timeout=600)
     assert out1.returncode == 0, out1.stderr[-2000:]
     d1 = json.loads([l for l in out1.stdout.splitlines() if l.startswith("{")][-1])
     assert d2["n_gpus"] == 2 and d1["n_gpus"] == 1 and d2["scaling"] == "strong"
     assert d2["proof_sha256"] == d1["proof_sha256"]
+    for name in ("a", "b", "c"):
+        assert (np.load(tmp_path / "two" / f"proof_{name}.npy") == np.load(tmp_path / "one" / f"proof_{name}.npy")).all(), name
     assert d2["config"]["shard_mode"] == want_mode and d2["config"]["pk"]["table_fallback"] == 0
     assert d2["config"]["pk"]["bucket_shard_world"] == (2 if want_mode == "bucket" else 1)
     assert d2["configs4"]["shard_mode"] == want_mode
@@ -593,10 +597,12 @@ def test_bench_two_ranks_one_gpu(launcher):
     assert c4["proof_sha256"] == d13["proof_sha256"]
 
 
-def test_bench_rccl_single_rank():
+def test_bench_rccl_single_rank(tmp_path):
     """the collective path of bench.py over RCCL itself (backend "nccl"): one rank on the one visible GPU -- process group
     bound to the device, all-gather of the partial records as device tensors, all-reduce of the timing, barrier.  Proof
-    must equal the plain single-GPU run's."""
+    must equal the plain single-GPU run's.  That plain run (no --full) reports the headline and nothing that needs work of its
+    own, and --dump-outputs writes the very proof it hashed."""
+    import hashlib
     import json
     import os
     import subprocess
@@ -609,11 +615,18 @@ def test_bench_rccl_single_rank():
     envd = dict(env, G16_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     outd = subprocess.run(base, env=envd, capture_output=True, text=True, timeout=600)
     assert outd.returncode == 0, outd.stderr[-3000:]
-    out1 = subprocess.run(base, env=env, capture_output=True, text=True, timeout=600)
+    out1 = subprocess.run(base + ["--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     assert out1.returncode == 0, out1.stderr[-3000:]
     dd = json.loads([l for l in outd.stdout.splitlines() if l.startswith("{")][-1])
     d1 = json.loads([l for l in out1.stdout.splitlines() if l.startswith("{")][-1])
     assert dd["proof_sha256"] == d1["proof_sha256"] and dd["n_gpus"] == 1
+    assert d1["steps"] == 2 and d1["ms_per_step"] > 0 and d1["value"] > 0
+    assert not {"roofline", "roofline_ntt", "value_incl_h2d", "projected_scaling", "pipelined", "cpu_baseline"} & set(d1), sorted(d1)
+    dumped = [np.load(tmp_path / f"proof_{name}.npy") for name in ("a", "b", "c")]
+    assert [x.shape for x in dumped] == [(2, 12), (4, 12), (2, 12)] and all(x.dtype == np.float64 for x in dumped)
+    words = np.concatenate([x.reshape(-1) for x in dumped])
+    assert (words == np.floor(words)).all() and words.min() >= 0 and words.max() < 2**32
+    assert hashlib.sha256(words.astype(np.uint32).tobytes()).hexdigest() == d1["proof_sha256"]
     # the distributed witness map's RCCL path with the one rank a one-GPU box has: stages enqueued by g16_dwm_stage_async on the
     # library's stream, all_to_all_single issued on that same stream through torch's ExternalStream, g16_prove_partial_h behind them
     envw = dict(envd, G16_BENCH_FORCE_DWM="1", G16_DWM_FORCE_COLLECTIVE="1", MASTER_PORT=str(port + 1))

@@ -10,7 +10,7 @@ for v in main "$@" main; do
     echo "variant $v parity: $(tail -1 $O/pytest_ntt$v.log)"
   fi
   for k in 22 20; do
-    timeout 300 python bench.py --log2 $k --steps 6 --warmup 2 --no-cpu-baseline > $O/ntt_${v}_k$k.json 2> $O/ntt_${v}_k$k.err
+    timeout 300 python bench.py --full --log2 $k --steps 6 --warmup 2 --no-cpu-baseline > $O/ntt_${v}_k$k.json 2> $O/ntt_${v}_k$k.err
     python - $O/ntt_${v}_k$k.json $v $k <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")]

@@ -15,7 +15,7 @@ PY
 }
 single() {
   name=$1; shift
-  env "$@" timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-pipelined --no-projection > $O/single_$name.json 2> $O/single_$name.err
+  env "$@" timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-pipelined --no-projection > $O/single_$name.json 2> $O/single_$name.err
   python - $O/single_$name.json $name <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")]

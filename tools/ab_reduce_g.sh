@@ -3,7 +3,7 @@
 O=gpurun_out/$1; mkdir -p $O
 for v in 8 plan 8 plan 32; do
   if [ $v = plan ]; then unset G16_MSM_REDUCE_G; else export G16_MSM_REDUCE_G=$v; fi
-  timeout 300 python bench.py --steps 8 --warmup 2 --no-cpu-baseline > $O/redg_$v.json 2> $O/redg_$v.err
+  timeout 300 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline > $O/redg_$v.json 2> $O/redg_$v.err
   python - $O/redg_$v.json $v <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")]

@@ -4,7 +4,7 @@
 O=gpurun_out/$1; mkdir -p $O
 single() { # name, env...
   name=$1; shift
-  env "$@" timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline > $O/seg_single_$name.json 2> $O/seg_single_$name.err
+  env "$@" timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $O/seg_single_$name.json 2> $O/seg_single_$name.err
   python - $O/seg_single_$name.json $name <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")]

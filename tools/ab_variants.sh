@@ -10,7 +10,7 @@ for v in "$@"; do
   # parity: every variant must produce the SAME proof bytes over the same key / witness / r, s (hash in the JSON line); the full
   # parity tier is run on the variant that is kept (a per-variant pytest subset cost 140 s of box time each in round 4)
   par=""
-  G16_BENCH_PRINT_PROOF=1 timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline $AB_BENCH_ARGS > $O/ab_${i}_$v.json 2> $O/ab_${i}_$v.err
+  G16_BENCH_PRINT_PROOF=1 timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline $AB_BENCH_ARGS > $O/ab_${i}_$v.json 2> $O/ab_${i}_$v.err
   python - $O/ab_${i}_$v.json $v "$par" <<'PY'
 import json, sys
 l = [x for x in open(sys.argv[1]) if x.startswith("{")]

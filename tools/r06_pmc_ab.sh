@@ -8,7 +8,7 @@ run() {  # tag, counters..., env
   tag=$1; shift
   ctrs=$1; shift
   timeout 400 env "$@" rocprofv3 --pmc $ctrs -d $O/pmc_$tag -o pmc --output-format csv -- \
-     python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pipelined --no-projection > $O/bench_$tag.json 2> $O/bench_$tag.err
+     python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pipelined --no-projection > $O/bench_$tag.json 2> $O/bench_$tag.err
   echo "$tag rc=$?"
   python - $O/pmc_$tag "$ctrs" $tag >> $O/summary.txt <<'PY'
 import sys, json, subprocess
