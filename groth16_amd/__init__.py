@@ -15,14 +15,19 @@ Reference interface mirrored (paths relative to /root/reference):
   rerandomize_proof / Groth16.rerandomize_proof      src/prover.rs:223-250 (host: three scalar multiplications)
   Groth16.create_proof_with_reduction / prove / setup src/prover.rs:173-217, src/lib.rs:63-82, src/generator.rs:20-45 -- host-side
       synthesis (groth16_amd.r1cs: ConstraintSystem, Variable, lc, ConstraintSynthesizer) in front of the GPU calls
+  Groth16.prepare_verifying_key / prepare_inputs / verify_proof_with_prepared_inputs / verify_proof, process_vk /
+      verify_with_processed_vk                      src/verifier.rs:13-76, src/lib.rs:84-96 (GPU batch: verify_proofs)
+  VerifyingKey / PreparedVerifyingKey               src/data_structures.rs:31-66
 """
 from .binding import (G16Error, Lib, PolynomialDegreeTooLarge, SynthesisError, UnexpectedIdentity, lib, FQ_LIMBS, CURVE_ID)  # noqa: F401
 from .groth16 import (ConstraintMatrices, Groth16, LibsnarkReduction, PipelinedProver, Proof, ProvingKey, ShardedProver, finalize_host,  # noqa: F401
                       rerandomize_proof, shard_ranges)
+from .binding import MalformedVerifyingKey  # noqa: F401
+from .verifier import PreparedVerifyingKey, VerifyingKey, host_pairing, verify_proof_host  # noqa: F401
 from .r1cs import AssignmentMissing, ConstraintSynthesizer, ConstraintSystem, LinearCombination, Variable, lc  # noqa: F401
 
 __all__ = [
     "Groth16", "LibsnarkReduction", "ConstraintMatrices", "ProvingKey", "Proof", "ShardedProver", "PipelinedProver", "G16Error", "SynthesisError",
     "PolynomialDegreeTooLarge", "UnexpectedIdentity", "lib", "ConstraintSystem", "ConstraintSynthesizer", "Variable", "LinearCombination",
-    "lc", "AssignmentMissing",
+    "lc", "AssignmentMissing", "VerifyingKey", "PreparedVerifyingKey", "MalformedVerifyingKey", "verify_proof_host", "host_pairing",
 ]

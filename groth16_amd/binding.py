@@ -35,6 +35,10 @@ class UnexpectedIdentity(SynthesisError):
     """gamma or delta is zero (generator.rs:110-111)"""
 
 
+class MalformedVerifyingKey(SynthesisError):
+    """public inputs + 1 != gamma_abc_g1 (verifier.rs:29-31)"""
+
+
 class InvalidData(G16Error):
     """ark_serialize::SerializationError::InvalidData"""
 
@@ -63,6 +67,10 @@ class ToxicWasteC(C.Structure):
 class ParamsViewC(C.Structure):
     _fields_ = [(n, u64p) for n in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2", "gamma_g2", "gamma_abc_g1")] + \
                [(n, C.c_void_p) for n in ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query")] + [("flags", C.c_uint32)]
+
+
+class VkViewC(C.Structure):
+    _fields_ = [(n, u64p) for n in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")] + [("n_gamma_abc", C.c_uint64)]
 
 
 class ProofC(C.Structure):
@@ -113,6 +121,8 @@ EXPORTS = [
     "g16_host_qap_evaluations", "g16_serialized_point_size", "g16_serialize_points", "g16_deserialize_points",
     "g16_pk_load_bucket_shard", "g16_pk_rebind_bucket_shard", "g16_pk_get_info", "g16_msm_bucket_shard", "g16_host_msm_model_shard",
     "g16_abi_version", "g16_struct_size", "g16_get_timings_sized", "g16_pk_get_info_sized",
+    "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
+    "g16_host_pairing", "g16_host_verify",
 ]
 
 
@@ -214,6 +224,16 @@ class Lib:
         c.g16_deserialize_points.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_uint64, C.c_int, u64p]
         c.g16_host_qap_evaluations.argtypes = [C.c_int, C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p, u64p]
 
+        c.g16_pvk_load.argtypes = [C.c_void_p, C.POINTER(VkViewC), C.POINTER(C.c_void_p)]
+        c.g16_pvk_free.argtypes = [C.c_void_p]
+        c.g16_pvk_free.restype = None
+        c.g16_pvk_alpha_beta.argtypes = [C.c_void_p, u64p]
+        c.g16_verify_batch.argtypes = [C.c_void_p, C.c_void_p, u64p, C.c_uint64, u64p, C.c_uint64, C.c_void_p]
+        c.g16_verify_batch_prepared.argtypes = [C.c_void_p, C.c_void_p, u64p, u64p, C.c_uint64, C.c_void_p]
+        c.g16_pairing.argtypes = [C.c_void_p, u64p, u64p, C.c_uint64, u64p]
+        c.g16_host_pairing.argtypes = [C.c_int, u64p, u64p, C.c_uint64, u64p]
+        c.g16_host_verify.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, u64p, C.c_uint64, C.c_void_p]
+
     def check(self, status: int):
         if status == 0:
             return
@@ -227,6 +247,8 @@ class Lib:
             raise UnexpectedIdentity(status, msg)
         if status == 9:
             raise InvalidData(status, msg)
+        if status == 11:
+            raise MalformedVerifyingKey(status, msg)
         raise G16Error(status, msg)
 
     def version(self) -> str:

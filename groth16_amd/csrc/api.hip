@@ -79,6 +79,19 @@ static void diag_counts(g16_diag* out) {
 #endif
 }
 
+// the devices and streams of a context, for the verifier (verify.hip): one entry, or one per device of a multi-device context
+namespace g16 {
+int ctx_devices(const g16_ctx* ctx, int* curve, std::vector<int>& devs, std::vector<hipStream_t>& streams) {
+    if (!ctx) return G16_ERR_BAD_ARG;
+    *curve = ctx->curve;
+    devs.clear();
+    streams.clear();
+    if (ctx->subs.empty()) { devs.push_back(ctx->device); streams.push_back(ctx->stream); }
+    for (const g16_ctx* s : ctx->subs) { devs.push_back(s->device); streams.push_back(s->stream); }
+    return G16_OK;
+}
+}  // namespace g16
+
 // g16_pk_load on a multi-device context: the retry with base ranges after an automatic bucket-space load ran out of memory
 static thread_local bool g_multi_force_base = false;
 
@@ -914,6 +927,7 @@ const char* g16_strerror(int status) {
         case G16_ERR_UNEXPECTED_IDENTITY: return "unexpected identity: gamma or delta is zero";
         case G16_ERR_INVALID_DATA: return "invalid data: the bytes do not encode a point of the group";
         case G16_ERR_NO_PEER_ACCESS: return "two devices of a multi-device context have no peer access (G16_MULTI_REQUIRE_PEER)";
+        case G16_ERR_MALFORMED_VK: return "malformed verifying key: public inputs + 1 != gamma_abc_g1";
         default: return "unknown status";
     }
 }
@@ -929,6 +943,7 @@ uint64_t g16_struct_size(int which) {
         case G16_STRUCT_PROOF: return sizeof(g16_proof);
         case G16_STRUCT_PARTIAL: return sizeof(g16_partial);
         case G16_STRUCT_PK_VIEW: return sizeof(g16_pk_view);
+        case G16_STRUCT_VK_VIEW: return sizeof(g16_vk_view);
         default: return 0;
     }
 }

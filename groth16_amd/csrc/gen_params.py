@@ -6,6 +6,12 @@ __graft_entry__.build() / the Makefile; output is committed so the GPU box needs
 Constants: BLS12-381 and BN254 field moduli, Fr multiplicative generator and 2-adicity
 (ark-bls12-381 / ark-bn254 0.5.0 Fr configs: GENERATOR = 7 / 5, TWO_ADICITY = 32 / 28),
 curve coefficients and standard generators.
+
+Pairing constants (pairing.hpp), in the 30-bit Montgomery form the pairing arithmetic runs in (x * 2^(30 NL) mod q):
+the sextic non-residue xi = s + u (Fq6 = Fq2[v]/(v^3 - xi), Fq12 = Fq6[w]/(w^2 - v), so w^6 = xi), the Frobenius
+coefficients gamma[j][k] = xi^(k (q^j - 1) / 6) that map a w^k coefficient under the j-th power of Frobenius (j = 1..3,
+k = 1..5: Fq6 = even k, Fq12 = odd k; Fq2's own Frobenius is conjugation), 1/2, and the loop parameters: BLS12-381
+|x| with x negative, BN254 6x + 2 as non-adjacent signed digits and x for the final exponentiation.
 """
 import os
 
@@ -13,7 +19,7 @@ CURVES = {
     "Bls12_381": dict(
         q=0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB,
         r=0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
-        gen=7, s=32, b1=4, b2=(4, 4),
+        gen=7, s=32, b1=4, b2=(4, 4), xi=1, x=-0xD201000000010000,
         g1=(0x17F1D3A73197D7942695638C4FA9AC0FC3688C4F9774B905A14E3A3F171BAC586C55E83FF97A1AEFFB3AF00ADB22C6BB,
             0x08B3F481E3AAA0F1A09E30ED741D8AE4FCF5E095D5D00AF600DB18CB2C04B3EDD03CC744A2888AE40CAA232946C5E7E1),
         g2=(0x024AA2B2F08F0A91260805272DC51051C6E47AD4FA403B02B4510B647AE3D1770BAC0326A805BBEFD48056C8C121BDB8,
@@ -25,6 +31,7 @@ CURVES = {
         q=21888242871839275222246405745257275088696311157297823662689037894645226208583,
         r=21888242871839275222246405745257275088548364400416034343698204186575808495617,
         gen=5, s=28, b1=3, b2=None,  # 3/(9+u), computed below
+        xi=9, x=4965661367192848881,
         g1=(1, 2),
         g2=(10857046999023057135944570762232829481370756359578518086990519993285655852781,
             11559732032986387107991004021392285783925812861821192530917403151452391805634,
@@ -97,6 +104,84 @@ def field_struct(name, p):
     return "\n".join(out), n, R
 
 
+def limbs30_of(v, p):
+    nl = (p.bit_length() + 29) // 30
+    return [(v >> (30 * i)) & ((1 << 30) - 1) for i in range(nl - 1)] + [v >> (30 * (nl - 1))]
+
+
+def mont30(v, p):
+    nl = (p.bit_length() + 29) // 30
+    return limbs30_of(v % p * (1 << (30 * nl)) % p, p)
+
+
+def fq2_mul(a, b, q):
+    return ((a[0] * b[0] - a[1] * b[1]) % q, (a[0] * b[1] + a[1] * b[0]) % q)
+
+
+def fq2_pow(a, e, q):
+    r = (1, 0)
+    for bit in bin(e)[2:]:
+        r = fq2_mul(r, r, q)
+        if bit == "1":
+            r = fq2_mul(r, a, q)
+    return r
+
+
+def naf(n):
+    out = []
+    while n:
+        if n & 1:
+            d = 2 - (n & 3)
+            n -= d
+        else:
+            d = 0
+        out.append(d)
+        n >>= 1
+    return out  # little-endian digits in {-1, 0, 1}
+
+
+def pairing_consts(c):
+    """lines of the Consts struct that pairing.hpp reads"""
+    q, xi, x = c["q"], (c["xi"], 1), c["x"]
+    nl = (q.bit_length() + 29) // 30
+    o = []
+    o.append("    static constexpr int XI = %d;  // xi = XI + u" % c["xi"])
+    gam = []
+    for j in (1, 2, 3):
+        for k in range(1, 6):
+            g = fq2_pow(xi, k * (q ** j - 1) // 6, q)
+            gam.append(mont30(g[0], q))
+            gam.append(mont30(g[1], q))
+    o.append("    // gamma[j-1][k-1][c] = component c of xi^(k (q^j - 1) / 6), 30-bit Montgomery form")
+    o.append("    G16_HD static constexpr uint32_t frob30(int j, int k, int c, int i) {")
+    o.append("        constexpr uint32_t t[30][%d] = {%s};" % (nl, ", ".join(arr(g) for g in gam)))
+    o.append("        return t[((j - 1) * 5 + (k - 1)) * 2 + c][i];")
+    o.append("    }")
+    o.append("    G16_HD static constexpr uint32_t two_inv30(int i) {")
+    o.append("        constexpr uint32_t t[%d] = %s;" % (nl, arr(mont30(pow(2, q - 2, q), q))))
+    o.append("        return t[i];")
+    o.append("    }")
+    o.append("    static constexpr uint64_t ATE_X_ABS = 0x%016xull;" % abs(x))
+    o.append("    static constexpr bool ATE_X_NEG = %s;" % ("true" if x < 0 else "false"))
+    if c["xi"] == 1:
+        # BLS12: the Miller loop runs over |x|; the hard part of the final exponentiation uses (x - 1)^2 / 3
+        assert (x - 1) ** 2 % 3 == 0
+        e = (x - 1) ** 2 // 3
+        o.append("    static constexpr uint64_t HARD_E_LO = 0x%016xull, HARD_E_HI = 0x%016xull;  // (x - 1)^2 / 3" % (e & (2 ** 64 - 1), e >> 64))
+        o.append("    static constexpr int ATE_NAF_LEN = 0;")
+        o.append("    G16_HD static constexpr int ate_naf(int) { return 0; }")
+    else:
+        d = naf(6 * x + 2)
+        assert sum(v << i for i, v in enumerate(d)) == 6 * x + 2
+        o.append("    static constexpr uint64_t HARD_E_LO = 0, HARD_E_HI = 0;")
+        o.append("    static constexpr int ATE_NAF_LEN = %d;  // non-adjacent form of 6x + 2, little-endian" % len(d))
+        o.append("    G16_HD static constexpr int ate_naf(int i) {")
+        o.append("        constexpr signed char t[%d] = {%s};" % (len(d), ", ".join(str(v) for v in d)))
+        o.append("        return t[i];")
+        o.append("    }")
+    return o
+
+
 def mont(v, p, R, n):
     return arr(limbs32(v % p * R % p, n))
 
@@ -135,6 +220,7 @@ def main():
             o.append("        constexpr uint32_t t[%d] = %s;" % (n, mont(val, p, R, n)))
             o.append("        return t[i];")
             o.append("    }")
+        o.extend(pairing_consts(c))
         o.append("};")
     o.append("}  // namespace g16")
     with open(os.path.join(here, "params_gen.hpp"), "w") as f:

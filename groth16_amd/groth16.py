@@ -459,6 +459,61 @@ class Groth16:
         """prover.rs:155-168 on a circuit: r = s = 0 (same as create_proof_with_reduction_no_zk(circuit, pk))"""
         return self.create_proof_with_reduction_no_zk(circuit, pk)
 
+    # -- verifier.rs:13-76, lib.rs:84-96 ----------------------------------------------------------
+    def prepare_verifying_key(self, vk) -> "PreparedVerifyingKey":
+        """verifier.rs:13-20: e(alpha, beta), -gamma / -delta prepared and gamma_abc_g1's window tables, resident on this object's
+        GPU(s).  `vk`: a VerifyingKey or a ProvingKey that carries gamma_g2 / gamma_abc_g1."""
+        from .verifier import PreparedVerifyingKey
+        return PreparedVerifyingKey(self._ctx, vk)
+
+    def process_vk(self, vk) -> "PreparedVerifyingKey":   # lib.rs:84-86
+        return self.prepare_verifying_key(vk)
+
+    def prepare_inputs(self, pvk, public_inputs) -> np.ndarray:
+        """verifier.rs:25-39 (host): gamma_abc_g1[0] + sum x_i gamma_abc_g1[i + 1] as G1 affine; MalformedVerifyingKey on a length
+        mismatch"""
+        from .binding import MalformedVerifyingKey
+        from .verifier import as_vk
+        vk = as_vk(pvk.vk if hasattr(pvk, "vk") else pvk)
+        L = FQ_LIMBS[self.curve]
+        x = [_c(v).reshape(4) for v in public_inputs] if len(public_inputs) else []
+        bases = _c(vk.gamma_abc_g1).reshape(-1, 2 * L)
+        if len(x) + 1 != bases.shape[0]:
+            raise MalformedVerifyingKey(11, "malformed verifying key: public inputs + 1 != gamma_abc_g1")
+        lb, cid = self._ctx.lib, CURVE_ID[self.curve]
+        acc = bases[0].copy()
+        for xi, b in zip(x, bases[1:]):
+            k, t, s = np.zeros(4, dtype=np.uint64), np.zeros(2 * L, dtype=np.uint64), np.zeros(2 * L, dtype=np.uint64)
+            lb.check(lb.c.g16_host_field_op(cid, 0, 4, ptr64(_c(xi)), None, ptr64(k)))          # canonical x_i
+            lb.check(lb.c.g16_host_group_op(cid, 0, 1, ptr64(_c(b)), ptr64(k), ptr64(t)))       # x_i * base
+            lb.check(lb.c.g16_host_group_op(cid, 0, 0, ptr64(acc), ptr64(t), ptr64(s)))         # acc + that
+            acc = s
+        return acc
+
+    def verify_proof_with_prepared_inputs(self, pvk, proof: Proof, prepared_inputs: np.ndarray) -> bool:   # verifier.rs:44-65
+        from .verifier import verify_batch_prepared
+        return bool(verify_batch_prepared(self._ctx, pvk, [proof], _c(prepared_inputs).reshape(1, -1))[0] == 1)
+
+    def verify_proof(self, pvk, proof: Proof, public_inputs) -> bool:   # verifier.rs:68-76
+        return bool(self.verify_proofs(pvk, [proof], [public_inputs])[0])
+
+    def verify_with_processed_vk(self, pvk, x, proof: Proof) -> bool:   # lib.rs:88-96
+        return self.verify_proof(pvk, proof, x)
+
+    def verify_proofs(self, pvk, proofs: Sequence[Proof], public_inputs_list) -> np.ndarray:
+        """verify_proof over a batch, one GPU lane per proof: a bool per proof"""
+        return self.verify_verdicts(pvk, proofs, public_inputs_list) == 1
+
+    def verify_verdicts(self, pvk, proofs, public_inputs_list) -> np.ndarray:
+        """g16_verify_batch's verdict bytes: 1 accept, 0 reject, 2 a point of the proof is off its curve"""
+        from .verifier import verify_batch
+        return verify_batch(self._ctx, pvk, proofs, public_inputs_list)
+
+    def pairing(self, g1s: np.ndarray, g2s: np.ndarray) -> np.ndarray:
+        """prod e(g1s[i], g2s[i]) on the GPU (GT as arkworks' 12 Fq limbs)"""
+        from .verifier import device_pairing
+        return device_pairing(self._ctx, g1s, g2s)
+
     # -- prover.rs:223-250 ----------------------------------------------------------------------
     def rerandomize_proof(self, vk: ProvingKey, proof: Proof, rng=None) -> Proof:
         return rerandomize_proof(self.curve, vk, proof, rng)

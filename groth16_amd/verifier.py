@@ -1,0 +1,161 @@
+"""Groth16 verification (src/verifier.rs:13-76, src/lib.rs:84-96) through the library's pairing: the batch form runs one proof per
+GPU lane (g16_verify_batch); ``verify_proof_host`` runs the same C++ templates on the CPU (g16_host_verify)."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+import numpy as np
+
+from .binding import CURVE_ID, FQ_LIMBS, VkViewC, lib, ptr64
+
+
+def _c(a) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(a, dtype=np.uint64))
+
+
+@dataclass
+class VerifyingKey:
+    """src/data_structures.rs:31-44; affine Montgomery limbs (gamma_abc_g1: (n, 2 * FQ) array)."""
+
+    curve: str
+    alpha_g1: np.ndarray
+    beta_g2: np.ndarray
+    gamma_g2: np.ndarray
+    delta_g2: np.ndarray
+    gamma_abc_g1: np.ndarray
+
+    @staticmethod
+    def from_proving_key(pk) -> "VerifyingKey":
+        if pk.gamma_g2 is None or pk.gamma_abc_g1 is None:
+            raise ValueError("this ProvingKey carries no gamma_g2 / gamma_abc_g1 (a key made by setup() or generate_parameters has them)")
+        return VerifyingKey(pk.curve, _c(pk.alpha_g1), _c(pk.beta_g2), _c(pk.gamma_g2), _c(pk.delta_g2), _c(pk.gamma_abc_g1))
+
+    def view(self):
+        """(g16_vk_view, the arrays it points into)"""
+        L = FQ_LIMBS[self.curve]
+        keep = [_c(self.alpha_g1).reshape(-1), _c(self.beta_g2).reshape(-1), _c(self.gamma_g2).reshape(-1), _c(self.delta_g2).reshape(-1),
+                _c(self.gamma_abc_g1).reshape(-1, 2 * L)]
+        v = VkViewC(*[ptr64(a) for a in keep], keep[4].shape[0])
+        return v, keep
+
+    @property
+    def num_public(self) -> int:
+        return _c(self.gamma_abc_g1).reshape(-1, 2 * FQ_LIMBS[self.curve]).shape[0] - 1
+
+
+def as_vk(vk) -> VerifyingKey:
+    return vk if isinstance(vk, VerifyingKey) else VerifyingKey.from_proving_key(vk)
+
+
+class PreparedVerifyingKey:
+    """src/data_structures.rs:56-66: owns the device-resident g16_pvk (e(alpha, beta), the prepared lines of -gamma and -delta,
+    the window tables of gamma_abc_g1) of one context."""
+
+    def __init__(self, ctx, vk):
+        self.vk = as_vk(vk)
+        self.curve = self.vk.curve
+        self._ctx = ctx
+        self.handle = C.c_void_p()
+        view, keep = self.vk.view()
+        lb = lib()
+        lb.check(lb.c.g16_pvk_load(ctx.handle, C.byref(view), C.byref(self.handle)))
+        del keep
+
+    @property
+    def alpha_g1_beta_g2(self) -> np.ndarray:
+        """GT value as arkworks' 12 Fq (Montgomery limbs), c0.c0.c0 ... c1.c2.c1"""
+        out = np.zeros(12 * FQ_LIMBS[self.curve], dtype=np.uint64)
+        lb = lib()
+        lb.check(lb.c.g16_pvk_alpha_beta(self.handle, ptr64(out)))
+        return out
+
+    def close(self):
+        if self.handle:
+            lib().c.g16_pvk_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _flat_proofs(proofs, curve) -> np.ndarray:
+    L = FQ_LIMBS[curve]
+    if isinstance(proofs, np.ndarray):
+        return _c(proofs).reshape(-1, 8 * L)
+    if not len(proofs):
+        return np.zeros((0, 8 * L), np.uint64)
+    return _c(np.stack([p if isinstance(p, np.ndarray) else p.flat() for p in proofs])).reshape(-1, 8 * L)
+
+
+def verify_batch(ctx, pvk: PreparedVerifyingKey, proofs, public_inputs_list) -> np.ndarray:
+    """verdict bytes: 1 accept, 0 reject, 2 a proof point is not on its curve"""
+    flat = _flat_proofs(proofs, pvk.curve)
+    n = flat.shape[0]
+    if len(public_inputs_list) != n:
+        raise ValueError("one public-input vector per proof")
+    rows = [_c(x).reshape(-1, 4) if len(x) else np.zeros((0, 4), dtype=np.uint64) for x in public_inputs_list]
+    num_public = rows[0].shape[0] if n else pvk.vk.num_public
+    if any(r.shape[0] != num_public for r in rows):
+        raise ValueError("every proof of a batch needs the same number of public inputs")
+    x = np.ascontiguousarray(np.concatenate(rows).reshape(-1)) if n and num_public else np.zeros(0, dtype=np.uint64)
+    verdicts = np.zeros(n, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_verify_batch(ctx.handle, pvk.handle, ptr64(flat.reshape(-1)), n, ptr64(x) if x.size else None, num_public,
+                                   verdicts.ctypes.data_as(C.c_void_p)))
+    return verdicts
+
+
+def verify_batch_prepared(ctx, pvk: PreparedVerifyingKey, proofs, prepared_inputs) -> np.ndarray:
+    flat = _flat_proofs(proofs, pvk.curve)
+    n = flat.shape[0]
+    ic = _c(prepared_inputs).reshape(n, 2 * FQ_LIMBS[pvk.curve])
+    verdicts = np.zeros(n, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_verify_batch_prepared(ctx.handle, pvk.handle, ptr64(flat.reshape(-1)), ptr64(ic.reshape(-1)), n, verdicts.ctypes.data_as(C.c_void_p)))
+    return verdicts
+
+
+def verify_proof_host(curve: str, vk, proof, public_inputs) -> bool:
+    """verify_proof (verifier.rs:68-76) on the CPU through g16_host_verify; raises MalformedVerifyingKey for a wrong input count.
+    A proof with a point off its curve is rejected (False)."""
+    return host_verdict(curve, vk, proof, public_inputs) == 1
+
+
+def host_verdict(curve: str, vk, proof, public_inputs) -> int:
+    """g16_host_verify's verdict byte (1 / 0 / 2)"""
+    vkk = as_vk(vk)
+    view, keep = vkk.view()
+    x = _c(public_inputs).reshape(-1) if len(public_inputs) else np.zeros(0, dtype=np.uint64)
+    flat = _c(proof if isinstance(proof, np.ndarray) else proof.flat()).reshape(-1)
+    v = np.zeros(1, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_host_verify(CURVE_ID[curve], C.byref(view), ptr64(flat), ptr64(x) if x.size else None, x.size // 4,
+                                  v.ctypes.data_as(C.c_void_p)))
+    del keep
+    return int(v[0])
+
+
+def host_pairing(curve: str, g1s, g2s) -> np.ndarray:
+    """prod e(g1s[i], g2s[i]) on the CPU, as arkworks' 12 Fq limbs"""
+    L = FQ_LIMBS[curve]
+    a = _c(g1s).reshape(-1, 2 * L)
+    b = _c(g2s).reshape(-1, 4 * L)
+    out = np.zeros(12 * L, dtype=np.uint64)
+    lb = lib()
+    lb.check(lb.c.g16_host_pairing(CURVE_ID[curve], ptr64(a.reshape(-1)) if a.size else None, ptr64(b.reshape(-1)) if b.size else None,
+                                   a.shape[0], ptr64(out)))
+    return out
+
+
+def device_pairing(ctx, g1s, g2s) -> np.ndarray:
+    L = FQ_LIMBS[ctx.curve]
+    a = _c(g1s).reshape(-1, 2 * L)
+    b = _c(g2s).reshape(-1, 4 * L)
+    out = np.zeros(12 * L, dtype=np.uint64)
+    lb = lib()
+    lb.check(lb.c.g16_pairing(ctx.handle, ptr64(a.reshape(-1)) if a.size else None, ptr64(b.reshape(-1)) if b.size else None, a.shape[0],
+                              ptr64(out)))
+    return out

@@ -9,6 +9,9 @@
  *   g16_ntt              <->  EvaluationDomain::{fft,ifft}_in_place (+coset)      src/r1cs_to_qap.rs:201-232
  *   g16_pk_load          <->  &ProvingKey<E>                                      src/data_structures.rs:125-143
  *   g16_circuit_load     <->  &ConstraintMatrices<F>, num_inputs, num_constraints src/prover.rs:30-32
+ *   g16_pvk_load         <->  prepare_verifying_key / process_vk                    src/verifier.rs:13-20, src/lib.rs:84-86
+ *   g16_verify_batch     <->  verify_proof (per proof)                             src/verifier.rs:25-76
+ *   g16_verify_batch_prepared <-> verify_proof_with_prepared_inputs               src/verifier.rs:44-65
  *   g16_prove_partial / g16_prove_finalize: the same proof with the MSM base set sharded
  *                             over several GPUs (one process per GPU; the host exchanges the
  *                             fixed-size g16_partial records, e.g. one RCCL all-gather).
@@ -53,7 +56,8 @@ typedef enum {
     G16_ERR_INTERNAL = 7,
     G16_ERR_UNEXPECTED_IDENTITY = 8, /* SynthesisError::UnexpectedIdentity: gamma or delta is zero (generator.rs:110-111) */
     G16_ERR_INVALID_DATA = 9,        /* SerializationError::InvalidData: bytes that are not a point of the group        */
-    G16_ERR_NO_PEER_ACCESS = 10      /* g16_ctx_create_multi with G16_MULTI_REQUIRE_PEER=1: a device pair without peer access */
+    G16_ERR_NO_PEER_ACCESS = 10,     /* g16_ctx_create_multi with G16_MULTI_REQUIRE_PEER=1: a device pair without peer access */
+    G16_ERR_MALFORMED_VK = 11        /* SynthesisError::MalformedVerifyingKey: public inputs + 1 != gamma_abc_g1 (verifier.rs:29-31) */
 } g16_status;
 
 typedef enum { G16_BLS12_381 = 0, G16_BN254 = 1 } g16_curve;
@@ -375,6 +379,39 @@ int g16_host_msm_model_shard(int curve, int g2, const uint64_t* bases, const uin
  * standard field / group code; 0 = all checks passed, otherwise the number of the first failing check */
 int g16_host_selftest(int curve, uint64_t seed, int iters);
 
+/* ---- verifier (src/verifier.rs:13-76, src/lib.rs:84-96) ------------------------------------------------------------
+ * GT values cross as 12 Fq in arkworks' order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1 (Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - xi)),
+ * Montgomery limbs as every other field element: byte-equal to PairingOutput.0.  Pairings are optimal ate with the exact final
+ * exponentiation f^((q^12 - 1) / r); a pair with an identity point contributes 1. */
+typedef struct {
+    const uint64_t* alpha_g1;     /* G1 affine */
+    const uint64_t* beta_g2;      /* G2 affine */
+    const uint64_t* gamma_g2;
+    const uint64_t* delta_g2;
+    const uint64_t* gamma_abc_g1; /* n_gamma_abc G1 affine points */
+    uint64_t n_gamma_abc;
+} g16_vk_view;                    /* VerifyingKey, data_structures.rs:31-44 */
+typedef struct g16_pvk g16_pvk;   /* PreparedVerifyingKey (data_structures.rs:56-66), resident on the ctx's device(s) */
+/* e(alpha, beta), the line coefficients of -gamma and -delta and window tables of gamma_abc_g1[1..], computed on the GPU */
+int g16_pvk_load(g16_ctx* ctx, const g16_vk_view* vk, g16_pvk** out);
+void g16_pvk_free(g16_pvk* pvk);
+int g16_pvk_alpha_beta(const g16_pvk* pvk, uint64_t* out_fq12);
+/* proofs: n x (A | B | C) affine; public_inputs: n x num_public Fr.  verdicts[i]: 1 accept, 0 the pairing equation fails,
+ * 2 A, B or C is not on its curve (a superset of the reference, whose point types cannot hold such points).
+ * G16_ERR_MALFORMED_VK fails the whole call when num_public + 1 != n_gamma_abc.  A multi-device ctx cuts the batch into one
+ * chunk per device; verdicts stay in input order. */
+int g16_verify_batch(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
+                     uint64_t num_public, uint8_t* verdicts);
+/* the same with IC = prepare_inputs(..) given per proof (n G1 affine) */
+int g16_verify_batch_prepared(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, const uint64_t* prepared_inputs, uint64_t n,
+                              uint8_t* verdicts);
+/* prod_i e(g1s[i], g2s[i]) on the ctx's (first) GPU; G16_ERR_UNEXPECTED_IDENTITY if the Miller loop gave 0 (verifier.rs:62) */
+int g16_pairing(g16_ctx* ctx, const uint64_t* g1s, const uint64_t* g2s, uint64_t n_pairs, uint64_t* out_fq12);
+/* the same templates on the CPU (no GPU needed) */
+int g16_host_pairing(int curve, const uint64_t* g1s, const uint64_t* g2s, uint64_t n_pairs, uint64_t* out_fq12);
+int g16_host_verify(int curve, const g16_vk_view* vk, const uint64_t* proof, const uint64_t* public_inputs, uint64_t num_public,
+                    uint8_t* verdict);
+
 const char* g16_strerror(int status);
 /* text of the last HIP error seen on this thread ("" if none) */
 const char* g16_last_error(void);
@@ -385,7 +422,7 @@ const char* g16_version(void);
  * sizes (g16_struct_size), or uses the *_sized readers below, which copy min(size, library's size) bytes and never more. */
 #define G16_ABI_VERSION 2
 int g16_abi_version(void);
-enum { G16_STRUCT_TIMINGS = 0, G16_STRUCT_PK_INFO = 1, G16_STRUCT_DIAG = 2, G16_STRUCT_PROOF = 3, G16_STRUCT_PARTIAL = 4, G16_STRUCT_PK_VIEW = 5 };
+enum { G16_STRUCT_TIMINGS = 0, G16_STRUCT_PK_INFO = 1, G16_STRUCT_DIAG = 2, G16_STRUCT_PROOF = 3, G16_STRUCT_PARTIAL = 4, G16_STRUCT_PK_VIEW = 5, G16_STRUCT_VK_VIEW = 6 };
 /* sizeof the library's own idea of a struct of this header; 0 for an unknown `which` */
 uint64_t g16_struct_size(int which);
 /* g16_get_timings / g16_pk_get_info into a caller struct of `size` bytes (its sizeof at ITS compile time) */

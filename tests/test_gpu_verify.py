@@ -1,0 +1,187 @@
+"""GPU tier: the verifier kernels (verify.hip) against the host templates, the big-int pairing model and the expected verdicts of
+honest and tampered proofs, on both curves."""
+import numpy as np
+import pytest
+
+import pairing_model as pmod
+import pymodel as pm
+from helpers import g1_to_arr, g2_to_arr, mont_to_ints, ints_to_mont, oracle
+from verify_cases import oracle_case, tamperings, wrong_input
+
+import groth16_amd as g
+from groth16_amd.serialize import proof_from_bytes, proof_to_bytes
+from groth16_amd.verifier import host_verdict
+
+pytestmark = pytest.mark.gpu
+NAMES = ["bls12_381", "bn254"]
+
+
+def as_proof(flat, cp):
+    L = cp.fq_limbs64
+    return g.Proof(flat[: 2 * L].copy(), flat[2 * L: 6 * L].copy(), flat[6 * L:].copy())
+
+
+@pytest.fixture(scope="module", params=NAMES)
+def setup(request):
+    name = request.param
+    vk, proofs, x, cp = oracle_case(name)
+    with g.Groth16(name, device=0) as prover:
+        pvk = prover.prepare_verifying_key(vk)
+        yield name, prover, pvk, vk, proofs, x, cp
+        pvk.close()
+
+
+def test_gpu_pairing_equals_host_and_model(setup):
+    name, prover, pvk, vk, proofs, x, cp = setup
+    G1, G2 = pm.groups(cp)
+    pairs = [(G1.mul(cp.g1, 12345), cp.g2), (cp.g1, G2.mul(cp.g2, 777)), (None, cp.g2)]
+    g1s, g2s = g1_to_arr([p for p, _ in pairs], cp), g2_to_arr([q for _, q in pairs], cp)
+    got = prover.pairing(g1s, g2s)
+    assert (got == g.host_pairing(name, g1s, g2s)).all()
+    assert (got == pmod.to_ark_limbs(name, pmod.pairing_product(name, pairs))).all()
+
+
+def test_alpha_beta_equals_model(setup):
+    name, prover, pvk, vk, proofs, x, cp = setup
+    from helpers import arr_to_g1, arr_to_g2
+    want = pmod.to_ark_limbs(name, pmod.pairing(name, arr_to_g1(vk.alpha_g1, cp)[0], arr_to_g2(vk.beta_g2, cp)[0]))
+    assert (pvk.alpha_g1_beta_g2 == want).all()
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1000, 4097])
+def test_batch_verdicts(setup, n):
+    """honest proofs fanned out with rerandomize_proof, tampered and off-curve ones at seeded positions"""
+    name, prover, pvk, vk, proofs, x, cp = setup
+    base = [as_proof(proofs[0], cp)]
+    rng = np.random.default_rng(n)
+    for _ in range(3):
+        base.append(g.rerandomize_proof(name, vk, base[0]))
+    cases = tamperings(proofs, x, cp)
+    flat = np.stack([base[i % len(base)].flat() for i in range(n)])
+    xs = [x] * n
+    want = np.ones(n, dtype=np.uint8)
+    pos = rng.choice(n, size=min(n, 2 * len(cases)), replace=False)
+    for k, i in enumerate(pos):
+        label, p, xi, v = cases[k % len(cases)]
+        flat[i], xs[i], want[i] = p, xi, v
+    got = prover.verify_verdicts(pvk, flat, xs)
+    assert (got == want).all(), np.nonzero(got != want)
+    for i in list(pos[:4]) + [0, n - 1]:
+        assert host_verdict(name, vk, flat[i], xs[i]) == got[i]
+    assert (prover.verify_proofs(pvk, flat, xs) == (want == 1)).all()
+
+
+def test_identity_a_and_c(setup):
+    name, prover, pvk, vk, proofs, x, cp = setup
+    L = cp.fq_limbs64
+    a0, c0 = proofs[0].copy(), proofs[0].copy()
+    a0[: 2 * L] = 0
+    c0[6 * L:] = 0
+    got = prover.verify_verdicts(pvk, np.stack([a0, c0]), [x, x])
+    assert list(got) == [host_verdict(name, vk, a0, x), host_verdict(name, vk, c0, x)] == [0, 0]
+
+
+def test_no_public_inputs(setup):
+    """a key with gamma_abc_g1 = [IC] verifies the same proof with no inputs (l = 0)"""
+    name, prover, pvk, vk, proofs, x, cp = setup
+    ic = prover.prepare_inputs(pvk, x)
+    vk0 = g.VerifyingKey(name, vk.alpha_g1, vk.beta_g2, vk.gamma_g2, vk.delta_g2, ic.reshape(1, -1))
+    pvk0 = prover.prepare_verifying_key(vk0)
+    try:
+        assert prover.verify_proof(pvk0, as_proof(proofs[0], cp), [])
+        assert list(prover.verify_verdicts(pvk0, np.stack(proofs), [[], []])) == [1, 1]
+        assert g.verify_proof_host(name, vk0, proofs[0], [])
+        with pytest.raises(g.MalformedVerifyingKey):
+            prover.verify_proof(pvk0, as_proof(proofs[0], cp), x)
+    finally:
+        pvk0.close()
+
+
+def test_r_s_zero_proofs(setup):
+    name, prover, pvk, vk, proofs, x, cp = setup
+    orc = oracle()
+    ck = orc.syn_circuit(name, 4, 9)
+    pk, _ = orc.setup(ck, 3)
+    zero = np.zeros(4, dtype=np.uint64)
+    flat, _ = orc.prove(pk, ck, zero, zero)
+    assert prover.verify_proof(pvk, as_proof(np.asarray(flat, np.uint64), cp), x)
+
+
+def test_proofs_read_back_from_bytes(setup):
+    name, prover, pvk, vk, proofs, x, cp = setup
+    for compressed in (True, False):
+        p = proof_from_bytes(name, proof_to_bytes(name, as_proof(proofs[1], cp), compressed), compressed)
+        assert prover.verify_proof(pvk, p, x)
+
+
+def test_prepared_inputs_equal_verify_proof(setup):
+    name, prover, pvk, vk, proofs, x, cp = setup
+    for p in proofs:
+        pr = as_proof(p, cp)
+        for xi in (x, wrong_input(x, cp)):
+            ic = prover.prepare_inputs(pvk, xi)
+            assert prover.verify_proof_with_prepared_inputs(pvk, pr, ic) == prover.verify_proof(pvk, pr, xi)
+    with pytest.raises(g.MalformedVerifyingKey):
+        prover.verify_proof(pvk, as_proof(proofs[0], cp), np.concatenate([x, x]))
+
+
+def test_multi_device_context_keeps_input_order(setup):
+    name, _, _, vk, proofs, x, cp = setup
+    cases = tamperings(proofs, x, cp)
+    flat = np.stack([c[1] for c in cases] * 5)
+    xs = [c[2] for c in cases] * 5
+    want = np.array([c[3] for c in cases] * 5, dtype=np.uint8)
+    with g.Groth16(name, device=[0, 0]) as multi:
+        pvk = multi.prepare_verifying_key(vk)
+        try:
+            assert (multi.verify_verdicts(pvk, flat, xs) == want).all()
+        finally:
+            pvk.close()
+
+
+def test_gpu_made_proof_is_accepted(setup):
+    """a proof of the GPU prover (syn circuit, as smoke() makes it) and its rerandomisations"""
+    name, prover, pvk, vk, proofs, x, cp = setup
+    orc = oracle()
+    ck = orc.syn_circuit(name, 10, 1)
+    pk, ex = orc.setup(ck, 5)
+    mats = g.ConstraintMatrices(ck.num_inputs, ck.num_vars - ck.num_inputs, ck.num_constraints, *[(m.row_ptr, m.col, m.val) for m in ck.abc])
+    gpk = g.ProvingKey(name, pk.alpha_g1, pk.beta_g1, pk.delta_g1, pk.beta_g2, pk.delta_g2, pk.a_query, pk.b_g1_query, pk.b_g2_query,
+                       pk.h_query, pk.l_query, ex["gamma_g2"].reshape(1, -1), np.ascontiguousarray(ex["gamma_abc"]))
+    r, s = orc.rand_fr(name, 11, 1)[0], orc.rand_fr(name, 12, 1)[0]
+    proof = prover.create_proof_with_reduction_and_matrices(gpk, r, s, mats, ck.num_inputs, ck.num_constraints, ck.z)
+    pvk2 = prover.prepare_verifying_key(gpk)   # a ProvingKey that carries gamma_g2 / gamma_abc_g1
+    try:
+        xi = np.ascontiguousarray(ck.z[1: ck.num_inputs]).reshape(-1, 4)
+        batch = [proof] + [g.rerandomize_proof(name, gpk, proof) for _ in range(3)]
+        assert prover.verify_proofs(pvk2, batch, [xi] * 4).all()
+        if len(xi):
+            assert not prover.verify_proof(pvk2, proof, ints_to_mont([(mont_to_ints(xi, cp.r)[0] + 1) % cp.r] +
+                                                                     mont_to_ints(xi, cp.r)[1:], cp.r, 4))
+    finally:
+        pvk2.close()
+
+
+@pytest.mark.parametrize("curve", NAMES)
+def test_2_20_gpu_proof_with_gpu_key_is_accepted(curve):
+    """a 2^20-constraint proof of the GPU prover under a key made by the GPU generator (which fills gamma_g2 / gamma_abc_g1)"""
+    cp = pm.CURVES[curve]
+    orc = oracle()
+    ck = orc.syn_circuit(curve, 20, 37)
+    toxic = orc.rand_fr(curve, 920, 5)                           # alpha beta gamma delta t
+    gens = orc.setup(orc.syn_circuit(curve, 2, 1), 3)[1]
+    r, s = orc.rand_fr(curve, 71, 1)[0], orc.rand_fr(curve, 72, 1)[0]
+    with g.Groth16(curve, device=0) as prover:
+        mats = g.ConstraintMatrices(ck.num_inputs, ck.num_vars - ck.num_inputs, ck.num_constraints,
+                                    *[(m.row_ptr, m.col, m.val) for m in ck.abc])
+        pk = prover.generate_parameters_with_qap(mats, toxic[0], toxic[1], toxic[2], toxic[3], gens["g1gen"], gens["g2gen"], toxic[4])
+        proof = prover.create_proof_with_reduction_and_matrices(pk, r, s, mats, ck.num_inputs, ck.num_constraints, ck.z)
+        pvk = prover.prepare_verifying_key(pk)
+        try:
+            xi = np.ascontiguousarray(ck.z[1: ck.num_inputs]).reshape(-1, 4)
+            assert prover.verify_proof(pvk, proof, xi)
+            assert g.verify_proof_host(curve, pk, proof, xi)
+            if len(xi):
+                assert not prover.verify_proof(pvk, proof, wrong_input(xi, cp))
+        finally:
+            pvk.close()
