@@ -107,11 +107,7 @@ struct alignas(16) Fp {
         if constexpr (N >= G16_NOINLINE_MUL_LIMBS) return mul_outlined(*this, o);
         else return mul_inlined(o);
     }
-#ifdef G16_MUL_BYVAL
-    G16_HD_NOINLINE static Fp mul_outlined(Fp a, Fp b) { return a.mul_inlined(b); }
-#else
     G16_HD_NOINLINE static Fp mul_outlined(const Fp& a, const Fp& b) { return a.mul_inlined(b); }
-#endif
     G16_HD Fp mul_inlined(const Fp& o) const {
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__SIZEOF_INT128__)
         // host: the same Montgomery product on 64-bit limbs (R = 2^(32N) = 2^(64 N/2) is the same radix),

@@ -20,6 +20,12 @@
 #include "field.hpp"
 #include "fips_asm_gen.hpp"
 
+// Assembly products on this compile: the device runs the product-scanning chains as the generated blocks of fips_asm_gen.hpp (FipsAsm);
+// -DG16_NO_FIPS_ASM is the one diagnostic fallback, to the C++ fips<> that the host runs anyway.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(G16_NO_FIPS_ASM)
+#define G16_ASM_PRODUCTS 1
+#endif
+
 namespace g16 {
 
 template <class P>
@@ -135,117 +141,11 @@ struct Fp30 {
 
     // Montgomery product a*b/R' (mod p).  Inputs: normalised limbs, a < A p, b < B p with
     // A*B*p/R' <= 0.5  (A = B = 16 is fine for every supported field); output < 1.5 p, normalised.
-    G16_HD Fp30 mul(const Fp30& b) const {
-#ifdef G16_FP30_OUTLINE
-        return mul_outlined(*this, b);
-#else
-        return mul_impl(b);
-#endif
-    }
-    // ---- double-width column primitives (T has 2*NL 64-bit columns) -----------------------------
-    // One sweep of limb products adds CNT(c) = min(c + 1, 2 NL - 1 - c) products (each < 2^60) to column c.  A 64-bit column
-    // holds 15 of them plus the small carries that travel with it, so sweeps can pile up in a column WITHOUT any carry work
-    // until (sweeps so far + 1) * CNT(c) would pass G16_RELAX_LIMIT; only then is the column "relaxed" (wide_relax), and only that
-    // column: for NL = 13 that is 9 of 25 columns between a product and its reduction, none at all for NL <= 8.
-    // The column type is a template parameter so that the host self-test can run every routine with 128-bit columns beside the
-    // 64-bit ones on all-ones limbs and demand identical results (no overflow anywhere).
-#ifndef G16_RELAX_LIMIT
-#define G16_RELAX_LIMIT 16   // products (< 2^60 each) a 64-bit column may hold before it is relaxed.  16 (2^30 - 1)^2 = 2^64 - 2^35 + 16 leaves
-                             // 2^35 - 16 for the carries that travel with a column (a relaxation carry < 2^34, the reduction's carry < 2^34);
-                             // g16_host_selftest PROVES the plan for the real moduli by worst-case bound propagation (hosttest.hip
-                             // column_headroom: codes 605-609; 16 and 17 give the same plan, 18 fails with 605) beside the 128-bit shadow
-                             // runs.  Rounds 2-3 used 15: 11 relaxed columns per 13-limb product instead of 9.
-#endif
-    static constexpr int col_count(int c) { return c + 1 < 2 * NL - 1 - c ? c + 1 : 2 * NL - 1 - c; }
-    // T = a*b as NL^2 limb products
-    template <class U>
-    G16_HD static void wide_mul(U* T, const Fp30& a, const Fp30& b) {
-        G16_UNROLL for (int c = 0; c < 2 * NL; ++c) T[c] = 0;
-        G16_UNROLL for (int i = 0; i < NL; ++i) {
-            G16_UNROLL for (int j = 0; j < NL; ++j) T[i + j] += (uint64_t)a.l[i] * b.l[j];
-        }
-    }
-    // T = a*a with the symmetric products taken once against the doubled operand: NL(NL+1)/2 multiply-adds.
-    // A column holds <= CNT/2 doubled products (< 2^61) and one square: the same magnitude as CNT plain products.
-    template <class U>
-    G16_HD static void wide_sqr(U* T, const Fp30& a) {
-        G16_UNROLL for (int c = 0; c < 2 * NL; ++c) T[c] = 0;
-        G16_UNROLL for (int i = 0; i < NL; ++i) {
-            T[2 * i] += (uint64_t)a.l[i] * a.l[i];
-            const uint32_t a2 = a.l[i] << 1;
-            G16_UNROLL for (int j = i + 1; j < NL; ++j) T[i + j] += (uint64_t)a2 * a.l[j];
-        }
-    }
-    // T += a*b (one more sweep; the caller relaxes in between)
-    template <class U>
-    G16_HD static void wide_mul_add(U* T, const Fp30& a, const Fp30& b) {
-        G16_UNROLL for (int i = 0; i < NL; ++i) {
-            G16_UNROLL for (int j = 0; j < NL; ++j) T[i + j] += (uint64_t)a.l[i] * b.l[j];
-        }
-    }
-    // SWEEPS sweeps have been accumulated and one more (a product sweep or the reduction) follows: every column that could
-    // not absorb it hands its high word to the next column -- T[c] = lo32 + hi32 * 2^32 and 2^32 = 4 * 2^30, so
-    // T[c + 1] += 4 * hi32: one multiply-add and one register clear instead of the shift / mask / 64-bit add of a full carry
-    // step.  The column keeps < 2^32 (not < 2^30: nothing needs that before the reduction's own carry chain).
-    template <int SWEEPS, class U>
-    G16_HD static void wide_relax(U* T) {
-#ifdef G16_FP30_FULL_NORMALIZE
-        wide_normalize(T);
-#else
-#if defined(__HIP_DEVICE_COMPILE__)
-        // the factor 4 is made opaque so that the compiler keeps ONE v_mad_u64_u32 (hi32 * 4 + T[c + 1]); written as a shift it
-        // becomes a 64-bit shift, two masks and a 64-bit add -- as expensive as the full carry step this replaces
-        uint32_t four = 4u;
-        asm("" : "+s"(four));
-        G16_UNROLL for (int c = 0; c + 1 < 2 * NL; ++c) {
-            if ((SWEEPS + 1) * col_count(c) > G16_RELAX_LIMIT) {
-                T[c + 1] += (uint64_t)(uint32_t)(T[c] >> 32) * four;
-                T[c] = (U)(uint32_t)T[c];
-            }
-        }
-#else
-        G16_UNROLL for (int c = 0; c + 1 < 2 * NL; ++c) {
-            if ((SWEEPS + 1) * col_count(c) > G16_RELAX_LIMIT) {
-                T[c + 1] += (T[c] >> 32) << 2;
-                T[c] &= (U)0xffffffffu;
-            }
-        }
-#endif
-#endif
-    }
-    // one full carry sweep -> every column < 2^30 (the top column takes the rest)
-    template <class U>
-    G16_HD static void wide_normalize(U* T) {
-        G16_UNROLL for (int c = 0; c + 1 < 2 * NL; ++c) {
-            T[c + 1] += T[c] >> 30;
-            T[c] &= MASK;
-        }
-    }
-    // Montgomery reduction of T (value < ~400 p^2; columns relaxed for one more sweep): returns T / R' mod p, < p (1 + T/(R' p))
-    template <class U>
-    G16_HD static Fp30 wide_redc(U* T) {
-        U carry = 0;
-        G16_UNROLL for (int i = 0; i < NL; ++i) {
-            T[i] += carry;
-            const uint32_t m = ((uint32_t)T[i] * P::PINV30) & MASK;
-            G16_UNROLL for (int j = 0; j < NL; ++j) T[i + j] += (uint64_t)m * P::p30(j);  // column c again gets <= CNT(c) products
-            carry = T[i] >> 30;  // low 30 bits are zero now
-        }
-        Fp30 r;
-        G16_UNROLL for (int j = 0; j < NL; ++j) {
-            const U v = T[NL + j] + carry;
-            r.l[j] = (j == NL - 1) ? (uint32_t)v : ((uint32_t)v & MASK);
-            carry = v >> 30;
-        }
-        return r;
-    }
-#ifndef G16_NO_FIPS
-#define G16_FIPS 1
-#endif
-    // ---- product scanning (round 6): the same sums COLUMN BY COLUMN --------------------------------------------------------
-    // The operand-scanning forms above add the reduction's carry into a column that already holds its limb products: one 64-bit add
-    // per column on top of the shift that produced the carry (26 per product; the compiler also splits column chains and adds
-    // the halves, 33 v_lshl_add_u64 per product in the round-5 ISA).  Column-major, ONE running accumulator takes column c's
+    G16_HD Fp30 mul(const Fp30& b) const { return mul_impl(b); }
+    // ---- product scanning: the NL^2 limb products of every sweep and of the reduction, summed COLUMN BY COLUMN ---------------
+    // (The operand-scanning forms of rounds 2-5 -- 2 NL columns of T, one sweep at a time -- added the reduction's carry into a column
+    // that already held its limb products: one 64-bit add per column on top of the shift that produced the carry.  DESIGN.md "Tried
+    // and retired".)  Column-major, ONE running accumulator takes column c's
     // products of every sweep and of the reduction, and its carry-out `acc >> 30` is the SEED of column c + 1's multiply-add chain:
     // the add disappears (v_mad_u64_u32 has a free 64-bit addend), the 2 NL columns of T are never materialised (fewer live
     // registers), and with the field's REAL modulus limbs in the bound only 5 of 25 columns of a 13-limb product exceed what a
@@ -388,8 +288,7 @@ struct Fp30 {
     }
     template <class U>
     G16_HD Fp30 mul_cols(const Fp30& b) const {
-#ifdef G16_FIPS
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(G16_NO_FIPS_ASM)
+#ifdef G16_ASM_PRODUCTS
         if constexpr (sizeof(U) == 8 && FipsAsm<P>::available) {   // the same chain as hand-scheduled assembly (gen_fips_asm.py)
             static_assert(fips_asm_plan_agrees<1>(), "gen_fips_asm.py and Fp30::fips_plan disagree on the column plan");
             Fp30 r;
@@ -400,17 +299,10 @@ struct Fp30 {
         const Fp30* xs[1] = {this};
         const Fp30* ys[1] = {&b};
         return fips<U, 1, false>(xs, ys);
-#else
-        U T[2 * NL];
-        wide_mul(T, *this, b);
-        wide_relax<1>(T);
-        return wide_redc(T);
-#endif
     }
     template <class U>
     G16_HD Fp30 sqr_cols() const {
-#ifdef G16_FIPS
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(G16_NO_FIPS_ASM)
+#ifdef G16_ASM_PRODUCTS
         if constexpr (sizeof(U) == 8 && FipsAsm<P>::available) {
             static_assert(fips_asm_plan_agrees<1>(), "gen_fips_asm.py and Fp30::fips_plan disagree on the column plan");
             Fp30 r;
@@ -420,18 +312,11 @@ struct Fp30 {
 #endif
         const Fp30* xs[1] = {this};
         return fips<U, 1, true>(xs, xs);
-#else
-        U T[2 * NL];
-        wide_sqr(T, *this);
-        wide_relax<1>(T);
-        return wide_redc(T);
-#endif
     }
     // x1 y1 + x2 y2 under one reduction
     template <class U>
     G16_HD static Fp30 mul2_cols(const Fp30& x1, const Fp30& y1, const Fp30& x2, const Fp30& y2) {
-#ifdef G16_FIPS
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(G16_NO_FIPS_ASM)
+#ifdef G16_ASM_PRODUCTS
         if constexpr (sizeof(U) == 8 && FipsAsm<P>::available) {
             static_assert(fips_asm_plan_agrees<2>(), "gen_fips_asm.py and Fp30::fips_plan disagree on the column plan");
             Fp30 r;
@@ -442,21 +327,12 @@ struct Fp30 {
         const Fp30* xs[2] = {&x1, &x2};
         const Fp30* ys[2] = {&y1, &y2};
         return fips<U, 2, false>(xs, ys);
-#else
-        U T[2 * NL];
-        wide_mul(T, x1, y1);
-        wide_relax<1>(T);
-        wide_mul_add(T, x2, y2);
-        wide_relax<2>(T);
-        return wide_redc(T);
-#endif
     }
     // x1 y1 + x2 y2 + x3 y3 + x4 y4 under one reduction
     template <class U>
     G16_HD static Fp30 mul4_cols(const Fp30& x1, const Fp30& y1, const Fp30& x2, const Fp30& y2, const Fp30& x3, const Fp30& y3,
                                  const Fp30& x4, const Fp30& y4) {
-#ifdef G16_FIPS
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(G16_NO_FIPS_ASM)
+#ifdef G16_ASM_PRODUCTS
         if constexpr (sizeof(U) == 8 && FipsAsm<P>::available) {
             static_assert(fips_asm_plan_agrees<4>(), "gen_fips_asm.py and Fp30::fips_plan disagree on the column plan");
             Fp30 r;
@@ -467,18 +343,6 @@ struct Fp30 {
         const Fp30* xs[4] = {&x1, &x2, &x3, &x4};
         const Fp30* ys[4] = {&y1, &y2, &y3, &y4};
         return fips<U, 4, false>(xs, ys);
-#else
-        U T[2 * NL];
-        wide_mul(T, x1, y1);
-        wide_relax<1>(T);
-        wide_mul_add(T, x2, y2);
-        wide_relax<2>(T);
-        wide_mul_add(T, x3, y3);
-        wide_relax<3>(T);
-        wide_mul_add(T, x4, y4);
-        wide_relax<4>(T);
-        return wide_redc(T);
-#endif
     }
     template <class U>
     G16_HD static Fp30 mul_sub_cols(const Fp30& a, const Fp30& b, const Fp30& c, const Fp30& d) {
@@ -492,7 +356,7 @@ struct Fp30 {
     template <int K>
     G16_HD Fp30 mul_sub_k(const Fp30& b, const Fp30& s) const {
         static_assert(K == 2 || K == 4 || K == 8, "fused subtraction: K = 2, 4, 8");
-#if defined(__HIP_DEVICE_COMPILE__) && defined(G16_FIPS) && !defined(G16_NO_FIPS_ASM) && !defined(G16_NO_FUSED_SUB)
+#ifdef G16_ASM_PRODUCTS
         if constexpr (FipsAsm<P>::has_sub) {
             static_assert(fips_asm_plan_agrees<1>(), "gen_fips_asm.py and Fp30::fips_plan disagree on the column plan");
             Fp30 r;
@@ -507,7 +371,7 @@ struct Fp30 {
     template <int K>
     G16_HD static Fp30 mul2_sub_k(const Fp30& x1, const Fp30& y1, const Fp30& x2, const Fp30& y2, const Fp30& s) {
         static_assert(K == 2 || K == 4 || K == 8, "fused subtraction: K = 2, 4, 8");
-#if defined(__HIP_DEVICE_COMPILE__) && defined(G16_FIPS) && !defined(G16_NO_FIPS_ASM) && !defined(G16_NO_FUSED_SUB)
+#ifdef G16_ASM_PRODUCTS
         if constexpr (FipsAsm<P>::has_sub) {
             static_assert(fips_asm_plan_agrees<2>(), "gen_fips_asm.py and Fp30::fips_plan disagree on the column plan");
             Fp30 r;
@@ -521,7 +385,7 @@ struct Fp30 {
     }
     // this^2 + 6 p - (u + 2 v)   (X3 = R^2 - PPP - 2 Q of the XYZZ additions; u, v < ~1.5 p normalised)
     G16_HD Fp30 sqr_sub_x3(const Fp30& u, const Fp30& v) const {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(G16_FIPS) && !defined(G16_NO_FIPS_ASM) && !defined(G16_NO_FUSED_SUB)
+#ifdef G16_ASM_PRODUCTS
         if constexpr (FipsAsm<P>::has_sub) {
             Fp30 r;
             FipsAsm<P>::sqr_x3(r.l, l, u.l, v.l);
@@ -532,7 +396,7 @@ struct Fp30 {
     }
     // this * b + 6 p - (u + 2 v)   (the lane pair's X3: its squaring is a product of prepared operands)
     G16_HD Fp30 mul_sub_x3(const Fp30& b, const Fp30& u, const Fp30& v) const {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(G16_FIPS) && !defined(G16_NO_FIPS_ASM) && !defined(G16_NO_FUSED_SUB)
+#ifdef G16_ASM_PRODUCTS
         if constexpr (FipsAsm<P>::has_sub) {
             Fp30 r;
             FipsAsm<P>::mul_x3(r.l, l, b.l, u.l, v.l);
@@ -542,21 +406,10 @@ struct Fp30 {
         return mul_impl(b).template sub<6>(u.add_dbl(v));
     }
     G16_HD Fp30 mul_impl(const Fp30& b) const { return mul_cols<uint64_t>(b); }
-    G16_HD_NOINLINE static Fp30 mul_outlined(Fp30 a, Fp30 b) { return a.mul_impl(b); }
-    // a*b - c*d with ONE Montgomery reduction (the double-width sums share it): 3 NL^2 multiply-adds instead of 4 NL^2.
-    // Requires d < 2p and a*b + 2p*c < ~400 p^2; output < 1.2p for the bounds the group formulas feed it.
-    // In the REGISTER-RESIDENT accumulator (Acc30: reductions, table builder) this stays opt-in (G16_FP30_MUL_SUB): round 2 measured
-    // -4.7 % at equal occupancy, but the fused form needs ~15 more live registers than the 256 that keep two waves per SIMD; held
-    // to 256 the allocator spilled 18 dwords and the pass was 1.8 % SLOWER than two plain products (profiles/r02_ab_g1_occupancy.txt).
-    // The bucket pass itself no longer has that problem: its accumulator is parked in LDS (AccParked, round 4) and it calls
-    // mul_sub_fused below -- G1 pass 9.14 -> 8.90 ms (profiles/r04_ab_parked_accumulator.txt).
-    G16_HD static Fp30 mul_sub(const Fp30& a, const Fp30& b, const Fp30& c, const Fp30& d) {
-#if defined(G16_FP30_OUTLINE) || !defined(G16_FP30_MUL_SUB)
-        return a.mul(b).template sub<2>(c.mul(d));
-#else
-        return mul_sub_cols<uint64_t>(a, b, c, d);
-#endif
-    }
+    // a*b - c*d as two products: what the REGISTER-RESIDENT accumulator (Acc30: reductions, table builder) calls.  The fused form below
+    // needs ~15 more live registers than the 256 that keep two waves per SIMD (DESIGN.md "Tried and retired"); the bucket pass, whose
+    // accumulator is parked in LDS (AccParked), has them and calls mul_sub_fused.
+    G16_HD static Fp30 mul_sub(const Fp30& a, const Fp30& b, const Fp30& c, const Fp30& d) { return a.mul(b).template sub<2>(c.mul(d)); }
     // ---- operand views (round 6).  A lane-pair Fq2 product needs its FIRST operand as both components in both lanes (two DPP
     // broadcasts per limb) and its SECOND operand's partner component, negated for the even lane (a carry-propagating 16p - b and a
     // select).  An operand that enters several products of a group formula (PP: three, PPP and Pd and R: two) is prepared ONCE
@@ -571,21 +424,10 @@ struct Fp30 {
     G16_HD static Fp30 mul_add_fused_v(const Fp30& a, const Fp30& b, const Fp30& c, const Fp30& d) { return mul2_cols<uint64_t>(a, b, c, d); }
     // a*b + c*d under one reduction (the sign-tracking mixed addition's Y: no operand is negated)
     G16_HD static Fp30 mul_add_fused(const Fp30& a, const Fp30& b, const Fp30& c, const Fp30& d) { return mul2_cols<uint64_t>(a, b, c, d); }
-    // the fused form unconditionally: AccParked (bucket pass) has the registers for it -- its accumulator is not in them
-    G16_HD static Fp30 mul_sub_fused(const Fp30& a, const Fp30& b, const Fp30& c, const Fp30& d) {
-#ifdef G16_NO_MUL_SUB_FUSED
-        return a.mul(b).template sub<2>(c.mul(d));
-#else
-        return mul_sub_cols<uint64_t>(a, b, c, d);
-#endif
-    }
-    G16_HD Fp30 sqr() const {
-#if defined(G16_FP30_OUTLINE) || defined(G16_FP30_NO_SQR)
-        return mul(*this);
-#else
-        return sqr_cols<uint64_t>();
-#endif
-    }
+    // a*b - c*d with ONE Montgomery reduction (the double-width sums share it): 3 NL^2 multiply-adds instead of 4 NL^2.
+    // Requires d < 2p and a*b + 2p*c < ~400 p^2; output < 1.2p for the bounds the group formulas feed it.
+    G16_HD static Fp30 mul_sub_fused(const Fp30& a, const Fp30& b, const Fp30& c, const Fp30& d) { return mul_sub_cols<uint64_t>(a, b, c, d); }
+    G16_HD Fp30 sqr() const { return sqr_cols<uint64_t>(); }
 
     // exact: is the value (any bound < 16p, normalised) congruent to 0 mod p?
     // Fast filter on the low limb: v = k p with k < 16 forces (v0 * p^-1 mod 2^30) = k < 16.
@@ -631,21 +473,13 @@ struct Fp30 {
     typedef Fp30 Raw;   // the one-lane field whose limb layout partial sums are stored in
     // accumulator trait constants (see Acc30): bounds of this field's product outputs are < 1.5p
     static constexpr int KM = 2, K2M = 4, KX = 8, KY = 4;
-    G16_HD Fp30 settle() const { return *this; }
 // Two waves per SIMD (<= 256 registers): at 257 the kernel silently drops to ONE wave per SIMD and loses ~20 % (measured: the
 // round-2 DIRECT template parameter cost 10.1 -> 12.5 ms per pass that way; tests/test_kernel_resources.py now asserts it).
 #ifndef G16_ACC_MIN_WAVES
 #define G16_ACC_MIN_WAVES 2
 #endif
     static constexpr int ACC_MIN_WAVES = G16_ACC_MIN_WAVES;
-#ifndef G16_G1_PREFETCH
-#define G16_G1_PREFETCH true
-#endif
-    static constexpr bool ACC_PREFETCH = G16_G1_PREFETCH;
-#ifndef G16_G1_PARKED
-#define G16_G1_PARKED 1
-#endif
-    static constexpr bool ACC_PARKED = G16_G1_PARKED != 0;   // bucket pass: accumulator coordinates in LDS (AccParked)
+    static constexpr bool ACC_PREFETCH = true;   // bucket pass: gather the next point while the current one is added
     // ---- bucket-kernel hooks: one lane per task
     static constexpr int LANES_PER_TASK = 1;
     template <class A>
@@ -763,7 +597,7 @@ struct Fp30 {
 // (lazy reduction: the two double-width sums are reduced once each), i.e. 6 NL^2 multiply-adds -- the
 // same count as Karatsuba's 3 full products, with outputs that obey the single-product bound (< 1.5p)
 // so the group formulas and their K constants are shared with G1.  Inputs: components < 16p.
-// mul/sqr are out-of-line by default: fully inlined, the G2 bucket kernel is ~300 KB of code and, once
+// mul/sqr are out-of-line: fully inlined, the G2 bucket kernel is ~300 KB of code and, once
 // the waves of a CU drift apart, instruction fetch (64 KB I-cache) becomes the bottleneck -- measured
 // 129 ms (inlined) vs 83 ms (out-of-line) for the 2^22-point G2 bucket pass (profiles/r01_*).
 template <class P>
@@ -793,20 +627,8 @@ struct Fp2x30 {
     }
     G16_HD_NOINLINE static Fp2x30 mul_outlined(const Fp2x30& a, const Fp2x30& b) { return a.mul_impl(b); }
     G16_HD_NOINLINE static Fp2x30 sqr_outlined(const Fp2x30& a) { return a.sqr_impl(); }
-    G16_HD Fp2x30 mul(const Fp2x30& o) const {
-#ifdef G16_FP2X30_INLINE
-        return mul_impl(o);
-#else
-        return mul_outlined(*this, o);
-#endif
-    }
-    G16_HD Fp2x30 sqr() const {
-#ifdef G16_FP2X30_INLINE
-        return sqr_impl();
-#else
-        return sqr_outlined(*this);
-#endif
-    }
+    G16_HD Fp2x30 mul(const Fp2x30& o) const { return mul_outlined(*this, o); }
+    G16_HD Fp2x30 sqr() const { return sqr_outlined(*this); }
     template <int K>
     G16_HD Fp2x30 mul_sub_k(const Fp2x30& o, const Fp2x30& s) const { return mul(o).template sub<K>(s); }
     G16_HD Fp2x30 sqr_sub_x3(const Fp2x30& u, const Fp2x30& v) const { return sqr().template sub<KM + K2M>(u.add_dbl(v)); }
@@ -826,104 +648,10 @@ struct Fp2x30 {
     G16_HD static Fp2x30 sqr_v(const Fp2x30& a) { return a.sqr(); }
     G16_HD static Fp2x30 sqr_sub_x3_v(const Fp2x30& a, const Fp2x30& u, const Fp2x30& v) { return a.sqr_sub_x3(u, v); }
     G16_HD static Fp2x30 mul_add_fused_v(const Fp2x30& a, const Fp2x30& b, const Fp2x30& c, const Fp2x30& d) { return mul_add_fused(a, b, c, d); }
-    G16_HD Fp2x30 settle() const { return *this; }
     G16_HD bool raw_zero() const { return c0.raw_zero() && c1.raw_zero(); }
     typedef Fp2x30 Raw;
-    static constexpr int ACC_MIN_WAVES = 1;
-    static constexpr bool ACC_PREFETCH = false;
-    static constexpr bool ACC_PARKED = false;
     static constexpr int PREFIX_LIMBS = 2 * B::NL;
-    // ---- bucket-kernel hooks: one lane per task
     static constexpr int LANES_PER_TASK = 1;
-    template <class A>
-    G16_HD static bool load_point(const A* bases, int64_t idx, Fp2x30& px, Fp2x30& py) {   // false for the identity
-        const A p = bases[idx];
-        if (p.is_identity()) return false;
-        px = from_packed(p.x);
-        py = from_packed(p.y);
-        return true;
-    }
-
-};
-
-// Fq2 for the G2 BUCKET kernel: Karatsuba over three base-field products that are passed in registers
-// (Fp30::mul_outlined by value) or inlined.  Unlike Fp2x30 no operand ever lives in scratch memory: the
-// out-of-line Fp2x30 product moved ~250 GB of scratch traffic per 2^22-point launch (rocprofv3 FETCH_SIZE +
-// WRITE_SIZE, profiles/r01_pmc_*).  Price: product outputs are only < 6p (c0 = v0 - v1 + 2p, c1 = v2 - v0 - v1 + 4p),
-// so the accumulator subtracts with larger K and "settles" X3 / Y3 with a weak reduction (4 conditional
-// subtractions, ~3 % of a mixed addition).
-template <class P>
-struct Fp2k30 {
-    typedef Fp30<P> B;
-    typedef Fp2<P> Std;
-    B c0, c1;
-    G16_HD static Fp2k30 zero() { return {B::zero(), B::zero()}; }
-    G16_HD static Fp2k30 one() { return {B::one(), B::zero()}; }
-    G16_HD static Fp2k30 from_packed(const Std& x) { return {B::unpack(x.c0.v), B::unpack(x.c1.v)}; }
-    G16_HD Fp2k30 add(const Fp2k30& o) const { return {c0.add(o.c0), c1.add(o.c1)}; }
-    G16_HD Fp2k30 dbl() const { return {c0.dbl(), c1.dbl()}; }
-    G16_HD Fp2k30 add_dbl(const Fp2k30& o) const { return {c0.add_dbl(o.c0), c1.add_dbl(o.c1)}; }
-    template <int K>
-    G16_HD Fp2k30 sub(const Fp2k30& o) const { return {c0.template sub<K>(o.c0), c1.template sub<K>(o.c1)}; }
-    G16_HD Fp2k30 neg2() const { return {c0.neg2(), c1.neg2()}; }
-    G16_HD static Fp2k30 cond_neg2(const Fp2k30& a, bool flip) { return flip ? a.neg2() : a; }
-    G16_HD static B bmul(const B& a, const B& b) {
-#ifdef G16_FP2K_INLINE
-        return a.mul_impl(b);
-#else
-        return B::mul_outlined(a, b);
-#endif
-    }
-    // inputs: components < 16p
-    G16_HD Fp2k30 mul(const Fp2k30& o) const {
-        const B v0 = bmul(c0, o.c0), v1 = bmul(c1, o.c1);       // < 1.5p
-        const B v2 = bmul(c0.add(c1), o.c0.add(o.c1));          // operands < 32p
-        return {v0.template sub<2>(v1), v2.template sub<4>(v0.add(v1))};   // < 3.5p, < 5.5p
-    }
-    G16_HD Fp2k30 sqr() const {                                 // both components < 2p
-        return {bmul(c0.add(c1), c0.template sub<16>(c1)), bmul(c0.dbl(), c1)};
-    }
-    template <int K>
-    G16_HD Fp2k30 mul_sub_k(const Fp2k30& o, const Fp2k30& s) const { return mul(o).template sub<K>(s); }
-    G16_HD Fp2k30 sqr_sub_x3(const Fp2k30& u, const Fp2k30& v) const { return sqr().template sub<16>(u.add_dbl(v)); }
-    G16_HD bool maybe_zero() const { return c0.maybe_zero() && c1.maybe_zero(); }
-    G16_HD bool is_zero_exact() const { return c0.is_zero_exact() && c1.is_zero_exact(); }
-    G16_HD Std to_std() const { return {c0.to_std(), c1.to_std()}; }
-    G16_HD Std to_packed() const { return {c0.to_packed(), c1.to_packed()}; }
-    // product outputs < 6p -> subtract them with K = 8 (16 when doubled); x, y are settled below 2p
-    static constexpr int KM = 8, K2M = 16, KX = 2, KY = 2;
-    G16_HD static Fp2k30 mul_sub(const Fp2k30& a, const Fp2k30& b, const Fp2k30& c, const Fp2k30& d) { return a.mul(b).template sub<KM>(c.mul(d)); }
-    G16_HD static Fp2k30 mul_sub_fused(const Fp2k30& a, const Fp2k30& b, const Fp2k30& c, const Fp2k30& d) { return mul_sub(a, b, c, d); }
-    G16_HD static Fp2k30 mul_add_fused(const Fp2k30& a, const Fp2k30& b, const Fp2k30& c, const Fp2k30& d) { return a.mul(b).add(c.mul(d)); }
-    typedef Fp2k30 Lhs;
-    typedef Fp2k30 Rhs;
-    G16_HD static const Fp2k30& lhs(const Fp2k30& a) { return a; }
-    G16_HD static const Fp2k30& rhs(const Fp2k30& a) { return a; }
-    G16_HD static Fp2k30 mul_v(const Fp2k30& a, const Fp2k30& b) { return a.mul(b); }
-    G16_HD static Fp2k30 sqr_v(const Fp2k30& a) { return a.sqr(); }
-    G16_HD static Fp2k30 sqr_sub_x3_v(const Fp2k30& a, const Fp2k30& u, const Fp2k30& v) { return a.sqr_sub_x3(u, v); }
-    G16_HD static Fp2k30 mul_add_fused_v(const Fp2k30& a, const Fp2k30& b, const Fp2k30& c, const Fp2k30& d) { return mul_add_fused(a, b, c, d); }
-    G16_HD Fp2k30 settle() const { return {c0.weak_reduce32(), c1.weak_reduce32()}; }
-    G16_HD bool raw_zero() const { return c0.raw_zero() && c1.raw_zero(); }
-    typedef Fp2x30<P> Raw;
-#ifndef G16_G2_MIN_WAVES
-#define G16_G2_MIN_WAVES 1
-#endif
-    static constexpr int ACC_MIN_WAVES = G16_G2_MIN_WAVES;
-    static constexpr bool ACC_PREFETCH = false;
-    static constexpr bool ACC_PARKED = false;
-    static constexpr int PREFIX_LIMBS = 2 * B::NL;
-    // ---- bucket-kernel hooks: one lane per task
-    static constexpr int LANES_PER_TASK = 1;
-    template <class A>
-    G16_HD static bool load_point(const A* bases, int64_t idx, Fp2k30& px, Fp2k30& py) {   // false for the identity
-        const A p = bases[idx];
-        if (p.is_identity()) return false;
-        px = from_packed(p.x);
-        py = from_packed(p.y);
-        return true;
-    }
-
 };
 
 // Fq2 for the G2 bucket kernel, LANE-PAIR form: two adjacent lanes (2k, 2k+1) own one bucket; lane parity `hi`
@@ -1009,13 +737,7 @@ struct Fp2p30 {
         const B y2 = sel(hi, ob, ob.neg16());         // lane0: 16p-b1  lane1: b0
         const B z1 = md.neg2();                       // lane0: 2p-d0   lane1: 2p-d1
         const B z2 = sel(hi, od.neg2(), od);          // lane0: d1      lane1: 2p-d0
-#ifdef G16_PAIR_Y3_SPLIT
-        // two two-sweep products and a lazy sum (one reduction more; measured no faster at three waves per SIMD: the passes are bound by
-        // their vector-instruction count, profiles/r06_ab_g2_three_waves.txt); output < 2 (1 + T / (R' p)) p
-        return B::template mul2_cols<uint64_t>(a0, mb, a1, y2).add(B::template mul2_cols<uint64_t>(c0, z1, c1, z2));
-#else
         return B::template mul4_cols<uint64_t>(a0, mb, a1, y2, c0, z1, c1, z2);
-#endif
     }
     G16_HD static B pair_mul_sub(bool hi, const B& ma, const B& oa, const B& mb, const B& ob, const B& mc, const B& oc, const B& md,
                                  const B& od) {
@@ -1045,25 +767,11 @@ struct Fp2p30 {
     G16_HD static Fp2p30 mul_add_fused_v(const Lhs& a, const Rhs& b, const Lhs& c, const Rhs& d) {
         return {B::template mul4_cols<uint64_t>(a.a0, b.m, a.a1, b.y2, c.a0, d.m, c.a1, d.y2)};
     }
-    // Measured in round 2 (profiles/r02_ab_mul_sub.txt, 2^22, same box) inside the register-resident accumulator: the fused form was
-    // 4.7 % FASTER for G1 (Fp30::mul_sub) but 5 % SLOWER here (27.9 -> 29.3 ms per G2 pass): eight operand sets + the column array
-    // exceeded the 256 VGPRs of a two-waves-per-SIMD kernel.  Acc30 therefore keeps two products (G16_PAIR_MUL_SUB opts in); the bucket
-    // pass, whose accumulator sits in LDS since round 4, uses mul_sub_fused below.
-    G16_HD static Fp2p30 mul_sub(const Fp2p30& a, const Fp2p30& b, const Fp2p30& c, const Fp2p30& d) {
-#ifdef G16_PAIR_MUL_SUB
-        return {pair_mul_sub_c(lane_hi(), comp0(a.c), comp1(a.c), b.c, swap(b.c), comp0(c.c), comp1(c.c), d.c, swap(d.c))};
-#else
-        return a.mul(b).template sub<2>(c.mul(d));
-#endif
-    }
-    // Round 4: with the accumulator parked in LDS (AccParked) the four-sweep form fits: 23.6 vs 24.0 ms per 2^22-point G2 pass on one
-    // box (profiles/r04_ab_parked_accumulator.txt), where round 2 measured it 5 % slower inside the register-resident Acc30
+    // Two products inside the register-resident Acc30: the four-sweep form's eight operand sets exceed the 256 registers of a
+    // two-waves-per-SIMD kernel there (DESIGN.md "Tried and retired").  The bucket pass, whose accumulator sits in LDS, uses mul_sub_fused.
+    G16_HD static Fp2p30 mul_sub(const Fp2p30& a, const Fp2p30& b, const Fp2p30& c, const Fp2p30& d) { return a.mul(b).template sub<2>(c.mul(d)); }
     G16_HD static Fp2p30 mul_sub_fused(const Fp2p30& a, const Fp2p30& b, const Fp2p30& c, const Fp2p30& d) {
-#ifdef G16_NO_MUL_SUB_FUSED
-        return a.mul(b).template sub<2>(c.mul(d));
-#else
         return {pair_mul_sub_c(lane_hi(), comp0(a.c), comp1(a.c), b.c, swap(b.c), comp0(c.c), comp1(c.c), d.c, swap(d.c))};
-#endif
     }
     G16_HD static Fp2p30 zero() { return {B::zero()}; }
     G16_HD static Fp2p30 one() { return {lane_hi() ? B::zero() : B::one()}; }
@@ -1094,7 +802,6 @@ struct Fp2p30 {
     G16_HD bool maybe_zero() const { return both(c.maybe_zero()); }
     G16_HD bool is_zero_exact() const { return both(c.is_zero_exact()); }
     static constexpr int KM = 2, K2M = 4, KX = 8, KY = 4;
-    G16_HD Fp2p30 settle() const { return *this; }
     // ---- batched-affine hooks (batch_affine.hpp): each lane of the pair handles its own component
     G16_HD Fp2p30 canonical_lt8p() const { return {c.canonical_lt8p()}; }
     G16_HD Fp2p30 neg_canonical() const { return {c.neg_canonical()}; }
@@ -1115,15 +822,8 @@ struct Fp2p30 {
 #ifndef G16_PAIR_MIN_WAVES
 #define G16_PAIR_MIN_WAVES 2
 #endif
-#ifndef G16_PAIR_PREFETCH
-#define G16_PAIR_PREFETCH false
-#endif
     static constexpr int ACC_MIN_WAVES = G16_PAIR_MIN_WAVES;
-    static constexpr bool ACC_PREFETCH = G16_PAIR_PREFETCH;
-#ifndef G16_PAIR_PARKED
-#define G16_PAIR_PARKED 1
-#endif
-    static constexpr bool ACC_PARKED = G16_PAIR_PARKED != 0;   // bucket pass: accumulator coordinates in LDS (AccParked)
+    static constexpr bool ACC_PREFETCH = false;
     // ---- bucket-kernel hooks: two lanes per task, each touching only its half of every Fq2 value
     static constexpr int LANES_PER_TASK = 2;
     template <class A>
@@ -1160,10 +860,9 @@ struct alignas(16) AccRaw {
     R x, y, zz, zzz;
 };
 
-// Lazy extended-Jacobian accumulator, F = Fp30<P> (G1), Fp2x30<P> or Fp2k30<P> (G2).  Invariants between
-// calls (per base-field component), "tight" fields (product outputs < 1.5p): x < 7.5p, y < 3.5p, zz, zzz < 1.8p;
-// Karatsuba field (product outputs < 6p): x, y < 2p (settled), zz, zzz < 6p.  The K of every subtraction is the
-// field's trait constant: KM for a product output, K2M for a doubled one, KX / KY for x / y; identity kept as a flag.
+// Lazy extended-Jacobian accumulator, F = Fp30<P> (G1), Fp2x30<P> or Fp2p30<P> (G2).  Invariants between calls (per base-field
+// component; product outputs < 1.5p): x < 7.5p, y < 3.5p, zz, zzz < 1.8p.  The K of every subtraction is the field's trait constant:
+// KM for a product output, K2M for a doubled one, KX / KY for x / y; identity kept as a flag.
 template <class F>
 struct Acc30 {
     typedef typename F::Std StdF;
@@ -1185,8 +884,8 @@ struct Acc30 {
         const F S = px.mul(V);
         const F X2 = px.sqr();
         const F M = X2.dbl().add(X2);             // < 3 * (square bound)
-        const F X3 = M.sqr().template sub<F::K2M>(S.dbl()).settle();
-        const F Y3 = F::mul_sub(M, S.template sub<F::KX>(X3), py, W).settle();
+        const F X3 = M.sqr().template sub<F::K2M>(S.dbl());
+        const F Y3 = F::mul_sub(M, S.template sub<F::KX>(X3), py, W);
         x = X3; y = Y3; zz = V; zzz = W;
         inf = false;
     }
@@ -1211,8 +910,8 @@ struct Acc30 {
         const F PP = Pd.sqr();
         const F PPP = Pd.mul(PP);
         const F Q = x.mul(PP);
-        const F X3 = R.sqr().template sub<F::KM>(PPP).template sub<F::K2M>(Q.dbl()).settle();
-        const F Y3 = F::mul_sub(R, Q.template sub<F::KX>(X3), y, PPP).settle();
+        const F X3 = R.sqr().template sub<F::KM>(PPP).template sub<F::K2M>(Q.dbl());
+        const F Y3 = F::mul_sub(R, Q.template sub<F::KX>(X3), y, PPP);
         x = X3;
         y = Y3;
         zz = zz.mul(PP);
@@ -1228,8 +927,8 @@ struct Acc30 {
         const F S = x.mul(V);
         const F X2 = x.sqr();
         const F M = X2.dbl().add(X2);
-        const F X3 = M.sqr().template sub<F::K2M>(S.dbl()).settle();
-        const F Y3 = F::mul_sub(M, S.template sub<F::KX>(X3), y, W).settle();
+        const F X3 = M.sqr().template sub<F::K2M>(S.dbl());
+        const F Y3 = F::mul_sub(M, S.template sub<F::KX>(X3), y, W);
         x = X3; y = Y3;
         zz = V.mul(zz);
         zzz = W.mul(zzz);
@@ -1254,8 +953,8 @@ struct Acc30 {
         const F PP = Pd.sqr();
         const F PPP = Pd.mul(PP);
         const F Q = U1.mul(PP);
-        const F X3 = R.sqr().template sub<F::KM>(PPP).template sub<F::K2M>(Q.dbl()).settle();
-        const F Y3 = F::mul_sub(R, Q.template sub<F::KX>(X3), S1, PPP).settle();
+        const F X3 = R.sqr().template sub<F::KM>(PPP).template sub<F::K2M>(Q.dbl());
+        const F Y3 = F::mul_sub(R, Q.template sub<F::KX>(X3), S1, PPP);
         x = X3;
         y = Y3;
         zz = zz.mul(o.zz).mul(PP);
@@ -1400,20 +1099,14 @@ struct AccParked {
         const F S = px.mul(s.ld(CZZ));
         const F X2 = px.sqr();
         const F M = X2.dbl().add(X2);             // < 3 * (square bound)
-        const F X3 = M.sqr().template sub<F::K2M>(S.dbl()).settle();
+        const F X3 = M.sqr().template sub<F::K2M>(S.dbl());
         s.st(CX, X3);
-        s.st(CY, F::mul_sub(M, S.template sub<F::KX>(X3), py, s.ld(CZZZ)).settle());   // (cold path: two plain products, fewer registers)
+        s.st(CY, F::mul_sub(M, S.template sub<F::KX>(X3), py, s.ld(CZZZ)));   // (cold path: two plain products, fewer registers)
         inf = false;
     }
     // madd-2008-s: this += (px, +-py), affine canonical px, py, not the identity; `minus`: subtract the point (the signed digit's sign)
     G16_HD void add_affine(const F& px, const F& py) { add_affine_signed(px, py, false); }
-    G16_HD bool flip_for(bool minus) const {
-#ifdef G16_NO_SIGN_TRACK
-        return minus;
-#else
-        return minus != (neg && !inf);   // the point takes the parked sum's sign as well
-#endif
-    }
+    G16_HD bool flip_for(bool minus) const { return minus != (neg && !inf); }   // the point takes the parked sum's sign as well
     G16_HD void add_affine_signed(const F& px, const F& py_in, bool minus) { add_affine_core(px, F::cond_neg2(py_in, flip_for(minus))); }
     // y as the window table holds it (packed words): negated there -- one subtract-with-borrow per word -- and unpacked once
     template <class YP>
@@ -1434,22 +1127,6 @@ struct AccParked {
                 return;
             }
         }
-#if defined(G16_NO_OPERAND_VIEWS) || defined(G16_NO_SIGN_TRACK)
-        const F PP = Pd.sqr();
-        s.st(CZZ, s.ld(CZZ).mul(PP));
-        const F PPP = Pd.mul(PP);
-        s.st(CZZZ, s.ld(CZZZ).mul(PPP));
-        const F Q = s.ld(CX).mul(PP);
-        static_assert(F::KM + F::K2M == 6, "sqr_sub_x3 subtracts from 6 p");
-        const F X3 = R.sqr_sub_x3(PPP, Q).settle();
-        s.st(CX, X3);
-#ifdef G16_NO_SIGN_TRACK
-        s.st(CY, F::mul_sub_fused(R, Q.template sub<F::KX>(X3), s.ld(CY), PPP).settle());
-#else
-        s.st(CY, F::mul_add_fused(R, X3.template sub<F::KM>(Q), s.ld(CY), PPP).settle());   // = -Y3: the parked sum changes sign
-        neg = !neg;
-#endif
-#else
         // every operand that enters more than one product is prepared once (F::lhs / F::rhs: the lane pair's broadcasts / negation)
         const typename F::Lhs PdL = F::lhs(Pd);
         const F PP = F::sqr_v(PdL);
@@ -1461,12 +1138,11 @@ struct AccParked {
         const F Q = F::mul_v(F::lhs(s.ld(CX)), PPr);
         static_assert(F::KM + F::K2M == 6, "sqr_sub_x3 subtracts from 6 p");
         const typename F::Lhs RL = F::lhs(R);
-        const F X3 = F::sqr_sub_x3_v(RL, PPP, Q).settle();   // R^2 + 6 p - (PPP + 2 Q), the subtraction inside the squaring's high columns
+        const F X3 = F::sqr_sub_x3_v(RL, PPP, Q);   // R^2 + 6 p - (PPP + 2 Q), the subtraction inside the squaring's high columns
         s.st(CX, X3);
         // R (X3 - Q) + y PPP = -Y3: a SUM of products, so the parked sum changes sign (see `neg`)
-        s.st(CY, F::mul_add_fused_v(RL, F::rhs(X3.template sub<F::KM>(Q)), F::lhs(s.ld(CY)), PPPr).settle());
+        s.st(CY, F::mul_add_fused_v(RL, F::rhs(X3.template sub<F::KM>(Q)), F::lhs(s.ld(CY)), PPPr));
         neg = !neg;
-#endif
     }
 };
 
@@ -1492,9 +1168,9 @@ G16_HD void acc_dbl_streamed(D& d, bool& d_inf) {
     const F S = d.ld(CX).mul(V);
     const F X2 = d.ld(CX).sqr();
     const F M = X2.dbl().add(X2);
-    const F X3 = M.sqr().template sub<F::K2M>(S.dbl()).settle();
+    const F X3 = M.sqr().template sub<F::K2M>(S.dbl());
     d.st(CX, X3);
-    d.st(CY, F::mul_sub(M, S.template sub<F::KX>(X3), d.ld(CY), W).settle());
+    d.st(CY, F::mul_sub(M, S.template sub<F::KX>(X3), d.ld(CY), W));
 }
 
 template <class F, class D, class S>
@@ -1523,9 +1199,9 @@ G16_HD void acc_add_streamed(D& d, bool& d_inf, const S& s, bool s_inf) {
     d.st(CZZZ, d.ld(CZZZ).mul(s.ld(CZZZ)).mul(PPP));
     const F Q = U1.mul(PP);
     static_assert(F::KM + F::K2M == 6, "sqr_sub_x3 subtracts from 6 p");
-    const F X3 = R.sqr_sub_x3(PPP, Q).settle();
+    const F X3 = R.sqr_sub_x3(PPP, Q);
     d.st(CX, X3);
-    d.st(CY, F::mul_sub(R, Q.template sub<F::KX>(X3), S1, PPP).settle());
+    d.st(CY, F::mul_sub(R, Q.template sub<F::KX>(X3), S1, PPP));
 }
 
 // host-side Store for the self-tests: plain memory

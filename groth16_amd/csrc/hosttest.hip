@@ -80,12 +80,6 @@ struct BoundF {
     static BoundF mul_sub_fused(const BoundF& a, const BoundF& bb, const BoundF& c, const BoundF& d) {
         check(d.b <= 2.0 - 1e-3, "mul_sub_fused: d not below 2p");
         const double A = a.b > c.b ? a.b : c.b;
-#ifdef G16_PAIR_Y3_SPLIT
-        if (ctx().pair) {   // two two-sweep products, summed lazily (fp30.hpp pair_mul_sub)
-            const double Bb = bb.b > 16.0 ? bb.b : 16.0;
-            return {product(a.b, Bb, a.b * bb.b + a.b * Bb).b + product(c.b, 2.0, 4.0 * c.b).b};
-        }
-#endif
         if (ctx().pair) return product(A, bb.b > 16.0 ? bb.b : 16.0, a.b * bb.b + a.b * (bb.b > 16.0 ? bb.b : 16.0) + 4.0 * c.b);
         return product(A, bb.b > 2.0 ? bb.b : 2.0, a.b * bb.b + 2.0 * c.b);
     }
@@ -112,7 +106,6 @@ struct BoundF {
         }
         return product(A, bb.b > d.b ? bb.b : d.b, a.b * bb.b + c.b * d.b);
     }
-    BoundF settle() const { return *this; }
     bool maybe_zero() const { check(b < 16.0, "zero test on a value not below 16p"); return false; }
     bool is_zero_exact() const { check(b < 16.0, "zero test on a value not below 16p"); return false; }
     static constexpr int KM = 2, K2M = 4, KX = 8, KY = 4;
@@ -250,61 +243,14 @@ struct SelfTest {
         return 0;
     }
 
-    // Column-overflow check of the carry-free product routines (fp30.hpp: wide_mul / wide_relax / wide_redc): every routine is
-    // run twice, with 64-bit and with 128-bit columns, on the worst limbs the representation allows (all 2^30 - 1) and on
+    // Column-overflow check of the product-scanning routines (fp30.hpp: fips<> behind mul_cols / sqr_cols / mul2_cols / mul4_cols): every
+    // routine is run twice, with 64-bit and with 128-bit accumulators, on the worst limbs the representation allows (all 2^30 - 1) and on
     // random limbs.  The 128-bit run cannot overflow; identical limbs out mean the 64-bit run did not either.
-    // WORST CASE over all inputs of every 64-bit column of the lazy product forms, by bound propagation through the very plan the
-    // kernels are generated from (col_count, G16_RELAX_LIMIT): operand limbs at most 2^30 - 1, every reduction multiplier m_i at most
-    // 2^30 - 1, the field's REAL modulus limbs.  (The all-ones-limbs shadow runs below exercise one m sequence; this covers them all.)
-    // sweeps = operand sweeps in front of the reduction: 1 (mul, sqr), 2 (lane-pair product, a b - c d), 4 (lane-pair a b - c d).
-    template <class R30>
-    static int column_headroom() {
-        typedef unsigned __int128 W;
-        constexpr int NL = R30::NL;
-        const W M = R30::MASK, LIM = (W)1 << 64;
-        const int forms[3] = {1, 2, 4};
-        for (int f = 0; f < 3; ++f) {
-            const int sweeps = forms[f];
-            W T[2 * NL];
-            for (int c = 0; c < 2 * NL; ++c) T[c] = 0;
-            for (int s = 1; s <= sweeps; ++s) {
-                for (int c = 0; c < 2 * NL - 1; ++c) {
-                    T[c] += (W)R30::col_count(c) * M * M;
-                    if (T[c] >= LIM) return 605;
-                }
-                for (int c = 0; c + 1 < 2 * NL; ++c)     // wide_relax<s>
-                    if ((s + 1) * R30::col_count(c) > G16_RELAX_LIMIT) {
-                        T[c + 1] += (T[c] >> 32) << 2;
-                        if (T[c + 1] >= LIM) return 606;
-                        if (T[c] > 0xffffffffu) T[c] = 0xffffffffu;
-                    }
-            }
-            W carry = 0;
-            for (int i = 0; i < NL; ++i) {                // wide_redc
-                T[i] += carry;
-                if (T[i] >= LIM) return 607;
-                for (int j = 0; j < NL; ++j) {
-                    T[i + j] += M * (W)R30::Params_t::p30(j);
-                    if (T[i + j] >= LIM) return 608;
-                }
-                carry = T[i] >> 30;
-            }
-            for (int j = 0; j < NL; ++j) {
-                const W v = T[NL + j] + carry;
-                if (v >= LIM) return 609;
-                carry = v >> 30;
-            }
-        }
-        return 0;
-    }
-
+    // The accumulator plan itself is proven at compile time by static_assert(fips_plan<NS>().ok), and against the generated assembly
+    // by fips_asm_plan_agrees.
     template <class R30>
     static int selftest_columns(uint64_t seed, int iters) {
         typedef unsigned __int128 U128;
-        {
-            const int rc = column_headroom<R30>();
-            if (rc) return rc;
-        }
         uint64_t st = seed ^ 0xC0;
         for (int it = 0; it < iters + 4; ++it) {
             R30 a, b, c, d;
@@ -318,23 +264,8 @@ struct SelfTest {
             if (!a.template mul_cols<uint64_t>(b).same_limbs(a.template mul_cols<U128>(b))) return 601;
             if (!a.template sqr_cols<uint64_t>().same_limbs(a.template sqr_cols<U128>())) return 602;
             // two- and four-sweep forms (Fq2 products, fused differences); d is fed as-is where the routine negates it
-            {
-                uint64_t T[2 * R30::NL];
-                U128 W[2 * R30::NL];
-                R30::wide_mul(T, a, b); R30::wide_mul(W, a, b);
-                R30::template wide_relax<1>(T); R30::template wide_relax<1>(W);
-                R30::wide_mul_add(T, c, d); R30::wide_mul_add(W, c, d);
-                R30::template wide_relax<2>(T); R30::template wide_relax<2>(W);
-                uint64_t T2[2 * R30::NL];
-                U128 W2[2 * R30::NL];
-                for (int k = 0; k < 2 * R30::NL; ++k) { T2[k] = T[k]; W2[k] = W[k]; }
-                if (!R30::wide_redc(T2).same_limbs(R30::wide_redc(W2))) return 603;
-                R30::wide_mul_add(T, b, c); R30::wide_mul_add(W, b, c);
-                R30::template wide_relax<3>(T); R30::template wide_relax<3>(W);
-                R30::wide_mul_add(T, a, d); R30::wide_mul_add(W, a, d);
-                R30::template wide_relax<4>(T); R30::template wide_relax<4>(W);
-                if (!R30::wide_redc(T).same_limbs(R30::wide_redc(W))) return 604;
-            }
+            if (!R30::template mul2_cols<uint64_t>(a, b, c, d).same_limbs(R30::template mul2_cols<U128>(a, b, c, d))) return 603;
+            if (!R30::template mul4_cols<uint64_t>(a, b, c, d, b, c, a, d).same_limbs(R30::template mul4_cols<U128>(a, b, c, d, b, c, a, d))) return 604;
         }
         return 0;
     }
@@ -777,22 +708,6 @@ struct SelfTest {
             if (!(FP::pair_mul_sub(true, a1, a0, b1, b0, c1, c0, d1, d0).to_std() == want_ms.c1)) return 3602;
             if (!(F30::template mul_sub_cols<uint64_t>(a0, b0, c0, d0).to_std() == x.c0 * y.c0 - (z.c0 + y.c0) * w.c0)) return 3603;
         }
-        // ---- the bucket kernel's Karatsuba Fq2 (register-passed products, settled accumulator)
-        typedef Fp2k30<typename Fq::Params> FK;
-        for (int it = 0; it < iters / 4 + 4; ++it) {
-            Fq2 x = {rand_fq(st), rand_fq(st)}, y = {rand_fq(st), rand_fq(st)};
-            if (it == 0) x = Fq2::zero();
-            if (it == 1) { x = {Fq::zero() - Fq::one(), Fq::zero() - Fq::one()}; y = x; }
-            const FK a = {to30(x.c0), to30(x.c1)}, b = {to30(y.c0), to30(y.c1)};
-            if (!(a.mul(b).to_std() == x * y)) return 30;
-            if (!(a.sqr().to_std() == x.sqr())) return 31;
-            const FK big1 = a.add(b).add(a).template sub<8>(b), big2 = b.template sub<8>(a).add(b);  // 2a (<12p), 2b - a (<11p)
-            if (!(big1.mul(big2).to_std() == (x + x) * (y + y - x))) return 32;
-            if (!(big1.sqr().to_std() == (x + x).sqr())) return 33;
-            const FK wide = big1.add(big1).template sub<16>(b);      // 4a - b, bound < 30p
-            if (!(wide.settle().to_std() == (x + x + x + x - y))) return 34;
-            if (!(wide.settle().mul(b).to_std() == (x + x + x + x - y) * y)) return 35;
-        }
         {
             const G2A gen2 = C::g2_generator();
             std::vector<G2A> pts2;
@@ -818,20 +733,6 @@ struct SelfTest {
                     ref.add_affine(seq[i]);
                     if (!(acc.to_std().to_affine() == ref.to_affine())) return 1000 + round * 100 + (int)i;
                     if (!(park2.gather().to_std().to_affine() == ref.to_affine())) return 5500 + round * 100 + (int)i;
-                }
-                {   // the same sequence through the Karatsuba accumulator used by the G2 bucket kernel
-                    Acc30<FK> ak = Acc30<FK>::identity();
-                    G2X rk = G2X::identity();
-                    for (size_t i = 0; i < seq.size(); ++i) {
-                        const FK px = {to30(seq[i].x.c0), to30(seq[i].x.c1)};
-                        FK py = {to30(seq[i].y.c0), to30(seq[i].y.c1)};
-                        G2A q = seq[i];
-                        if (i & 1) { py = py.neg2(); q = q.neg(); }
-                        ak.add_affine(px, py);
-                        rk.add_affine(q);
-                        if (!(ak.to_std().to_affine() == rk.to_affine())) return 3000 + round * 100 + (int)i;
-                        if (!(Acc30<FK>::from_packed(ak.to_packed()).to_std().to_affine() == rk.to_affine())) return 3500 + round * 100 + (int)i;
-                    }
                 }
                 // full add / dbl / small multiple on G2
                 Acc30<F230> other = Acc30<F230>::from_packed(acc.to_packed());
@@ -862,29 +763,6 @@ struct SelfTest {
                 if (!(other.to_std().to_affine() == ro.to_affine())) return 2000 + round;
                 uint32_t kw[1] = {12345u + (uint32_t)round};
                 if (!(acc.mul_small(kw[0]).to_std().to_affine() == ref.mul_bits(kw, 32).to_affine())) return 2100 + round;
-                {   // the reductions' use of the Karatsuba accumulator: raw-limb hand-over from the bucket pass, full
-                    // additions, doublings and small multiples chained on lazy values
-                    typedef AccRaw<F230> Raw;
-                    Raw slot;
-                    acc.store_raw(&slot);
-                    Acc30<FK> k1 = Acc30<FK>::load_raw(slot), k2 = Acc30<FK>::load_raw(slot);
-                    G2X r1 = ref, r2 = ref;
-                    for (int j = 0; j < 6; ++j) {
-                        k1.dbl(); r1 = r1.dbl();
-                        k1.add(k2); r1.add(r2);
-                        k2.add(k1); r2.add(r1);
-                        Raw tmp;
-                        k2.store_raw(&tmp);
-                        k2 = Acc30<FK>::load_raw(tmp);
-                        if (!(k1.to_std().to_affine() == r1.to_affine())) return 4000 + round * 10 + j;
-                        if (!(k2.to_std().to_affine() == r2.to_affine())) return 4100 + round * 10 + j;
-                    }
-                    Acc30<FK> same = k1;
-                    same.add(k1); r2 = r1; r2.add(r1);          // equal operands -> doubling branch
-                    if (!(same.to_std().to_affine() == r2.to_affine())) return 4200 + round;
-                    if (!(k1.mul_small(kw[0]).to_std().to_affine() == r1.mul_bits(kw, 32).to_affine())) return 4300 + round;
-                    if (!(k1.mul_small(32760u).to_std().to_affine() == r1.mul_bits((const uint32_t[]){32760u}, 16).to_affine())) return 4400 + round;
-                }
             }
         }
         return 0;

@@ -442,14 +442,6 @@ struct LdsAccStore {
     }
 };
 
-// The reduction kernels add with acc_add_streamed (fp30.hpp) for the fields whose limbs can be moved word by word (the same
-// fields whose bucket pass parks its accumulator); -DG16_REDUCE_STREAMED=0 rebuilds the register-resident form (A/B).
-#ifndef G16_REDUCE_STREAMED
-#define G16_REDUCE_STREAMED 1
-#endif
-template <class F30>
-static constexpr bool REDUCE_STREAMED = F30::ACC_PARKED && (G16_REDUCE_STREAMED != 0);
-
 // Stores for the reductions' streamed additions (acc_add_streamed, fp30.hpp).
 // An AccRaw record in LDS or global memory as the lane(s) of one task see it: coordinate k of a one-lane field is the k-th F30 of the
 // record; of the lane pair, component (lane parity) of the k-th Fq2.  Identity <=> zz is all-zero limbs (AccRaw).
@@ -538,28 +530,20 @@ __global__ __launch_bounds__(ACC_THREADS, F30::ACC_MIN_WAVES) void bucket_accumu
         if ((offsets[mid] >> off_shift) <= start) lo = mid; else hi = mid;
     }
     uint32_t b = lo, b_first = offsets[b] >> off_shift, b_end = offsets[b + 1] >> off_shift;
-    // F30::ACC_PARKED: the running sum's coordinates live in LDS (AccParked); otherwise in registers (Acc30)
-    __shared__ __attribute__((aligned(16))) uint32_t acc_lds[F30::ACC_PARKED ? 4 * F30::PREFIX_LIMBS * ACC_THREADS : 4];
-    typedef typename std::conditional<F30::ACC_PARKED, AccParked<F30, LdsAccStore<F30>>, Acc30<F30>>::type Acc;
-    Acc acc;
-    if constexpr (F30::ACC_PARKED) {
-        acc.s.quad = acc_lds + 4 * threadIdx.x;
-        acc.s.tail = acc_lds + 4 * LdsAccStore<F30>::QUADS * ACC_THREADS + threadIdx.x;
-        acc.inf = true;
-    } else {
-        acc = Acc30<F30>::identity();
-    }
-    auto flush = [&](AccRaw<typename F30::Raw>* dst) {
-        if constexpr (F30::ACC_PARKED) { acc.gather().store_raw(dst); acc.inf = true; }
-        else { acc.store_raw(dst); acc = Acc30<F30>::identity(); }
-    };
+    // the running sum's coordinates live in LDS (AccParked)
+    __shared__ __attribute__((aligned(16))) uint32_t acc_lds[4 * F30::PREFIX_LIMBS * ACC_THREADS];
+    AccParked<F30, LdsAccStore<F30>> acc;
+    acc.s.quad = acc_lds + 4 * threadIdx.x;
+    acc.s.tail = acc_lds + 4 * LdsAccStore<F30>::QUADS * ACC_THREADS + threadIdx.x;
+    acc.inf = true;
+    auto flush = [&](AccRaw<typename F30::Raw>* dst) { acc.gather().store_raw(dst); acc.inf = true; };
     // software pipeline: the base point of entry e+1 is gathered (and the sorted word of entry e+2 loaded) before the
     // ~20k-instruction addition of entry e, so the HBM latencies hide under arithmetic.  (Touching the cache lines of
     // entry e+2 with direct-to-LDS loads was tried for the window tables' wider gather: 25 % slower.)
     uint32_t v_next = 0;
-    // a parked accumulator takes y PACKED (12 words as gathered): the signed digit's negation costs one subtract-with-borrow per word
-    // there, and the unpacking happens once, when the point is added (AccParked::add_affine_packed)
-    typedef typename std::conditional<F30::ACC_PARKED, typename F30::PackedC, F30>::type YNext;
+    // y stays PACKED (12 words as gathered): the signed digit's negation costs one subtract-with-borrow per word there, and the
+    // unpacking happens once, when the point is added (AccParked::add_affine_packed)
+    typedef typename F30::PackedC YNext;
     F30 px_next = F30::zero();
     YNext py_next = YNext::zero();
     bool ok_next = false;
@@ -575,10 +559,7 @@ __global__ __launch_bounds__(ACC_THREADS, F30::ACC_MIN_WAVES) void bucket_accumu
         v_next = DIRECT ? 0u : v;
         int64_t at = (int64_t)v;
         ok_next = DIRECT ? true : decode(v, &at);
-        if (ok_next) {
-            if constexpr (F30::ACC_PARKED) ok_next = F30::load_point_py(bases, at, px_next, py_next);
-            else ok_next = F30::load_point(bases, at, px_next, py_next);
-        }
+        if (ok_next) ok_next = F30::load_point_py(bases, at, px_next, py_next);
     };
     fetch(DIRECT ? start : sorted[start]);
     uint32_t v_fetch = DIRECT ? start + 1 : (start + 1 < end ? sorted[start + 1] : 0u);   // entry e+1's word, loaded one iteration early
@@ -598,14 +579,7 @@ __global__ __launch_bounds__(ACC_THREADS, F30::ACC_MIN_WAVES) void bucket_accumu
             else v_fetch = e + 2 < end ? sorted[e + 2] : 0u;
         };
         if constexpr (F30::ACC_PREFETCH) advance();
-        if (ok) {
-            if constexpr (F30::ACC_PARKED) {
-                acc.add_affine_packed(px, py, (v >> 31) != 0);   // the digit's sign and the parked sum's sign are one flip (AccParked)
-            } else {
-                if (v >> 31) py = py.neg2();
-                acc.add_affine(px, py);
-            }
-        }
+        if (ok) acc.add_affine_packed(px, py, (v >> 31) != 0);   // the digit's sign and the parked sum's sign are one flip (AccParked)
         if constexpr (!F30::ACC_PREFETCH) advance();
     }
     flush(&partials[slot_off[b] + (t - b_first / lseg)]);
@@ -634,26 +608,12 @@ __global__ void convert_bases30_kernel(Affine<F>* __restrict__ pts, uint64_t n) 
     pts[i] = a;
 }
 
-template <class F> struct Lazy30;   // field used by the reduction kernels (and by the G1 bucket pass)
-template <class P> struct Lazy30<Fp<P>> { typedef Fp30<P> type; typedef Fp30<P> acc_type; };
-template <class P> struct Lazy30<Fp2<P>> {
-#if defined(G16_G2_REDUCE_FP2K30)
-    typedef Fp2k30<P> type;       // register-passed Karatsuba (same raw limb layout): less scratch, but one wave per SIMD --
-                                  // measured slower for the reductions (82.1 vs 80.8 ms per proof at 2^22, same box)
-#elif defined(G16_G2_REDUCE_FP2X30)
-    typedef Fp2x30<P> type;       // one lane per task, 4-product lazy Fq2 with out-of-line products (2.8 KB of scratch per lane)
-#else
-    typedef Fp2p30<P> type;       // reductions, too, on lane pairs: no scratch, each dependent group operation ~1.7x shorter --
-                                  // what bounds a rank's share of a sharded proof is the G2 reduction chain
-#endif
-#if defined(G16_G2_ACC_FP2X30)
-    typedef Fp2x30<P> acc_type;
-#elif defined(G16_G2_ACC_FP2K30)
-    typedef Fp2k30<P> acc_type;   // register-passed Karatsuba, one lane per bucket
-#else
-    typedef Fp2p30<P> acc_type;   // bucket pass: lane-pair Fq2 (two lanes per bucket, one component each)
-#endif
-};
+// field used by the bucket pass and the reduction kernels: Fq as it is; Fq2 on lane pairs (two lanes per bucket, one component each) --
+// no scratch, each dependent group operation ~1.7x shorter than one lane per task, and what bounds a rank's share of a sharded proof
+// is the G2 reduction chain (the one-lane Fq2 forms: DESIGN.md "Tried and retired")
+template <class F> struct Lazy30;
+template <class P> struct Lazy30<Fp<P>> { typedef Fp30<P> type; };
+template <class P> struct Lazy30<Fp2<P>> { typedef Fp2p30<P> type; };
 
 // ---------------------------------------------------------------------------------------------
 // 5b. heavy buckets: a bucket with many partial sums (short top window, repeated scalars such as the all-equal
@@ -688,7 +648,7 @@ struct ReduceBatch {
 
 // (task = one lane, or one lane pair for the lane-pair Fq2: both lanes of a pair run the same control flow)
 template <class F30>
-__global__ __launch_bounds__(HEAVY_THREADS, (REDUCE_STREAMED<F30> && F30::LANES_PER_TASK == 1) ? G16_FIRST_STAGE_WAVES : REDUCE_STREAMED<F30> ? 2 : 1) void heavy_reduce_kernel(ReduceBatch<AccRaw<typename F30::Raw>, XYZZ<typename F30::Std>> batch) {
+__global__ __launch_bounds__(HEAVY_THREADS, F30::LANES_PER_TASK == 1 ? G16_FIRST_STAGE_WAVES : 2) void heavy_reduce_kernel(ReduceBatch<AccRaw<typename F30::Raw>, XYZZ<typename F30::Std>> batch) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     AccRaw<typename F30::Raw>* sh = reinterpret_cast<AccRaw<typename F30::Raw>*>(smem);
     constexpr uint32_t LPT = F30::LANES_PER_TASK, TASKS = HEAVY_THREADS / LPT;
@@ -699,45 +659,28 @@ __global__ __launch_bounds__(HEAVY_THREADS, (REDUCE_STREAMED<F30> && F30::LANES_
     for (uint32_t i = blockIdx.x; i < nheavy; i += gridDim.x) {
         const uint32_t b = heavy[1 + i];
         const uint32_t t0 = slot_off[b], t1 = slot_off[b + 1];
-        if constexpr (REDUCE_STREAMED<F30>) {
-            // streamed additions (acc_add_streamed): the task's sum lives in its LDS record from the start, every operand
-            // coordinate is fetched where it is consumed -- no 8-coordinate operand pair in registers
-            __syncthreads();  // previous iteration's readers are done with sh / partials[t0]
-            const RawAccStore<F30> mine{&sh[task]};
-            bool inf = true;
-            for (uint32_t q = t0 + task; q < t1; q += TASKS) {
-                const RawAccStore<F30> src{&partials[q]};
-                acc_add_streamed<F30>(mine, inf, src, src.inf());
-            }
-            if (inf) mine.set_inf();
-            __syncthreads();
-            for (uint32_t d = TASKS / 2; d > 0; d >>= 1) {
-                if (task < d) {
-                    const RawAccStore<F30> other{&sh[task + d]};
-                    bool mi = mine.inf();
-                    const bool was = mi;
-                    acc_add_streamed<F30>(mine, mi, other, other.inf());
-                    if (mi && !was) mine.set_inf();
-                }
-                __syncthreads();
-            }
-            if (task == 0) Acc30<F30>::load_raw(sh[0]).store_raw(&partials[t0]);
-        } else {
-        Acc30<F30> acc = Acc30<F30>::identity();
-        for (uint32_t q = t0 + task; q < t1; q += TASKS) acc.add(Acc30<F30>::load_raw(partials[q]));
+        // streamed additions (acc_add_streamed): the task's sum lives in its LDS record from the start, every operand
+        // coordinate is fetched where it is consumed -- no 8-coordinate operand pair in registers
         __syncthreads();  // previous iteration's readers are done with sh / partials[t0]
-        acc.store_raw(&sh[task]);
+        const RawAccStore<F30> mine{&sh[task]};
+        bool inf = true;
+        for (uint32_t q = t0 + task; q < t1; q += TASKS) {
+            const RawAccStore<F30> src{&partials[q]};
+            acc_add_streamed<F30>(mine, inf, src, src.inf());
+        }
+        if (inf) mine.set_inf();
         __syncthreads();
         for (uint32_t d = TASKS / 2; d > 0; d >>= 1) {
             if (task < d) {
-                Acc30<F30> x = Acc30<F30>::load_raw(sh[task]);
-                x.add(Acc30<F30>::load_raw(sh[task + d]));
-                x.store_raw(&sh[task]);
+                const RawAccStore<F30> other{&sh[task + d]};
+                bool mi = mine.inf();
+                const bool was = mi;
+                acc_add_streamed<F30>(mine, mi, other, other.inf());
+                if (mi && !was) mine.set_inf();
             }
             __syncthreads();
         }
         if (task == 0) Acc30<F30>::load_raw(sh[0]).store_raw(&partials[t0]);
-        }
     }
 }
 
@@ -757,27 +700,21 @@ __global__ __launch_bounds__(RED_THREADS, F30::LANES_PER_TASK == 1 ? G16_FIRST_S
     if (b >= M) return;
     const uint32_t t0 = slot_off[b], np = slot_off[b + 1] - t0;
     if (np < 2 || np > HEAVY_PARTS) return;   // (heavy buckets were combined into [t0] by heavy_reduce_kernel)
-    if constexpr (REDUCE_STREAMED<F30>) {
-        const RawAccStore<F30> mine{&partials[t0]};
-        bool inf = mine.inf();
-        const bool was = inf;
-        for (uint32_t q = 1; q < np; ++q) {
-            const RawAccStore<F30> src{&partials[t0 + q]};
-            acc_add_streamed<F30>(mine, inf, src, src.inf());
-        }
-        if (inf && !was) mine.set_inf();
-    } else {
-        Acc30<F30> acc = Acc30<F30>::load_raw(partials[t0]);
-        for (uint32_t q = 1; q < np; ++q) acc.add(Acc30<F30>::load_raw(partials[t0 + q]));
-        acc.store_raw(&partials[t0]);
+    const RawAccStore<F30> mine{&partials[t0]};
+    bool inf = mine.inf();
+    const bool was = inf;
+    for (uint32_t q = 1; q < np; ++q) {
+        const RawAccStore<F30> src{&partials[t0 + q]};
+        acc_add_streamed<F30>(mine, inf, src, src.inf());
     }
+    if (inf && !was) mine.set_inf();
 }
 
 // ---------------------------------------------------------------------------------------------
 // 6. bucket reduction: chunk of G buckets per lane, then one workgroup per window
 // ---------------------------------------------------------------------------------------------
 template <class F30>
-__global__ __launch_bounds__(RED_THREADS, (F30::LANES_PER_TASK == 1 || REDUCE_STREAMED<F30>) ? 2 : 1) void bucket_reduce_kernel(ReduceBatch<AccRaw<typename F30::Raw>, XYZZ<typename F30::Std>> batch, uint32_t B, int W,
+__global__ __launch_bounds__(RED_THREADS, 2) void bucket_reduce_kernel(ReduceBatch<AccRaw<typename F30::Raw>, XYZZ<typename F30::Std>> batch, uint32_t B, int W,
                                                                     uint32_t G) {
     const AccRaw<typename F30::Raw>* __restrict__ partials = batch.partials[blockIdx.y];
     const uint32_t* __restrict__ slot_off = batch.slot_off[blockIdx.y];
@@ -787,53 +724,41 @@ __global__ __launch_bounds__(RED_THREADS, (F30::LANES_PER_TASK == 1 || REDUCE_ST
     const uint32_t t = (blockIdx.x * RED_THREADS + threadIdx.x) / F30::LANES_PER_TASK;   // lanes of one task are adjacent
     if (t >= cpw * (uint32_t)W) return;
     const uint32_t w = t / cpw, ch = t % cpw, b_lo = ch * G;
-    if constexpr (REDUCE_STREAMED<F30>) {
-        // two running sums, `run` (the buckets so far) and `tot` (the runs), added to with acc_add_streamed: the partial sums come
-        // straight from their records in memory, `tot` lives in LDS, and `run` in LDS too for the lane pair (for the one-lane field it
-        // stays in registers: 13 KB of LDS per workgroup keeps eight workgroups per CU for the batched G1 reduction of the tail)
-        constexpr bool PAIR = F30::LANES_PER_TASK == 2;
-        constexpr int SLOTS = PAIR ? 8 : 4;
-        __shared__ __attribute__((aligned(16))) uint32_t red_lds[SLOTS * F30::PREFIX_LIMBS * RED_THREADS];
-        static_assert(RED_THREADS == ACC_THREADS, "LdsAccStore is laid out for ACC_THREADS lanes");
-        LdsAccStore<F30> tot_s;
-        tot_s.quad = red_lds + 4 * threadIdx.x;
-        tot_s.tail = red_lds + 4 * LdsAccStore<F30>::QUADS * RED_THREADS + threadIdx.x;
-        typename std::conditional<PAIR, LdsAccStore<F30>, RegAccStore<F30>>::type run_s;
-        if constexpr (PAIR) {
-            run_s.quad = tot_s.quad + 4 * LdsAccStore<F30>::WORDS_PER_VALUE;
-            run_s.tail = tot_s.tail + 4 * LdsAccStore<F30>::WORDS_PER_VALUE;
-        }
-        bool run_inf = true, tot_inf = true;
-        for (uint32_t bb = G; bb-- > 0;) {
-            const uint32_t gb = w * B + b_lo + bb;
-            const uint32_t t0 = slot_off[gb];
-            if (slot_off[gb + 1] != t0) {   // the bucket's partial sums were combined into [t0] (heavy_reduce_kernel / bucket_combine_kernel)
-                const RawAccStore<F30> src{const_cast<AccRaw<typename F30::Raw>*>(&partials[t0])};
-                acc_add_streamed<F30>(run_s, run_inf, src, src.inf());
-            }
-            acc_add_streamed<F30>(tot_s, tot_inf, run_s, run_inf);
-        }
-        gather_acc<F30>(run_s, run_inf).store_raw(&chunk_sum[t]);
-        gather_acc<F30>(tot_s, tot_inf).store_raw(&chunk_out[t]);
-    } else {
-    Acc30<F30> run = Acc30<F30>::identity(), tot = Acc30<F30>::identity();
+    // two running sums, `run` (the buckets so far) and `tot` (the runs), added to with acc_add_streamed: the partial sums come
+    // straight from their records in memory, `tot` lives in LDS, and `run` in LDS too for the lane pair (for the one-lane field it
+    // stays in registers: 13 KB of LDS per workgroup keeps eight workgroups per CU for the batched G1 reduction of the tail)
+    constexpr bool PAIR = F30::LANES_PER_TASK == 2;
+    constexpr int SLOTS = PAIR ? 8 : 4;
+    __shared__ __attribute__((aligned(16))) uint32_t red_lds[SLOTS * F30::PREFIX_LIMBS * RED_THREADS];
+    static_assert(RED_THREADS == ACC_THREADS, "LdsAccStore is laid out for ACC_THREADS lanes");
+    LdsAccStore<F30> tot_s;
+    tot_s.quad = red_lds + 4 * threadIdx.x;
+    tot_s.tail = red_lds + 4 * LdsAccStore<F30>::QUADS * RED_THREADS + threadIdx.x;
+    typename std::conditional<PAIR, LdsAccStore<F30>, RegAccStore<F30>>::type run_s;
+    if constexpr (PAIR) {
+        run_s.quad = tot_s.quad + 4 * LdsAccStore<F30>::WORDS_PER_VALUE;
+        run_s.tail = tot_s.tail + 4 * LdsAccStore<F30>::WORDS_PER_VALUE;
+    }
+    bool run_inf = true, tot_inf = true;
     for (uint32_t bb = G; bb-- > 0;) {
         const uint32_t gb = w * B + b_lo + bb;
         const uint32_t t0 = slot_off[gb];
-        if (slot_off[gb + 1] != t0) run.add(Acc30<F30>::load_raw(partials[t0]));   // combined into [t0] by the two kernels above
-        tot.add(run);
+        if (slot_off[gb + 1] != t0) {   // the bucket's partial sums were combined into [t0] (heavy_reduce_kernel / bucket_combine_kernel)
+            const RawAccStore<F30> src{const_cast<AccRaw<typename F30::Raw>*>(&partials[t0])};
+            acc_add_streamed<F30>(run_s, run_inf, src, src.inf());
+        }
+        acc_add_streamed<F30>(tot_s, tot_inf, run_s, run_inf);
     }
     // sum_b (b+1) S_b over the chunk = tot + b_lo * run: the b_lo * run part is assembled from bit-plane sums of `run` over
     // the chunks by the window level and the host (MsmPlan) -- no scalar multiplication in this chain of dependent additions
-    run.store_raw(&chunk_sum[t]);
-    tot.store_raw(&chunk_out[t]);
-    }
+    gather_acc<F30>(run_s, run_inf).store_raw(&chunk_sum[t]);
+    gather_acc<F30>(tot_s, tot_inf).store_raw(&chunk_out[t]);
 }
 
 // grid = (groups, planes): plane 0 sums the chunks' weighted sums, plane 1 their plain sums, plane 2 + k the plain sums of the
 // chunks whose index has bit k set
 template <class F30>
-__global__ __launch_bounds__(WIN_THREADS, REDUCE_STREAMED<F30> ? 2 : 1) void window_reduce_kernel(ReduceBatch<AccRaw<typename F30::Raw>, XYZZ<typename F30::Std>> batch, uint32_t cpw) {
+__global__ __launch_bounds__(WIN_THREADS, 2) void window_reduce_kernel(ReduceBatch<AccRaw<typename F30::Raw>, XYZZ<typename F30::Std>> batch, uint32_t cpw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     AccRaw<typename F30::Raw>* sh = reinterpret_cast<AccRaw<typename F30::Raw>*>(smem);
     constexpr uint32_t LPT = F30::LANES_PER_TASK, TASKS = WIN_THREADS / LPT;
@@ -843,40 +768,25 @@ __global__ __launch_bounds__(WIN_THREADS, REDUCE_STREAMED<F30> ? 2 : 1) void win
     XYZZ<typename F30::Std>* __restrict__ window_sums = batch.window_sums[blockIdx.z];
     const AccRaw<typename F30::Raw>* src = (p == 0 ? chunk_out : chunk_sum) + (uint64_t)w * cpw;
     const uint32_t mask = p >= 2 ? 1u << (p - 2) : 0u;
-    if constexpr (REDUCE_STREAMED<F30>) {   // streamed additions, as in heavy_reduce_kernel
-        const RawAccStore<F30> mine{&sh[task]};
-        bool inf = true;
-        for (uint32_t j = task; j < cpw; j += TASKS)
-            if (!mask || (j & mask)) {
-                const RawAccStore<F30> s_j{const_cast<AccRaw<typename F30::Raw>*>(&src[j])};
-                acc_add_streamed<F30>(mine, inf, s_j, s_j.inf());
-            }
-        if (inf) mine.set_inf();
-        __syncthreads();
-        for (uint32_t d = TASKS / 2; d > 0; d >>= 1) {
-            if (task < d) {
-                const RawAccStore<F30> other{&sh[task + d]};
-                bool mi = mine.inf();
-                const bool was = mi;
-                acc_add_streamed<F30>(mine, mi, other, other.inf());
-                if (mi && !was) mine.set_inf();
-            }
-            __syncthreads();
-        }
-    } else {
-    Acc30<F30> acc = Acc30<F30>::identity();
+    // streamed additions, as in heavy_reduce_kernel
+    const RawAccStore<F30> mine{&sh[task]};
+    bool inf = true;
     for (uint32_t j = task; j < cpw; j += TASKS)
-        if (!mask || (j & mask)) acc.add(Acc30<F30>::load_raw(src[j]));
-    acc.store_raw(&sh[task]);
+        if (!mask || (j & mask)) {
+            const RawAccStore<F30> s_j{const_cast<AccRaw<typename F30::Raw>*>(&src[j])};
+            acc_add_streamed<F30>(mine, inf, s_j, s_j.inf());
+        }
+    if (inf) mine.set_inf();
     __syncthreads();
     for (uint32_t d = TASKS / 2; d > 0; d >>= 1) {
         if (task < d) {
-            Acc30<F30> x = Acc30<F30>::load_raw(sh[task]);
-            x.add(Acc30<F30>::load_raw(sh[task + d]));
-            x.store_raw(&sh[task]);
+            const RawAccStore<F30> other{&sh[task + d]};
+            bool mi = mine.inf();
+            const bool was = mi;
+            acc_add_streamed<F30>(mine, mi, other, other.inf());
+            if (mi && !was) mine.set_inf();
         }
         __syncthreads();
-    }
     }
     // the plane sums are what leaves the device: standard arkworks Montgomery radix
     if (task == 0) Acc30<F30>::load_raw(sh[0]).store_std(&window_sums[(uint64_t)w * gridDim.y + p]);
@@ -1211,7 +1121,7 @@ static int alloc_msm_buffers(const ScalarSort& ss, Arena& arena, MsmBuffers<F>* 
 template <class F>
 int msm_bucket_pass(const Affine<F>* d_bases, int64_t shift, uint64_t base_count, const ScalarSort& ss, Arena& arena, hipStream_t st,
                     MsmBuffers<F>* out, EventTimer* bucket_timer) {
-    typedef typename Lazy30<F>::acc_type F30;
+    typedef typename Lazy30<F>::type F30;
     typedef AccRaw<typename Lazy30<F>::type::Raw> Raw;
     const MsmPlan& plan = ss.plan;
     const uint32_t M = plan.buckets();
@@ -1285,7 +1195,7 @@ template <class F30>
 static unsigned pass_lds_pad() {
     static const int want = [] { const char* e = getenv("G16_PASS_WG_PER_CU"); return e ? atoi(e) : 0; }();
     if (want <= 0) return 0;
-    const unsigned own = F30::ACC_PARKED ? 4u * F30::PREFIX_LIMBS * ACC_THREADS * 4u : 16u;
+    const unsigned own = 4u * F30::PREFIX_LIMBS * ACC_THREADS * 4u;
     const unsigned per = (160u * 1024u / (unsigned)want) & ~255u;
     return per > own ? per - own : 0;
 }
@@ -1293,7 +1203,7 @@ static unsigned pass_lds_pad() {
 // the bucket passes of n <= PASS_BATCH MSMs with one bucket layout as ONE launch (PassBatch above)
 template <class F>
 int msm_bucket_pass_batch(const PassJob<F>* jobs, int n, Arena& arena, hipStream_t st, EventTimer* bucket_timer) {
-    typedef typename Lazy30<F>::acc_type F30;
+    typedef typename Lazy30<F>::type F30;
     typedef AccRaw<typename Lazy30<F>::type::Raw> Raw;
     if (n < 1 || n > PASS_BATCH) return G16_ERR_INTERNAL;
     const MsmPlan& plan = jobs[0].ss->plan;
@@ -1482,7 +1392,7 @@ __global__ __launch_bounds__(TABLE_THREADS, 2) void build_window_tables_kernel(c
 
 template <class F>
 size_t window_table_park_bytes(uint64_t n, int W) {
-    typedef typename Lazy30<F>::acc_type F30;
+    typedef typename Lazy30<F>::type F30;
     const uint64_t chunk = std::min(n ? n : 1, TABLE_CHUNK);
     return (size_t)4 * (W > 1 ? W - 1 : 1) * TableLane<F30>::B::NL * chunk * F30::LANES_PER_TASK * sizeof(uint32_t);
 }
@@ -1492,7 +1402,7 @@ size_t window_table_park_bytes(uint64_t n, int W) {
 // table while the previous one is being built); nullptr: allocated here, and the call returns with the table finished.
 template <class F>
 int build_window_tables(const Affine<F>* d_src, uint64_t n, int c, int W, Affine<F>* d_table, hipStream_t st, void* park_buf) {
-    typedef typename Lazy30<F>::acc_type F30;
+    typedef typename Lazy30<F>::type F30;
     static_assert(sizeof(Affine<F>) == 2 * TableLane<F30>::PARTS * sizeof(typename TableLane<F30>::B::Std), "affine point = x parts | y parts");
     if (n == 0) return G16_OK;
     if (W > TABLE_MAX_W) return G16_ERR_INTERNAL;

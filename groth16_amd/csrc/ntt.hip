@@ -59,34 +59,23 @@ static constexpr int NTT_ROW = NTT_TILE + NTT_TILE / 32;  // padded row length (
 template <class Fr>
 struct PowTable { Fr p[32]; };  // base^(2^j)
 
-// One twiddle as the butterflies consume it.  G16_NTT_TW_UNPACKED = 1: the NL 30-bit limbs themselves (9 words for the 255-bit scalar
-// fields instead of the 8 packed ones) -- no shift / mask / align work per butterfly; 0: the packed w*R' words of rounds 1-3.
-#ifndef G16_NTT_TW_UNPACKED
-#define G16_NTT_TW_UNPACKED 1
-#endif
+// One twiddle as the butterflies consume it: the NL 30-bit limbs themselves (9 words for the 255-bit scalar fields instead of the 8
+// packed ones) -- no shift / mask / align work per butterfly.
 template <class P>
-struct Tw { uint32_t w[G16_NTT_TW_UNPACKED ? Fp30<P>::NL : P::N]; };
+struct Tw { uint32_t w[Fp30<P>::NL]; };
 template <class P>
 __device__ __forceinline__ Fp30<P> load_tw(const Tw<P>& e) {
-#if G16_NTT_TW_UNPACKED
     Fp30<P> r;
     G16_UNROLL for (int i = 0; i < Fp30<P>::NL; ++i) r.l[i] = e.w[i];
     return r;
-#else
-    return Fp30<P>::unpack(e.w);
-#endif
 }
 template <class P>
 __global__ void tw_convert_kernel(const Fp<P>* __restrict__ in, Tw<P>* __restrict__ out, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Tw<P> e;
-#if G16_NTT_TW_UNPACKED
     const Fp30<P> x = Fp30<P>::unpack(in[i].v);
     G16_UNROLL for (int k = 0; k < Fp30<P>::NL; ++k) e.w[k] = x.l[k];
-#else
-    G16_UNROLL for (int k = 0; k < P::N; ++k) e.w[k] = in[i].v[k];
-#endif
     out[i] = e;
 }
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# builds the micro-benchmarks in three code-shape variants (field-mul inlined / outlined by reference / by value)
+# builds the micro-benchmarks (tools/ubench.hip) as the library builds its field code
 set -e
 cd "$(dirname "$0")/.."
 CS=groth16_amd/csrc
@@ -9,6 +9,5 @@ build() { # name, flags
 }
 rm -f tools/bin/ubench_*
 build default ""
-build fp2inline "-DG16_FP2X30_INLINE"
 wait
 ls -la tools/bin

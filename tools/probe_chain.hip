@@ -2,9 +2,8 @@
 // are one serial multiply-add chain per product.)
 //   chains = 1, 2, 4, 8: that many independent accumulators, round-robin, each step depending on the same accumulator's last step
 //   product kernels: Fp30<BLS12-381 Fq>::mul / sqr / mul_sub_fused in a dependent loop (x = x * y), as the library builds them
-//     (this file compiled twice: product scanning as generated assembly, and -DG16_NO_FIPS = round 5's operand-scanning form)
 // waves per SIMD = workgroups of 256 lanes per compute unit (register use permitting).
-// Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -mllvm -pragma-unroll-threshold=200000 [-DG16_NO_FIPS] tools/probe_chain.hip -o tools/bin/probe_chain[_nofips]
+// Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -mllvm -pragma-unroll-threshold=200000 tools/probe_chain.hip -o tools/bin/probe_chain
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -83,20 +82,14 @@ static int time_kernel(K launch, double* ms_out) {
 int main() {
     void* d_out;
     CK(hipMalloc(&d_out, sizeof(uint64_t) * (256 * 8 * 256 + 16)));
-#ifdef G16_NO_FIPS
-    const char* form = "operand scanning (round 5)";
-#else
     const char* form = "product scanning (generated assembly)";
-#endif
     for (int w : {1, 2, 3, 4, 6, 8}) {
         const int blocks = 256 * w, iters = 4096;
         double ms;
-#ifndef G16_NO_FIPS
 #define CHAIN(CHN)                                                                                                                       \
         if (time_kernel([&](int it) { hipLaunchKernelGGL((k_chain<CHN>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)d_out, it ? it : iters); }, &ms)) return 1; \
         printf("CHAIN chains=%d waves/SIMD=%d  %.2f T mad/s\n", CHN, w, 65536.0 * iters * 8 * w / (ms * 1e-3) / 1e12);
         CHAIN(1) CHAIN(2) CHAIN(4) CHAIN(8)
-#endif
 #define PROD(KIND, NAME, PER)                                                                                                              \
         if (time_kernel([&](int it) { hipLaunchKernelGGL((k_prod<KIND>), dim3(blocks), dim3(256), 0, 0, (uint32_t*)d_out, it ? it : 512); }, &ms)) return 1; \
         printf("PROD  %-40s %-10s waves/SIMD=%d  %.1f G products/s\n", form, NAME, w, 65536.0 * 512 * PER * w / (ms * 1e-3) / 1e9);
