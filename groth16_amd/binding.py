@@ -122,7 +122,7 @@ EXPORTS = [
     "g16_pk_load_bucket_shard", "g16_pk_rebind_bucket_shard", "g16_pk_get_info", "g16_msm_bucket_shard", "g16_host_msm_model_shard",
     "g16_abi_version", "g16_struct_size", "g16_get_timings_sized", "g16_pk_get_info_sized",
     "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
-    "g16_host_pairing", "g16_host_verify",
+    "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
 ]
 
 
@@ -233,6 +233,9 @@ class Lib:
         c.g16_pairing.argtypes = [C.c_void_p, u64p, u64p, C.c_uint64, u64p]
         c.g16_host_pairing.argtypes = [C.c_int, u64p, u64p, C.c_uint64, u64p]
         c.g16_host_verify.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, u64p, C.c_uint64, C.c_void_p]
+        c.g16_verify_aggregate.argtypes = [C.c_void_p, C.c_void_p, u64p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_void_p]
+        c.g16_host_verify_aggregate.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_void_p]
+        c.g16_host_verify_aggregate_gt.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, C.c_uint64, u64p, C.c_uint64, u64p, u64p, u64p]
 
     def check(self, status: int):
         if status == 0:

@@ -363,6 +363,19 @@ struct Pairing {
         }
         return r;
     }
+    // a^e for a canonical little-endian exponent of nbits bits (e = 0 gives 1), a in the cyclotomic subgroup
+    G16_HD_NOINLINE static F12 cyc_pow_bits(const F12& a, const uint32_t* e, int nbits) {
+        F12 r = F12::one();
+        bool started = false;
+        for (int i = nbits - 1; i >= 0; --i) {
+            if (started) r = r.cyc_sqr();
+            if ((e[i >> 5] >> (i & 31)) & 1u) {
+                r = started ? r * a : a;
+                started = true;
+            }
+        }
+        return r;
+    }
     G16_HD static F12 exp_by_x(const F12& a) {   // a^x
         const F12 r = cyc_pow(a, K::ATE_X_ABS);
         return K::ATE_X_NEG ? r.conj() : r;

@@ -1,0 +1,108 @@
+// What verify.hip (one verify_proof per lane) and verify_aggregate.hip (one equation per batch) share: the prepared key, its
+// per-device part, the window-table form of prepare_inputs and the curve dispatch of the entry points.
+#pragma once
+#include "internal.hpp"
+#include "pairing.hpp"
+#include <new>
+#include <vector>
+
+namespace g16 {
+int ctx_devices(const g16_ctx* ctx, int* curve, std::vector<int>& devs, std::vector<hipStream_t>& streams);   // api.hip
+
+constexpr int VERIFY_BLOCK = 64;
+
+// host reads of caller memory: the point / field structs are 16-byte aligned, a caller's u64 buffer need not be
+template <class T>
+T ld(const void* p) {
+    T t;
+    memcpy(&t, p, sizeof(T));
+    return t;
+}
+constexpr int WINDOWS = 64, DIGITS = 15;   // 4-bit windows of a 256-bit scalar; table entry [base][window][digit - 1]
+
+template <class C>
+using Aff1 = Affine<typename Pairing<C>::F>;
+
+// per-device part of a prepared key
+template <class C>
+struct PvkDev {
+    typedef Pairing<C> PP;
+    int device = -1;
+    typename PP::Ell* lines = nullptr;   // [2][NCOEFF]: -gamma, -delta
+    Aff1<C>* tables = nullptr;           // [nb][WINDOWS][DIGITS]
+    typename PP::F12* ab = nullptr;      // e(alpha, beta)
+    typename C::G1A* gabc0 = nullptr;    // gamma_abc_g1[0]
+    int id_flags = 0;                    // bit 0: gamma is the identity, bit 1: delta is (their pairs contribute 1)
+    void release() {
+        if (device >= 0) (void)hipSetDevice(device);
+        (void)hipFree(lines);
+        (void)hipFree(tables);
+        (void)hipFree(ab);
+        (void)hipFree(gabc0);
+        lines = nullptr; tables = nullptr; ab = nullptr; gabc0 = nullptr;
+    }
+};
+
+// IC = gabc0 + sum_j x_j gamma_abc[j + 1] from the window tables; x: num_public Fr (Montgomery)
+template <class C>
+__device__ __host__ inline Aff1<C> prepare_inputs_tab(const typename C::G1A& gabc0, const Aff1<C>* tables, const typename C::Fr* x,
+                                                      uint64_t num_public) {
+    typedef typename Pairing<C>::F F;
+    XYZZ<F> acc = XYZZ<F>::identity();
+    if (!gabc0.is_identity()) {
+        const typename Pairing<C>::A1 g = Pairing<C>::g1_in(gabc0);
+        acc = XYZZ<F>::from_affine(Aff1<C>{g.x, g.y});
+    }
+    for (uint64_t j = 0; j < num_public; ++j) {
+        uint32_t k[8];
+        x[j].to_canonical(k);
+        for (int w = 0; w < WINDOWS; ++w) {
+            const uint32_t d = (k[w >> 3] >> (4 * (w & 7))) & 0xfu;
+            if (d) acc.add_affine(tables[(j * WINDOWS + (uint64_t)w) * DIGITS + d - 1]);
+        }
+    }
+    return acc.to_affine();
+}
+
+}  // namespace g16
+
+// one prepared key: the curve, e(alpha, beta) in ark form, and one resident copy per device of the context.  gamma_g2, delta_g2 and
+// gamma_abc_g1 are also kept on the host (arkworks form) for the once-per-batch tail of g16_verify_aggregate.
+struct g16_pvk {
+    int curve = 0;
+    uint64_t n_gamma_abc = 0;
+    uint64_t ab[72] = {};
+    std::vector<uint64_t> gamma_g2, delta_g2, gamma_abc_g1;
+    std::vector<g16::PvkDev<g16::Bls12_381>> bls;
+    std::vector<g16::PvkDev<g16::Bn254>> bn;
+    ~g16_pvk() {
+        for (auto& d : bls) d.release();
+        for (auto& d : bn) d.release();
+    }
+};
+
+namespace g16 {
+template <class C>
+inline std::vector<PvkDev<C>>& devs_of(g16_pvk* p);
+template <>
+inline std::vector<PvkDev<Bls12_381>>& devs_of<Bls12_381>(g16_pvk* p) { return p->bls; }
+template <>
+inline std::vector<PvkDev<Bn254>>& devs_of<Bn254>(g16_pvk* p) { return p->bn; }
+
+inline bool vk_view_ok(const g16_vk_view* vk) {
+    return vk && vk->alpha_g1 && vk->beta_g2 && vk->gamma_g2 && vk->delta_g2 && vk->gamma_abc_g1 && vk->n_gamma_abc >= 1;
+}
+}  // namespace g16
+
+#define G16_VERIFY_DISPATCH(curve, EXPR)                                                  \
+    do {                                                                                  \
+        try {                                                                             \
+            if ((curve) == G16_BLS12_381) { typedef Bls12_381 CC; return EXPR; }          \
+            if ((curve) == G16_BN254) { typedef Bn254 CC; return EXPR; }                  \
+            return G16_ERR_BAD_ARG;                                                       \
+        } catch (const std::bad_alloc&) {                                                 \
+            return G16_ERR_OOM;                                                           \
+        } catch (...) {                                                                   \
+            return G16_ERR_INTERNAL;                                                      \
+        }                                                                                 \
+    } while (0)

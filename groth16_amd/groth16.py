@@ -509,6 +509,23 @@ class Groth16:
         from .verifier import verify_batch
         return verify_batch(self._ctx, pvk, proofs, public_inputs_list)
 
+    def verify_aggregate_verdict(self, pvk, proofs, public_inputs_list, coeffs=None) -> int:
+        """g16_verify_aggregate: the whole batch in one randomised equation with one final exponentiation.  1 every proof is
+        accepted, 0 at least one is not, 2 a point is off its curve.  coeffs: one non-zero 128-bit integer per proof, fixed after
+        the proofs; None draws them from the operating system.  Sound for proofs whose points are in the prime-order subgroups
+        (proof_from_bytes(validate=2) checks that)."""
+        from .verifier import verify_aggregate
+        return verify_aggregate(self._ctx, pvk, proofs, public_inputs_list, coeffs)
+
+    def verify_proofs_aggregate(self, pvk, proofs, public_inputs_list, coeffs=None) -> bool:
+        return self.verify_aggregate_verdict(pvk, proofs, public_inputs_list, coeffs) == 1
+
+    def verify_proofs_aggregate_or_each(self, pvk, proofs, public_inputs_list) -> np.ndarray:
+        """a bool per proof: the aggregate check first, and only if it fails verify_proofs to name the culprits"""
+        if self.verify_proofs_aggregate(pvk, proofs, public_inputs_list):
+            return np.ones(len(public_inputs_list), dtype=bool)
+        return self.verify_proofs(pvk, proofs, public_inputs_list)
+
     def pairing(self, g1s: np.ndarray, g2s: np.ndarray) -> np.ndarray:
         """prod e(g1s[i], g2s[i]) on the GPU (GT as arkworks' 12 Fq limbs)"""
         from .verifier import device_pairing

@@ -1,5 +1,6 @@
 """Groth16 verification (src/verifier.rs:13-76, src/lib.rs:84-96) through the library's pairing: the batch form runs one proof per
-GPU lane (g16_verify_batch); ``verify_proof_host`` runs the same C++ templates on the CPU (g16_host_verify)."""
+GPU lane (g16_verify_batch); ``verify_proof_host`` runs the same C++ templates on the CPU (g16_host_verify).  The aggregate form
+(g16_verify_aggregate / g16_host_verify_aggregate) checks a whole batch under one key in one randomised equation."""
 from __future__ import annotations
 
 import ctypes as C
@@ -94,18 +95,96 @@ def verify_batch(ctx, pvk: PreparedVerifyingKey, proofs, public_inputs_list) -> 
     """verdict bytes: 1 accept, 0 reject, 2 a proof point is not on its curve"""
     flat = _flat_proofs(proofs, pvk.curve)
     n = flat.shape[0]
-    if len(public_inputs_list) != n:
-        raise ValueError("one public-input vector per proof")
-    rows = [_c(x).reshape(-1, 4) if len(x) else np.zeros((0, 4), dtype=np.uint64) for x in public_inputs_list]
-    num_public = rows[0].shape[0] if n else pvk.vk.num_public
-    if any(r.shape[0] != num_public for r in rows):
-        raise ValueError("every proof of a batch needs the same number of public inputs")
-    x = np.ascontiguousarray(np.concatenate(rows).reshape(-1)) if n and num_public else np.zeros(0, dtype=np.uint64)
+    x, num_public = _flat_inputs(public_inputs_list, n, pvk.vk.num_public)
     verdicts = np.zeros(n, dtype=np.uint8)
     lb = lib()
     lb.check(lb.c.g16_verify_batch(ctx.handle, pvk.handle, ptr64(flat.reshape(-1)), n, ptr64(x) if x.size else None, num_public,
                                    verdicts.ctypes.data_as(C.c_void_p)))
     return verdicts
+
+
+def _flat_inputs(public_inputs_list, n, default_num_public):
+    """(flat words, inputs per proof) of one vector of Fr rows per proof; an (n, num_public, 4) uint64 array is taken as it is"""
+    if len(public_inputs_list) != n:
+        raise ValueError("one public-input vector per proof")
+    if isinstance(public_inputs_list, np.ndarray) and public_inputs_list.dtype == np.uint64 and public_inputs_list.ndim == 3 and n:
+        if public_inputs_list.shape[2] != 4:
+            raise ValueError("an Fr element is 4 words")
+        return np.ascontiguousarray(public_inputs_list).reshape(-1), public_inputs_list.shape[1]
+    rows = [_c(x).reshape(-1, 4) if len(x) else np.zeros((0, 4), dtype=np.uint64) for x in public_inputs_list]
+    num_public = rows[0].shape[0] if n else default_num_public
+    if any(r.shape[0] != num_public for r in rows):
+        raise ValueError("every proof of a batch needs the same number of public inputs")
+    x = np.ascontiguousarray(np.concatenate(rows).reshape(-1)) if n and num_public else np.zeros(0, dtype=np.uint64)
+    return x, num_public
+
+
+def _flat_coeffs(coeffs, n):
+    """None, or n 128-bit coefficients (Python ints, or an (n, 2) array of little-endian 64-bit words) as n x 2 words"""
+    if coeffs is None:
+        return None
+    if isinstance(coeffs, np.ndarray) and coeffs.dtype == np.uint64:
+        out = _c(coeffs).reshape(-1, 2)
+    else:
+        ints = [int(r) for r in coeffs]
+        if any(r < 0 or r >> 128 for r in ints):
+            raise ValueError("a coefficient is a 128-bit unsigned integer")
+        out = np.array([[r & (2**64 - 1), r >> 64] for r in ints], dtype=np.uint64).reshape(-1, 2)
+    if out.shape[0] != n:
+        raise ValueError("one coefficient per proof")
+    return np.ascontiguousarray(out)
+
+
+def verify_aggregate(ctx, pvk: PreparedVerifyingKey, proofs, public_inputs_list, coeffs=None) -> int:
+    """g16_verify_aggregate's verdict: 1 every proof holds, 0 the aggregate equation fails, 2 a point is off its curve"""
+    flat = _flat_proofs(proofs, pvk.curve)
+    n = flat.shape[0]
+    x, num_public = _flat_inputs(public_inputs_list, n, pvk.vk.num_public)
+    r = _flat_coeffs(coeffs, n)
+    v = np.zeros(1, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_verify_aggregate(ctx.handle, pvk.handle, ptr64(flat.reshape(-1)) if n else None, n, ptr64(x) if x.size else None,
+                                       num_public, ptr64(r.reshape(-1)) if r is not None and n else None, v.ctypes.data_as(C.c_void_p)))
+    return int(v[0])
+
+
+def _host_aggregate_args(curve, vk, proofs, public_inputs_list, coeffs):
+    vkk = as_vk(vk)
+    flat = _flat_proofs(proofs, curve)
+    n = flat.shape[0]
+    x, num_public = _flat_inputs(public_inputs_list, n, vkk.num_public)
+    r = _flat_coeffs(coeffs, n)
+    view, keep = vkk.view()
+    args = (CURVE_ID[curve], C.byref(view), ptr64(flat.reshape(-1)) if n else None, n, ptr64(x) if x.size else None, num_public,
+            ptr64(r.reshape(-1)) if r is not None and n else None)
+    return args, (view, keep, flat, x, r)
+
+
+def host_aggregate_verdict(curve: str, vk, proofs, public_inputs_list, coeffs=None) -> int:
+    """g16_host_verify_aggregate's verdict byte (1 / 0 / 2)"""
+    args, keep = _host_aggregate_args(curve, vk, proofs, public_inputs_list, coeffs)
+    v = np.zeros(1, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_host_verify_aggregate(*args, v.ctypes.data_as(C.c_void_p)))
+    del keep
+    return int(v[0])
+
+
+def verify_proofs_aggregate_host(curve: str, vk, proofs, public_inputs_list, coeffs=None) -> bool:
+    """the randomised batch equation on the CPU: True iff every proof of the batch is accepted (see g16_verify_aggregate for the
+    soundness contract); coeffs=None draws the coefficients from the operating system"""
+    return host_aggregate_verdict(curve, vk, proofs, public_inputs_list, coeffs) == 1
+
+
+def host_aggregate_gt(curve: str, vk, proofs, public_inputs_list, coeffs):
+    """(lhs, rhs): the two GT values the aggregate equation compares, as arkworks' 12 Fq limbs"""
+    args, keep = _host_aggregate_args(curve, vk, proofs, public_inputs_list, coeffs)
+    L = FQ_LIMBS[curve]
+    lhs, rhs = np.zeros(12 * L, dtype=np.uint64), np.zeros(12 * L, dtype=np.uint64)
+    lb = lib()
+    lb.check(lb.c.g16_host_verify_aggregate_gt(*args, ptr64(lhs), ptr64(rhs)))
+    del keep
+    return lhs, rhs
 
 
 def verify_batch_prepared(ctx, pvk: PreparedVerifyingKey, proofs, prepared_inputs) -> np.ndarray:

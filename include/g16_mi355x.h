@@ -411,6 +411,27 @@ int g16_pairing(g16_ctx* ctx, const uint64_t* g1s, const uint64_t* g2s, uint64_t
 int g16_host_pairing(int curve, const uint64_t* g1s, const uint64_t* g2s, uint64_t n_pairs, uint64_t* out_fq12);
 int g16_host_verify(int curve, const g16_vk_view* vk, const uint64_t* proof, const uint64_t* public_inputs, uint64_t num_public,
                     uint8_t* verdict);
+/* Randomised batch verification: ALL n proofs under one key in one equation with one final exponentiation,
+ *   FE(prod_i ML(r_i A_i, B_i) * ML(sum_i r_i IC_i, -gamma) * ML(sum_i r_i C_i, -delta)) == e(alpha, beta)^(sum_i r_i).
+ * *verdict: 1 every proof is accepted; 0 the equation fails (at least one proof is invalid; g16_verify_batch names it); 2 some
+ * proof has a point off its curve (2 wins over 0).  n = 0 gives 1.
+ * coeffs: n x 2 words, the little-endian 128-bit r_i; a zero coefficient is G16_ERR_BAD_ARG (its proof would drop out of the check).
+ * Explicit coefficients make the call deterministic and let a caller supply transcript-derived values; they must be fixed AFTER the
+ * proofs.  coeffs == NULL: the library draws them from the operating system's generator (getrandom(2)), redrawing a zero.
+ * Contract: a batch with an invalid proof is accepted with probability about 2^-127 over the coefficients, PROVIDED the points of
+ * every proof lie in the prime-order subgroups -- what the reference guarantees by deserialising with Validate::Yes and what
+ * g16_deserialize_points with validation does here.  Like verify_proof itself, this function checks on-curve only.
+ * G16_ERR_MALFORMED_VK as g16_verify_batch.  A multi-device ctx cuts the batch into one chunk per device; the once-per-batch tail
+ * (two prepared pairs, the final exponentiation, the GT power) runs on the calling host thread. */
+int g16_verify_aggregate(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
+                         uint64_t num_public, const uint64_t* coeffs, uint8_t* verdict);
+/* the same templates on the CPU */
+int g16_host_verify_aggregate(int curve, const g16_vk_view* vk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
+                              uint64_t num_public, const uint64_t* coeffs, uint8_t* verdict);
+/* the two GT values that equation compares (arkworks' 12 Fq each), for explicit coefficients and n >= 1; G16_ERR_BAD_ARG if a point
+ * is off its curve, G16_ERR_UNEXPECTED_IDENTITY if the Miller product is 0 */
+int g16_host_verify_aggregate_gt(int curve, const g16_vk_view* vk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
+                                 uint64_t num_public, const uint64_t* coeffs, uint64_t* lhs_fq12, uint64_t* rhs_fq12);
 
 const char* g16_strerror(int status);
 /* text of the last HIP error seen on this thread ("" if none) */
