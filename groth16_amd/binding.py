@@ -123,6 +123,7 @@ EXPORTS = [
     "g16_abi_version", "g16_struct_size", "g16_get_timings_sized", "g16_pk_get_info_sized",
     "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
+    "g16_dev_fp30_op", "g16_host_fp30_op",
 ]
 
 
@@ -236,6 +237,8 @@ class Lib:
         c.g16_verify_aggregate.argtypes = [C.c_void_p, C.c_void_p, u64p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_void_p]
         c.g16_host_verify_aggregate.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_void_p]
         c.g16_host_verify_aggregate_gt.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, C.c_uint64, u64p, C.c_uint64, u64p, u64p, u64p]
+        c.g16_dev_fp30_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
+        c.g16_host_fp30_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
 
     def check(self, status: int):
         if status == 0:

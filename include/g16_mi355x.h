@@ -379,6 +379,32 @@ int g16_host_msm_model_shard(int curve, int g2, const uint64_t* bases, const uin
  * standard field / group code; 0 = all checks passed, otherwise the number of the first failing check */
 int g16_host_selftest(int curve, uint64_t seed, int iters);
 
+/* ---- the field lab (test hooks): ONE operation of the kernels' 30-bit-limb field arithmetic on raw limbs ----
+ * g16_dev_fp30_op runs one tuple per lane on the ctx's (first) GPU -- the product forms through the generated assembly blocks, the
+ * lane-pair forms with one Fq2 value per adjacent lane pair -- and g16_host_fp30_op runs the same code compiled for the host.
+ * field: 0 Fr, 1 Fq of the curve.  A slot is NL 32-bit words (NL = 13 for BLS12-381's Fq, 9 for the other three fields): 30-bit limbs,
+ * or the packed / standard form's 32-bit words padded with zeros, or a flag / small integer in word 0.  operands: n tuples of `in`
+ * slots; out: n tuples of `out` slots.  Preconditions are those of fp30.hpp; nothing is checked.  form (in -> out slots):
+ *   0 mul (2->1)  1 sqr (1)  2 mul2 = x0 y0 + x1 y1 (4)  3 mul4 (8)  4 / 6 / 8 mul_s2 / _s4 / _s8 = x y + K p - s (3)
+ *   5 / 7 / 9 mul2_s2 / _s4 / _s8 (5)  10 mul_x3 = x y + 6 p - (u + 2 v) (4)  11 sqr_x3 (3)                      [4..11: Fq only]
+ *   20..24 sub<K> = a + K p - b for K = 2, 4, 6, 8, 16 (2)  25 add_dbl = a + 2 b (2)  26 normalize (1)
+ *   27 sub_pow2(a, b, k) = a + 2^(k+1) p - b, k in word 0 of the third slot (3; Fr only)
+ *   28 unpack_cond_neg(packed y, flip) and cond_neg2(unpack(y), flip) (2->2)
+ *   30..33 cond_sub<K> for K = 2, 4, 8, 16  34 weak_reduce32  35 canonical_lt2p  36 canonical_lt8p  37 canonical_quick
+ *   38 neg_canonical  39 maybe_zero (flag)  40 is_zero_exact (flag)  41 to_std (words out)  42 std_to_r30 (words in and out)
+ *   43 to_packed (words out)                                                                                       [30..43: 1->1]
+ *   50 Fp2x30 mul (a0 a1 b0 b1 -> c0 c1)  51 Fp2x30 sqr (2->2)                                                      [Fq only]
+ *   lane pair (Fq only; Fq2 operand k in slots 2 k, 2 k + 1; 2 slots out): 60 mul_v(lhs a, rhs b)  61 sqr_v(lhs a)
+ *   62 sqr_sub_x3_v(lhs a, u, v)  63 mul_add_fused(a, b, c, d)  64 mul_sub_fused(a, b, c, d) (pair_mul_sub)
+ *   65 mul_add_fused_v(lhs a, rhs b, lhs c, rhs d)
+ *   accumulator (Fq only): a lazy XYZZ accumulator (Acc30) takes up to three mixed additions.  70 G1 (11 -> 5 slots), 71 G2 one lane,
+ *   72 G2 lane pair (21 -> 9; device only).  A field element takes C slots (1 for Fq, 2 for Fq2).  in: x y zz zzz raw lazy limbs |
+ *   a flag slot: word 0 the accumulator is the identity, word 1 the number of points, word 2 + j point j is the identity | x y of
+ *   three affine points (limbs, below 2 p).  out: x y zz zzz canonical in the packed form's words | word 0: the result is the identity
+ * G16_ERR_BAD_ARG for an unknown form or one the field does not have, n == 0 or n > 2^22. */
+int g16_dev_fp30_op(g16_ctx* ctx, int field, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
+int g16_host_fp30_op(int curve, int field, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
+
 /* ---- verifier (src/verifier.rs:13-76, src/lib.rs:84-96) ------------------------------------------------------------
  * GT values cross as 12 Fq in arkworks' order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1 (Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - xi)),
  * Montgomery limbs as every other field element: byte-equal to PairingOutput.0.  Pairings are optimal ate with the exact final

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Sanitizer tier: AddressSanitizer + UndefinedBehaviorSanitizer builds of the product's HOST code (api.hip, serialize.hip,
-# hosttest.hip and the host halves of every other translation unit; device code is compiled as usual, -fno-gpu-sanitize) and of the
+# hosttest.hip, devtest.hip's host twin of the field lab and the host halves of every other translation unit; device code is compiled as usual, -fno-gpu-sanitize) and of the
 # CPU oracle, then the whole CPU test tier (`-m "not gpu and not perf"`) against them.  No GPU needed.
 #   tools/sanitize.sh build   -> groth16_amd/libg16_asan.so, oracle/libg16_oracle_asan.so   (~10 min on 8 cores)
 #   tools/sanitize.sh test [pytest args]   -> runs the tier; a sanitizer report aborts the process, so a green run means none fired
