@@ -124,6 +124,7 @@ EXPORTS = [
     "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
     "g16_dev_fp30_op", "g16_host_fp30_op",
+    "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
 ]
 
 
@@ -237,6 +238,10 @@ class Lib:
         c.g16_verify_aggregate.argtypes = [C.c_void_p, C.c_void_p, u64p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_void_p]
         c.g16_host_verify_aggregate.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_void_p]
         c.g16_host_verify_aggregate_gt.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, C.c_uint64, u64p, C.c_uint64, u64p, u64p, u64p]
+        c.g16_verify_aggregate_checked.argtypes = c.g16_verify_aggregate.argtypes
+        c.g16_check_subgroups.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, C.c_void_p]
+        c.g16_check_proof_subgroups.argtypes = [C.c_void_p, u64p, C.c_uint64, C.c_void_p]
+        c.g16_host_check_subgroups.argtypes = [C.c_int, C.c_int, u64p, C.c_uint64, C.c_void_p]
         c.g16_dev_fp30_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_fp30_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
 

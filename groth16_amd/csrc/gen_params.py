@@ -12,6 +12,9 @@ the sextic non-residue xi = s + u (Fq6 = Fq2[v]/(v^3 - xi), Fq12 = Fq6[w]/(w^2 -
 coefficients gamma[j][k] = xi^(k (q^j - 1) / 6) that map a w^k coefficient under the j-th power of Frobenius (j = 1..3,
 k = 1..5: Fq6 = even k, Fq12 = odd k; Fq2's own Frobenius is conjugation), 1/2, and the loop parameters: BLS12-381
 |x| with x negative, BN254 6x + 2 as non-adjacent signed digits and x for the final exponentiation.
+
+Membership constants (subgroup.hpp): BLS12-381 beta (G1's endomorphism) and psi's two coefficients on the M-type twist,
+BN254 6x^2 (psi's eigenvalue on G2).
 """
 import os
 
@@ -140,6 +143,84 @@ def naf(n):
     return out  # little-endian digits in {-1, 0, 1}
 
 
+def fq2_inv(a, q):
+    n = pow((a[0] * a[0] + a[1] * a[1]) % q, q - 2, q)
+    return (a[0] * n % q, -a[1] * n % q)
+
+
+def ec_add(P, Q, q):
+    """affine addition on y^2 = x^3 + b over Fq2 (Fq embeds as (a, 0)); None is the identity"""
+    if P is None:
+        return Q
+    if Q is None:
+        return P
+    sub = lambda a, b: ((a[0] - b[0]) % q, (a[1] - b[1]) % q)
+    if P[0] == Q[0]:
+        if P[1] != Q[1] or P[1] == (0, 0):
+            return None
+        x2 = fq2_mul(P[0], P[0], q)
+        lam = fq2_mul(((3 * x2[0]) % q, (3 * x2[1]) % q), fq2_inv(((2 * P[1][0]) % q, (2 * P[1][1]) % q), q), q)
+    else:
+        lam = fq2_mul(sub(Q[1], P[1]), fq2_inv(sub(Q[0], P[0]), q), q)
+    x3 = sub(sub(fq2_mul(lam, lam, q), P[0]), Q[0])
+    return (x3, sub(fq2_mul(lam, sub(P[0], x3), q), P[1]))
+
+
+def ec_mul(P, k, q):
+    acc = None
+    for bit in bin(k)[2:]:
+        acc = ec_add(acc, acc, q)
+        if bit == "1":
+            acc = ec_add(acc, P, q)
+    return acc
+
+
+def subgroup_consts(c):
+    """lines of the Consts struct that subgroup.hpp reads: the endomorphism constants of the membership tests, each checked
+    here against a big-int scalar multiple of the generator (so the right root is chosen now, not by trial at run time)"""
+    q, r, x, xi = c["q"], c["r"], c["x"], (c["xi"], 1)
+    nl = (q.bit_length() + 29) // 30
+    conj = lambda a: (a[0], -a[1] % q)
+    g1 = ((c["g1"][0], 0), (c["g1"][1], 0))
+    g2 = ((c["g2"][0], c["g2"][1]), (c["g2"][2], c["g2"][3]))
+    o = []
+
+    def emit(name, rows):
+        o.append("    G16_HD static constexpr uint32_t %s(int k, int i) {" % name)
+        o.append("        constexpr uint32_t t[%d][%d] = {%s};" % (len(rows), nl, ", ".join(arr(mont30(v, q)) for v in rows)))
+        o.append("        return t[k][i];")
+        o.append("    }")
+
+    if c["xi"] == 1:
+        # G1: phi(x, y) = (beta x, y) acts on the r-torsion as -x^2 (a root of l^2 + l + 1 mod r = x^4 - x^2 + 1)
+        assert r == x ** 4 - x ** 2 + 1
+        g = 2
+        while pow(g, (q - 1) // 3, q) == 1:
+            g += 1
+        b = pow(g, (q - 1) // 3, q)
+        want = ec_mul(g1, (-x * x) % r, q)
+        beta = [v for v in (b, b * b % q) if ((v * g1[0][0] % q, 0), g1[1]) == want]
+        assert len(beta) == 1 and pow(beta[0], 3, q) == 1 and beta[0] != 1
+        o.append("    // beta: the cube root of unity with (beta x, y) = -[x^2](x, y) on G1; 30-bit Montgomery form")
+        emit("endo_beta30", beta)
+        # G2: psi = twist o Frobenius o untwist on the M-type twist, (conj(x) cx, conj(y) cy), acts as x
+        cx, cy = fq2_inv(fq2_pow(xi, (q - 1) // 3, q), q), fq2_inv(fq2_pow(xi, (q - 1) // 2, q), q)
+        scalar = x % r
+    else:
+        # G1 has cofactor 1.  G2: psi on the D-type twist is pairing.hpp's frob_twist(q, 1) and acts as q = 6x^2 mod r
+        assert q + 1 - (6 * x * x + 1) == r
+        cx, cy = fq2_pow(xi, (q - 1) // 3, q), fq2_pow(xi, (q - 1) // 2, q)
+        scalar = 6 * x * x
+        assert scalar.bit_length() == 127
+        o.append("    static constexpr uint64_t G2_ENDO_LO = 0x%016xull, G2_ENDO_HI = 0x%016xull;  // 6x^2, psi's eigenvalue on G2"
+                 % (scalar & (2 ** 64 - 1), scalar >> 64))
+    assert (fq2_mul(conj(g2[0]), cx, q), fq2_mul(conj(g2[1]), cy, q)) == ec_mul(g2, scalar, q)
+    if c["xi"] == 1:
+        o.append("    // psi(x, y) = (conj(x) psi[0..1], conj(y) psi[2..3]) = [x](x, y) on G2: xi^(-(q-1)/3), xi^(-(q-1)/2)")
+        emit("psi30", [cx[0], cx[1], cy[0], cy[1]])
+    return o
+
+
 def pairing_consts(c):
     """lines of the Consts struct that pairing.hpp reads"""
     q, xi, x = c["q"], (c["xi"], 1), c["x"]
@@ -221,6 +302,7 @@ def main():
             o.append("        return t[i];")
             o.append("    }")
         o.extend(pairing_consts(c))
+        o.extend(subgroup_consts(c))
         o.append("};")
     o.append("}  // namespace g16")
     with open(os.path.join(here, "params_gen.hpp"), "w") as f:

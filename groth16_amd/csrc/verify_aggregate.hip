@@ -12,6 +12,8 @@
 //   verify_agg_reduce_kernel   the same wave reduction over 64 workgroup results at a time, until one pair is left.
 //   verify_agg_scalar_kernel   s and the t_j in Fr: a grid column per j, partial sums per workgroup in LDS;
 //   verify_agg_scalar_reduce_kernel  adds the partial sums.
+//   (g16_verify_aggregate_checked runs the membership kernels of verify_subgroup.hip first, over the same uploaded proofs and on
+//   the same stream: verdict 3 when a point is on its curve but outside its prime-order subgroup)
 //   agg_tail (host)            once per call, on the host templates (a lone GPU lane runs this chain about ten times slower than
 //                              one host thread): S_IC, the two pairs with -gamma and -delta, finish_loop, ONE final
 //                              exponentiation, and e(alpha, beta)^s as a cyclotomic power of the stored GT value -- chosen over a
@@ -29,13 +31,6 @@ namespace g16 {
 constexpr int AGG_MAX_PER_LANE = 4;   // proofs that may share a lane's accumulator
 constexpr int AGG_SCALAR_BLOCK = 256;
 constexpr int AGG_SCALAR_GRID = 64;   // workgroups per column of the scalar stage (at most)
-
-template <class T>
-G16_HD T ld_any(const uint64_t* p) {   // caller memory on the host, 8-byte aligned words on the device
-    T t;
-    __builtin_memcpy(&t, p, sizeof(T));
-    return t;
-}
 
 // The per-proof stage for cnt <= AGG_MAX_PER_LANE proofs: f = prod ML'(r_i A_i, B_i) (the loop value before finish_loop),
 // sc = sum r_i C_i.  false: a point is off its curve (f and sc are then not used).
@@ -319,22 +314,7 @@ struct AggPartial {   // what one device hands back
     XYZZ<typename Pairing<C>::F> sc;
     std::vector<typename C::Fr> st;
     int off_curve = 0;
-};
-
-struct DevBufs {
-    std::vector<void*> p;
-    template <class T>
-    int get(T** out, size_t count) {
-        void* q = nullptr;
-        G16_HIP_TRY(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-        p.push_back(q);
-        *out = static_cast<T*>(q);
-        return G16_OK;
-    }
-    void release() {
-        for (void* q : p) (void)hipFree(q);
-        p.clear();
-    }
+    int off_subgroup = 0;   // the membership stage's summary (checked calls): bit 0 outside a subgroup, bit 1 off a curve
 };
 
 // Proofs per lane.  Sharing an accumulator saves a lane work but lengthens its chain, so it pays only while every SIMD keeps its two
@@ -349,7 +329,7 @@ inline int agg_per_lane(int device, uint64_t n) {
 
 template <class C>
 int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uint64_t* inputs, uint64_t num_public, const uint64_t* coeffs,
-                    uint64_t n, AggPartial<C>* out, DevBufs* bufs) {
+                    uint64_t n, bool check, AggPartial<C>* out, DevBufs* bufs) {
     typedef Pairing<C> PP;
     typedef XYZZ<typename PP::F> G1X;
     typedef typename C::Fr Fr;
@@ -379,6 +359,16 @@ int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uin
     G16_HIP_TRY(hipMemcpyAsync(d_coeffs, coeffs, n * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     if (num_public) G16_HIP_TRY(hipMemcpyAsync(d_inputs, inputs, n * num_public * 4 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     G16_HIP_TRY(hipMemsetAsync(d_off, 0, sizeof(int), s));
+    if (check) {   // the membership tests over the copy of the proofs the Miller stage is about to read
+        uint8_t *d_pt, *d_flags;
+        int* d_sub;
+        G16_TRY(bufs->get(&d_pt, 3 * n));
+        G16_TRY(bufs->get(&d_flags, n));
+        G16_TRY(bufs->get(&d_sub, 1));
+        G16_HIP_TRY(hipMemsetAsync(d_sub, 0, sizeof(int), s));
+        G16_TRY(subgroup_enqueue_proofs(s, C::CURVE_ID, d_proofs, n, d_pt, d_flags, d_sub));
+        G16_HIP_TRY(hipMemcpyAsync(&out->off_subgroup, d_sub, sizeof(int), hipMemcpyDeviceToHost, s));
+    }
     verify_agg_scalar_kernel<C><<<dim3(sgrid, (unsigned)cols), AGG_SCALAR_BLOCK, 0, s>>>(d_coeffs, d_inputs, num_public, n, d_part);
     G16_LAUNCH_CHECK();
     verify_agg_scalar_reduce_kernel<C><<<(unsigned)cols, VERIFY_BLOCK, 0, s>>>(d_part, sgrid, cols, d_st);
@@ -401,7 +391,7 @@ int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uin
 
 template <class C>
 int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* inputs, uint64_t num_public,
-                  const uint64_t* coeffs, uint8_t* verdict) {
+                  const uint64_t* coeffs, bool check, uint8_t* verdict) {
     typedef Pairing<C> PP;
     constexpr int L = C::Fq::N / 2;
     std::vector<uint64_t> own;
@@ -422,7 +412,7 @@ int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint
         if (hi == lo) continue;
         used[k] = 1;
         rc = aggregate_chunk<C>(streams[k], devs[k], proofs + lo * 8 * L, inputs ? inputs + lo * num_public * 4 : nullptr, num_public,
-                                r + 2 * lo, hi - lo, &part[k], &bufs[k]);
+                                r + 2 * lo, hi - lo, check, &part[k], &bufs[k]);
     }
     for (uint64_t k = 0; k < nd; ++k) {
         (void)hipSetDevice(devs[k]);
@@ -433,15 +423,17 @@ int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint
     typename PP::F12 f = PP::F12::one();
     XYZZ<typename PP::F> sc = XYZZ<typename PP::F>::identity();
     std::vector<typename C::Fr> st(num_public + 1, C::Fr::zero());
-    int off_curve = 0;
+    int off_curve = 0, off_subgroup = 0;
     for (uint64_t k = 0; k < nd; ++k) {
         if (!used[k]) continue;
         f = f * part[k].f;
         sc.add(part[k].sc);
         for (uint64_t j = 0; j <= num_public; ++j) st[j] = st[j] + part[k].st[j];
         off_curve |= part[k].off_curve;
+        off_subgroup |= part[k].off_subgroup;
     }
-    if (off_curve) { *verdict = 2; return G16_OK; }
+    if (off_curve || (off_subgroup & 2)) { *verdict = 2; return G16_OK; }
+    if (off_subgroup) { *verdict = 3; return G16_OK; }
     return agg_tail<C>(f, sc, st.data(), num_public, pvk->gamma_g2.data(), pvk->delta_g2.data(), pvk->gamma_abc_g1.data(), PP::load_gt(pvk->ab),
                        verdict, nullptr, nullptr);
 }
@@ -455,7 +447,15 @@ int g16_verify_aggregate(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proof
     if (!ctx || !pvk || !verdict || (n && !proofs) || (n && num_public && !public_inputs)) return G16_ERR_BAD_ARG;
     if (num_public + 1 != pvk->n_gamma_abc) return G16_ERR_MALFORMED_VK;
     if (!n) { *verdict = 1; return G16_OK; }
-    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, n, public_inputs, num_public, coeffs, verdict)));
+    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, n, public_inputs, num_public, coeffs, false, verdict)));
+}
+
+int g16_verify_aggregate_checked(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
+                                 uint64_t num_public, const uint64_t* coeffs, uint8_t* verdict) {
+    if (!ctx || !pvk || !verdict || (n && !proofs) || (n && num_public && !public_inputs)) return G16_ERR_BAD_ARG;
+    if (num_public + 1 != pvk->n_gamma_abc) return G16_ERR_MALFORMED_VK;
+    if (!n) { *verdict = 1; return G16_OK; }
+    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, n, public_inputs, num_public, coeffs, true, verdict)));
 }
 
 int g16_host_verify_aggregate(int curve, const g16_vk_view* vk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,

@@ -3,11 +3,18 @@
 #pragma once
 #include "internal.hpp"
 #include "pairing.hpp"
+#include <algorithm>
 #include <new>
 #include <vector>
 
 namespace g16 {
 int ctx_devices(const g16_ctx* ctx, int* curve, std::vector<int>& devs, std::vector<hipStream_t>& streams);   // api.hip
+
+// verify_subgroup.hip: enqueue the membership tests over n proofs (A | B | C) resident on the current device.  d_point_flags: 3 n
+// bytes of work space, d_flags: one byte per proof (1 / 0 / 2 as g16_check_proof_subgroups), *d_summary (may be null, zeroed by the
+// caller) |= 1 if a proof is outside a subgroup, 2 if a point is off its curve.
+int subgroup_enqueue_proofs(hipStream_t s, int curve, const uint64_t* d_proofs, uint64_t n, uint8_t* d_point_flags, uint8_t* d_flags,
+                            int* d_summary);
 
 constexpr int VERIFY_BLOCK = 64;
 
@@ -18,6 +25,30 @@ T ld(const void* p) {
     memcpy(&t, p, sizeof(T));
     return t;
 }
+template <class T>
+G16_HD T ld_any(const uint64_t* p) {   // caller memory on the host, 8-byte aligned words on the device
+    T t;
+    __builtin_memcpy(&t, p, sizeof(T));
+    return t;
+}
+
+// device buffers of one call, freed together
+struct DevBufs {
+    std::vector<void*> p;
+    template <class T>
+    int get(T** out, size_t count) {
+        void* q = nullptr;
+        G16_HIP_TRY(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+        p.push_back(q);
+        *out = static_cast<T*>(q);
+        return G16_OK;
+    }
+    void release() {
+        for (void* q : p) (void)hipFree(q);
+        p.clear();
+    }
+};
+
 constexpr int WINDOWS = 64, DIGITS = 15;   // 4-bit windows of a 256-bit scalar; table entry [base][window][digit - 1]
 
 template <class C>

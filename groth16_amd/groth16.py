@@ -509,22 +509,49 @@ class Groth16:
         from .verifier import verify_batch
         return verify_batch(self._ctx, pvk, proofs, public_inputs_list)
 
-    def verify_aggregate_verdict(self, pvk, proofs, public_inputs_list, coeffs=None) -> int:
+    def verify_aggregate_verdict(self, pvk, proofs, public_inputs_list, coeffs=None, check_subgroups: bool = False) -> int:
         """g16_verify_aggregate: the whole batch in one randomised equation with one final exponentiation.  1 every proof is
         accepted, 0 at least one is not, 2 a point is off its curve.  coeffs: one non-zero 128-bit integer per proof, fixed after
-        the proofs; None draws them from the operating system.  Sound for proofs whose points are in the prime-order subgroups
-        (proof_from_bytes(validate=2) checks that)."""
+        the proofs; None draws them from the operating system.  Sound for proofs whose points are in the prime-order subgroups:
+        check_subgroups=True (g16_verify_aggregate_checked) tests that on the GPU before the equation and is the call whose
+        contract needs no such proviso -- it answers 3 when every point is on its curve but one is outside its subgroup (2 wins
+        over 3, 3 over 0 / 1).  With the default False the caller vouches for the points (proof_from_bytes(validate=2) checks
+        them on the host)."""
         from .verifier import verify_aggregate
-        return verify_aggregate(self._ctx, pvk, proofs, public_inputs_list, coeffs)
+        return verify_aggregate(self._ctx, pvk, proofs, public_inputs_list, coeffs, check_subgroups)
 
-    def verify_proofs_aggregate(self, pvk, proofs, public_inputs_list, coeffs=None) -> bool:
-        return self.verify_aggregate_verdict(pvk, proofs, public_inputs_list, coeffs) == 1
+    def verify_proofs_aggregate(self, pvk, proofs, public_inputs_list, coeffs=None, check_subgroups: bool = False) -> bool:
+        return self.verify_aggregate_verdict(pvk, proofs, public_inputs_list, coeffs, check_subgroups) == 1
 
-    def verify_proofs_aggregate_or_each(self, pvk, proofs, public_inputs_list) -> np.ndarray:
-        """a bool per proof: the aggregate check first, and only if it fails verify_proofs to name the culprits"""
-        if self.verify_proofs_aggregate(pvk, proofs, public_inputs_list):
-            return np.ones(len(public_inputs_list), dtype=bool)
-        return self.verify_proofs(pvk, proofs, public_inputs_list)
+    def verify_proofs_aggregate_or_each(self, pvk, proofs, public_inputs_list, check_subgroups: bool = False) -> np.ndarray:
+        """a bool per proof: the aggregate check first, and only if it fails verify_proofs to name the culprits.  With
+        check_subgroups=True a proof with a point outside its subgroup (or off its curve) is answered False and the per-proof
+        verifier runs on the rest"""
+        verdict = self.verify_aggregate_verdict(pvk, proofs, public_inputs_list, check_subgroups=check_subgroups)
+        n = len(public_inputs_list)
+        if verdict == 1:
+            return np.ones(n, dtype=bool)
+        if not check_subgroups:
+            return self.verify_proofs(pvk, proofs, public_inputs_list)
+        from .verifier import _flat_proofs
+        flat = _flat_proofs(proofs, self.curve)
+        keep = np.flatnonzero(self.check_proof_subgroups(flat) == 1)
+        out = np.zeros(n, dtype=bool)
+        if keep.size:
+            out[keep] = self.verify_proofs(pvk, flat[keep], [public_inputs_list[i] for i in keep])
+        return out
+
+    def check_subgroups(self, points, g2: bool = False) -> np.ndarray:
+        """prime-order subgroup membership of affine points on the GPU (g16_check_subgroups): a uint8 per point -- 1 in the
+        subgroup, 0 on the curve but outside it, 2 off the curve"""
+        from .verifier import check_subgroups
+        return check_subgroups(self._ctx, points, g2)
+
+    def check_proof_subgroups(self, proofs) -> np.ndarray:
+        """the same per proof (g16_check_proof_subgroups): 2 if A, B or C is off its curve, otherwise 0 if one is outside its
+        subgroup, otherwise 1"""
+        from .verifier import check_proof_subgroups
+        return check_proof_subgroups(self._ctx, proofs)
 
     def pairing(self, g1s: np.ndarray, g2s: np.ndarray) -> np.ndarray:
         """prod e(g1s[i], g2s[i]) on the GPU (GT as arkworks' 12 Fq limbs)"""

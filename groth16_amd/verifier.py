@@ -135,17 +135,46 @@ def _flat_coeffs(coeffs, n):
     return np.ascontiguousarray(out)
 
 
-def verify_aggregate(ctx, pvk: PreparedVerifyingKey, proofs, public_inputs_list, coeffs=None) -> int:
-    """g16_verify_aggregate's verdict: 1 every proof holds, 0 the aggregate equation fails, 2 a point is off its curve"""
+def verify_aggregate(ctx, pvk: PreparedVerifyingKey, proofs, public_inputs_list, coeffs=None, check_subgroups: bool = False) -> int:
+    """g16_verify_aggregate's verdict: 1 every proof holds, 0 the aggregate equation fails, 2 a point is off its curve.
+    check_subgroups=True goes through g16_verify_aggregate_checked, which adds 3: a point is on its curve but outside its
+    prime-order subgroup"""
     flat = _flat_proofs(proofs, pvk.curve)
     n = flat.shape[0]
     x, num_public = _flat_inputs(public_inputs_list, n, pvk.vk.num_public)
     r = _flat_coeffs(coeffs, n)
     v = np.zeros(1, dtype=np.uint8)
     lb = lib()
-    lb.check(lb.c.g16_verify_aggregate(ctx.handle, pvk.handle, ptr64(flat.reshape(-1)) if n else None, n, ptr64(x) if x.size else None,
-                                       num_public, ptr64(r.reshape(-1)) if r is not None and n else None, v.ctypes.data_as(C.c_void_p)))
+    fn = lb.c.g16_verify_aggregate_checked if check_subgroups else lb.c.g16_verify_aggregate
+    lb.check(fn(ctx.handle, pvk.handle, ptr64(flat.reshape(-1)) if n else None, n, ptr64(x) if x.size else None, num_public,
+                ptr64(r.reshape(-1)) if r is not None and n else None, v.ctypes.data_as(C.c_void_p)))
     return int(v[0])
+
+
+def _flat_points(points, curve, g2) -> np.ndarray:
+    return _c(points).reshape(-1, (4 if g2 else 2) * FQ_LIMBS[curve])
+
+
+def check_subgroups(ctx, points, g2: bool = False) -> np.ndarray:
+    """g16_check_subgroups: a byte per affine point (G1, or G2 with g2=True) -- 1 in the prime-order subgroup, 0 on the curve
+    but outside it, 2 off the curve"""
+    flat = _flat_points(points, ctx.curve, g2)
+    flags = np.zeros(flat.shape[0], dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_check_subgroups(ctx.handle, int(bool(g2)), ptr64(flat.reshape(-1)) if flat.size else None, flat.shape[0],
+                                      flags.ctypes.data_as(C.c_void_p)))
+    return flags
+
+
+def check_proof_subgroups(ctx, proofs) -> np.ndarray:
+    """g16_check_proof_subgroups: a byte per proof -- 2 if A, B or C is off its curve, otherwise 0 if one of them is outside its
+    subgroup, otherwise 1"""
+    flat = _flat_proofs(proofs, ctx.curve)
+    flags = np.zeros(flat.shape[0], dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_check_proof_subgroups(ctx.handle, ptr64(flat.reshape(-1)) if flat.size else None, flat.shape[0],
+                                            flags.ctypes.data_as(C.c_void_p)))
+    return flags
 
 
 def _host_aggregate_args(curve, vk, proofs, public_inputs_list, coeffs):
@@ -201,6 +230,16 @@ def verify_proof_host(curve: str, vk, proof, public_inputs) -> bool:
     """verify_proof (verifier.rs:68-76) on the CPU through g16_host_verify; raises MalformedVerifyingKey for a wrong input count.
     A proof with a point off its curve is rejected (False)."""
     return host_verdict(curve, vk, proof, public_inputs) == 1
+
+
+def check_subgroups_host(curve: str, points, g2: bool = False) -> np.ndarray:
+    """check_subgroups on the CPU through g16_host_check_subgroups (the same C++ templates, no GPU): 1 / 0 / 2 per point"""
+    flat = _flat_points(points, curve, g2)
+    flags = np.zeros(flat.shape[0], dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_host_check_subgroups(CURVE_ID[curve], int(bool(g2)), ptr64(flat.reshape(-1)) if flat.size else None, flat.shape[0],
+                                           flags.ctypes.data_as(C.c_void_p)))
+    return flags
 
 
 def host_verdict(curve: str, vk, proof, public_inputs) -> int:

@@ -446,7 +446,8 @@ int g16_host_verify(int curve, const g16_vk_view* vk, const uint64_t* proof, con
  * proofs.  coeffs == NULL: the library draws them from the operating system's generator (getrandom(2)), redrawing a zero.
  * Contract: a batch with an invalid proof is accepted with probability about 2^-127 over the coefficients, PROVIDED the points of
  * every proof lie in the prime-order subgroups -- what the reference guarantees by deserialising with Validate::Yes and what
- * g16_deserialize_points with validation does here.  Like verify_proof itself, this function checks on-curve only.
+ * g16_deserialize_points with validation does here.  Like verify_proof itself, this function checks on-curve only;
+ * g16_verify_aggregate_checked below runs the membership tests on the GPU first and needs no such proviso.
  * G16_ERR_MALFORMED_VK as g16_verify_batch.  A multi-device ctx cuts the batch into one chunk per device; the once-per-batch tail
  * (two prepared pairs, the final exponentiation, the GT power) runs on the calling host thread. */
 int g16_verify_aggregate(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
@@ -458,6 +459,26 @@ int g16_host_verify_aggregate(int curve, const g16_vk_view* vk, const uint64_t* 
  * is off its curve, G16_ERR_UNEXPECTED_IDENTITY if the Miller product is 0 */
 int g16_host_verify_aggregate_gt(int curve, const g16_vk_view* vk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
                                  uint64_t num_public, const uint64_t* coeffs, uint64_t* lhs_fq12, uint64_t* rhs_fq12);
+
+/* ---- prime-order subgroup membership on the GPU (the point checks of Validate::Yes, without the byte formats) ----
+ * Endomorphism tests with public constants: BLS12-381 G1 phi(P) = -[x^2]P, BLS12-381 G2 psi(Q) = [x]Q,
+ * BN254 G2 psi(Q) = [6x^2]Q; BN254 G1 has cofactor 1, so on-curve is membership.  A flag byte is 1: in the subgroup (the
+ * identity included), 0: on the curve but outside the subgroup, 2: off the curve (as in every verifier verdict).
+ * points: n packed affine points in host memory (g2 = 0: G1, 1: G2), flags: n bytes.  What Validate::Yes checks of a point
+ * once its bytes are decoded; g16_deserialize_points(validate = 2) is the host path for byte input.  n = 0 is G16_OK.  A
+ * multi-device ctx cuts the array into one chunk per device; flags stay in input order. */
+int g16_check_subgroups(g16_ctx* ctx, int g2, const uint64_t* points, uint64_t n, uint8_t* flags);
+/* proofs: n x (A | B | C) as for g16_verify_batch, uploaded once; flags[i]: 2 if any of A, B, C is off its curve, otherwise 0 if
+ * any is outside its subgroup, otherwise 1 -- Validate::Yes for a whole Proof<E> (data_structures.rs:8-16). */
+int g16_check_proof_subgroups(g16_ctx* ctx, const uint64_t* proofs, uint64_t n, uint8_t* flags);
+/* g16_verify_aggregate with the membership tests run first, on the same uploaded copy of the proofs and the same stream: the
+ * check Validate::Yes makes when the reference deserialises a proof, so the 2^-127 contract holds with NO proviso on the points.
+ * *verdict as g16_verify_aggregate, plus 3: every point is on its curve but some point is outside its prime-order subgroup
+ * (the equation's outcome is then not reported; g16_check_proof_subgroups names the proofs).  2 wins over 3, 3 over 0 / 1. */
+int g16_verify_aggregate_checked(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
+                                 uint64_t num_public, const uint64_t* coeffs, uint8_t* verdict);
+/* g16_check_subgroups' templates on the CPU (no GPU needed); the point checks of Validate::Yes */
+int g16_host_check_subgroups(int curve, int g2, const uint64_t* points, uint64_t n, uint8_t* flags);
 
 const char* g16_strerror(int status);
 /* text of the last HIP error seen on this thread ("" if none) */

@@ -4,6 +4,7 @@
     python tools/verify_bench.py --curve bls12_381 --n 1024 [--reps 3]     one JSON line per call
     python tools/verify_bench.py --curve bn254 --host [--reps 20]
     python tools/verify_bench.py --curve bls12_381 --n 65536 --aggregate [--reps 5]
+    python tools/verify_bench.py --curve bls12_381 --n 65536 --subgroup [--reps 5]
 
 --n: proofs per g16_verify_batch call (copies of rerandomised honest proofs of a small SYN circuit, one public input); the line
 reports the g16_pvk_load time, the best of --reps timed calls after one warm-up call (host clock around the call, which ends in a
@@ -11,7 +12,10 @@ device synchronise; includes the host->device copy of the proofs), and proofs/s.
 g16_host_verify -- this library's host C++ on the same pairing templates, NOT ark-groth16.  --aggregate: g16_verify_aggregate (one
 randomised equation per batch, coefficients drawn by the library) on the same batch, clock and warm-up, and in the same process
 g16_verify_batch for the same n; both get the public inputs as one (n, l, 4) array, so neither figure carries a Python loop over the
-proofs.  `spread` is (slowest - fastest) / fastest of the --reps timed calls.  Run each step under its own time limit."""
+proofs.  --subgroup: on one batch and in one process g16_verify_aggregate, g16_verify_aggregate_checked,
+g16_check_proof_subgroups alone, and the host path the last one replaces -- g16_deserialize_points(validate=2) over the same 3n
+points (uncompressed bytes, so no square root is in the figure) on the CPUs the process may use; the line reports the ratios
+checked / aggregate and host / GPU check.  `spread` is (slowest - fastest) / fastest of the --reps timed calls.  Run each step under its own time limit."""
 import argparse
 import json
 import os
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--host", action="store_true")
     ap.add_argument("--aggregate", action="store_true")
+    ap.add_argument("--subgroup", action="store_true")
     a = ap.parse_args()
     vk, proofs, x, cp = oracle_case(a.curve)
     L = cp.fq_limbs64
@@ -50,6 +55,8 @@ def main():
                           for _ in range(7)]
     flat = np.ascontiguousarray(np.stack([base[i % len(base)] for i in range(a.n)]))
     xs = [x] * a.n
+    if a.subgroup:
+        return subgroup(a, vk, flat, np.ascontiguousarray(np.broadcast_to(x.reshape(1, -1, 4), (a.n,) + x.reshape(-1, 4).shape)), L)
     if a.aggregate:
         return aggregate(a, vk, flat, np.ascontiguousarray(np.broadcast_to(x.reshape(1, -1, 4), (a.n,) + x.reshape(-1, 4).shape)))
     with g.Groth16(a.curve, device=0) as prover:
@@ -89,6 +96,31 @@ def aggregate(a, vk, flat, xs):
     print(json.dumps(dict(curve=a.curve, n=a.n, mode="aggregate", batch_ms=round(agg * 1e3, 3), proofs_per_s=round(a.n / agg, 1),
                           spread=round(agg_spread, 4), per_proof_batch_ms=round(each * 1e3, 3), per_proof_proofs_per_s=round(a.n / each, 1),
                           per_proof_spread=round(each_spread, 4), speedup=round(each / agg, 3), reps=a.reps)))
+
+
+def subgroup(a, vk, flat, xs, L):
+    from groth16_amd.serialize import deserialize_points, serialize_points
+    g1 = np.ascontiguousarray(np.concatenate([flat[:, : 2 * L], flat[:, 6 * L:]]))
+    g2 = np.ascontiguousarray(flat[:, 2 * L: 6 * L])
+    b1, b2 = serialize_points(a.curve, g1, False, compressed=False), serialize_points(a.curve, g2, True, compressed=False)
+
+    def host():
+        deserialize_points(a.curve, b1, 2 * a.n, False, compressed=False, validate=2)
+        deserialize_points(a.curve, b2, a.n, True, compressed=False, validate=2)
+
+    with g.Groth16(a.curve, device=0) as prover:
+        pvk = prover.prepare_verifying_key(vk)
+        assert prover.verify_aggregate_verdict(pvk, flat, xs, check_subgroups=True) == 1, "the benchmark batch was rejected"
+        assert (prover.check_proof_subgroups(flat) == 1).all()
+        agg, agg_spread = timed(lambda: prover.verify_aggregate_verdict(pvk, flat, xs), a.reps)
+        chk, chk_spread = timed(lambda: prover.verify_aggregate_verdict(pvk, flat, xs, check_subgroups=True), a.reps)
+        sub, sub_spread = timed(lambda: prover.check_proof_subgroups(flat), a.reps)
+        pvk.close()
+    hst, hst_spread = timed(host, a.reps)
+    print(json.dumps(dict(curve=a.curve, n=a.n, mode="subgroup", aggregate_ms=round(agg * 1e3, 3), aggregate_spread=round(agg_spread, 4),
+                          checked_ms=round(chk * 1e3, 3), checked_spread=round(chk_spread, 4), check_only_ms=round(sub * 1e3, 3),
+                          check_only_spread=round(sub_spread, 4), host_validate_ms=round(hst * 1e3, 3), host_spread=round(hst_spread, 4),
+                          checked_over_aggregate=round(chk / agg, 3), host_over_gpu_check=round(hst / sub, 1), reps=a.reps)))
 
 
 if __name__ == "__main__":
