@@ -23,7 +23,7 @@ from .binding import (G16Error, Lib, PolynomialDegreeTooLarge, SynthesisError, U
 from .groth16 import (ConstraintMatrices, Groth16, LibsnarkReduction, PipelinedProver, Proof, ProvingKey, ShardedProver, finalize_host,  # noqa: F401
                       rerandomize_proof, shard_ranges)
 from .binding import MalformedVerifyingKey  # noqa: F401
-from .verifier import (PreparedVerifyingKey, VerifyingKey, check_subgroups_host, host_pairing, verify_proof_host,  # noqa: F401
+from .verifier import (PreparedVerifyingKey, VerifyingKey, check_subgroups_host, decompress_points_host, host_pairing, verify_proof_host,  # noqa: F401
                        verify_proofs_aggregate_host)
 from .r1cs import AssignmentMissing, ConstraintSynthesizer, ConstraintSystem, LinearCombination, Variable, lc  # noqa: F401
 
@@ -31,4 +31,5 @@ __all__ = [
     "Groth16", "LibsnarkReduction", "ConstraintMatrices", "ProvingKey", "Proof", "ShardedProver", "PipelinedProver", "G16Error", "SynthesisError",
     "PolynomialDegreeTooLarge", "UnexpectedIdentity", "lib", "ConstraintSystem", "ConstraintSynthesizer", "Variable", "LinearCombination",
     "lc", "AssignmentMissing", "VerifyingKey", "PreparedVerifyingKey", "MalformedVerifyingKey", "verify_proof_host", "verify_proofs_aggregate_host", "check_subgroups_host", "host_pairing",
+    "decompress_points_host",
 ]

@@ -125,6 +125,7 @@ EXPORTS = [
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
     "g16_dev_fp30_op", "g16_host_fp30_op",
     "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
+    "g16_decompress_points", "g16_decompress_proofs", "g16_host_decompress_points", "g16_verify_aggregate_bytes",
 ]
 
 
@@ -242,6 +243,10 @@ class Lib:
         c.g16_check_subgroups.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, C.c_void_p]
         c.g16_check_proof_subgroups.argtypes = [C.c_void_p, u64p, C.c_uint64, C.c_void_p]
         c.g16_host_check_subgroups.argtypes = [C.c_int, C.c_int, u64p, C.c_uint64, C.c_void_p]
+        c.g16_decompress_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, u64p, C.c_void_p]
+        c.g16_decompress_proofs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p]
+        c.g16_host_decompress_points.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_uint64, u64p, C.c_void_p]
+        c.g16_verify_aggregate_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_void_p]
         c.g16_dev_fp30_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_fp30_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
 

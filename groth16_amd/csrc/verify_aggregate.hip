@@ -315,6 +315,7 @@ struct AggPartial {   // what one device hands back
     std::vector<typename C::Fr> st;
     int off_curve = 0;
     int off_subgroup = 0;   // the membership stage's summary (checked calls): bit 0 outside a subgroup, bit 1 off a curve
+    int undecodable = 0;    // the decoding stage's summary (byte input): bit 0 some proof's bytes do not decode
 };
 
 // Proofs per lane.  Sharing an accumulator saves a lane work but lengthens its chain, so it pays only while every SIMD keeps its two
@@ -327,9 +328,32 @@ inline int agg_per_lane(int device, uint64_t n) {
     return (int)std::min<uint64_t>(std::max<uint64_t>(n / resident, 1), AGG_MAX_PER_LANE);
 }
 
+// The byte input of g16_verify_aggregate_bytes: uploads n compressed proofs (a third of the affine form), decodes them into a device
+// buffer on the same stream and hands that buffer to aggregate_chunk; an undecodable point is the identity there.
 template <class C>
-int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uint64_t* inputs, uint64_t num_public, const uint64_t* coeffs,
-                    uint64_t n, bool check, AggPartial<C>* out, DevBufs* bufs) {
+int decode_chunk(hipStream_t s, int device, const uint8_t* bytes, uint64_t n, AggPartial<C>* out, DevBufs* bufs, uint64_t** d_resident) {
+    constexpr int L = C::Fq::N / 2;
+    constexpr uint64_t PROOF_BYTES = 4 * ((C::Fq::Params::BITS + 7) / 8);
+    G16_HIP_TRY(hipSetDevice(device));
+    uint8_t *d_bytes, *d_pt, *d_status;
+    int* d_bad;
+    G16_TRY(bufs->get(&d_bytes, n * PROOF_BYTES));
+    G16_TRY(bufs->get(d_resident, n * 8 * L));
+    G16_TRY(bufs->get(&d_pt, 3 * n));
+    G16_TRY(bufs->get(&d_status, n));
+    G16_TRY(bufs->get(&d_bad, 1));
+    G16_HIP_TRY(hipMemcpyAsync(d_bytes, bytes, n * PROOF_BYTES, hipMemcpyHostToDevice, s));
+    G16_HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    G16_TRY(decompress_enqueue_proofs(s, C::CURVE_ID, d_bytes, n, *d_resident, d_pt, d_status, d_bad));
+    G16_HIP_TRY(hipMemcpyAsync(&out->undecodable, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    return G16_OK;
+}
+
+// proofs: n x (A | B | C) affine in host memory, uploaded here -- or d_resident: the same already on this device (written by earlier
+// work on s)
+template <class C>
+int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uint64_t* d_resident, const uint64_t* inputs, uint64_t num_public,
+                    const uint64_t* coeffs, uint64_t n, bool check, AggPartial<C>* out, DevBufs* bufs) {
     typedef Pairing<C> PP;
     typedef XYZZ<typename PP::F> G1X;
     typedef typename C::Fr Fr;
@@ -340,12 +364,16 @@ int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uin
     const uint64_t blocks = (lanes + VERIFY_BLOCK - 1) / VERIFY_BLOCK, blocks2 = (blocks + VERIFY_BLOCK - 1) / VERIFY_BLOCK;
     const unsigned sgrid = (unsigned)std::min<uint64_t>((n + AGG_SCALAR_BLOCK - 1) / AGG_SCALAR_BLOCK, AGG_SCALAR_GRID);
     const uint64_t cols = num_public + 1;
-    uint64_t *d_proofs, *d_coeffs, *d_inputs;
+    const uint64_t* d_proofs = d_resident;
+    uint64_t *d_upload, *d_coeffs, *d_inputs;
     typename PP::F12* d_f[2];
     G1X* d_c[2];
     Fr *d_part, *d_st;
     int* d_off;
-    G16_TRY(bufs->get(&d_proofs, n * 8 * L));
+    if (!d_resident) {
+        G16_TRY(bufs->get(&d_upload, n * 8 * L));
+        d_proofs = d_upload;
+    }
     G16_TRY(bufs->get(&d_coeffs, n * 2));
     G16_TRY(bufs->get(&d_inputs, n * num_public * 4));
     G16_TRY(bufs->get(&d_f[0], blocks));
@@ -355,7 +383,7 @@ int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uin
     G16_TRY(bufs->get(&d_part, sgrid * cols));
     G16_TRY(bufs->get(&d_st, cols));
     G16_TRY(bufs->get(&d_off, 1));
-    G16_HIP_TRY(hipMemcpyAsync(d_proofs, proofs, n * 8 * L * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    if (!d_resident) G16_HIP_TRY(hipMemcpyAsync(d_upload, proofs, n * 8 * L * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     G16_HIP_TRY(hipMemcpyAsync(d_coeffs, coeffs, n * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     if (num_public) G16_HIP_TRY(hipMemcpyAsync(d_inputs, inputs, n * num_public * 4 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     G16_HIP_TRY(hipMemsetAsync(d_off, 0, sizeof(int), s));
@@ -389,11 +417,13 @@ int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uin
     return G16_OK;
 }
 
+// proofs (affine) or bytes (compressed, decoded on the device; check is then set)
 template <class C>
-int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* inputs, uint64_t num_public,
-                  const uint64_t* coeffs, bool check, uint8_t* verdict) {
+int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, const uint8_t* bytes, uint64_t n, const uint64_t* inputs,
+                  uint64_t num_public, const uint64_t* coeffs, bool check, uint8_t* verdict) {
     typedef Pairing<C> PP;
     constexpr int L = C::Fq::N / 2;
+    constexpr uint64_t PROOF_BYTES = 4 * ((C::Fq::Params::BITS + 7) / 8);
     std::vector<uint64_t> own;
     const uint64_t* r = nullptr;
     G16_TRY(agg_coeffs(coeffs, n, own, &r));
@@ -411,8 +441,11 @@ int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint
         const uint64_t lo = n * k / nd, hi = n * (k + 1) / nd;
         if (hi == lo) continue;
         used[k] = 1;
-        rc = aggregate_chunk<C>(streams[k], devs[k], proofs + lo * 8 * L, inputs ? inputs + lo * num_public * 4 : nullptr, num_public,
-                                r + 2 * lo, hi - lo, check, &part[k], &bufs[k]);
+        uint64_t* d_resident = nullptr;
+        if (bytes) rc = decode_chunk<C>(streams[k], devs[k], bytes + lo * PROOF_BYTES, hi - lo, &part[k], &bufs[k], &d_resident);
+        if (rc == G16_OK)
+            rc = aggregate_chunk<C>(streams[k], devs[k], bytes ? nullptr : proofs + lo * 8 * L, d_resident,
+                                    inputs ? inputs + lo * num_public * 4 : nullptr, num_public, r + 2 * lo, hi - lo, check, &part[k], &bufs[k]);
     }
     for (uint64_t k = 0; k < nd; ++k) {
         (void)hipSetDevice(devs[k]);
@@ -423,7 +456,7 @@ int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint
     typename PP::F12 f = PP::F12::one();
     XYZZ<typename PP::F> sc = XYZZ<typename PP::F>::identity();
     std::vector<typename C::Fr> st(num_public + 1, C::Fr::zero());
-    int off_curve = 0, off_subgroup = 0;
+    int off_curve = 0, off_subgroup = 0, undecodable = 0;
     for (uint64_t k = 0; k < nd; ++k) {
         if (!used[k]) continue;
         f = f * part[k].f;
@@ -431,11 +464,18 @@ int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint
         for (uint64_t j = 0; j <= num_public; ++j) st[j] = st[j] + part[k].st[j];
         off_curve |= part[k].off_curve;
         off_subgroup |= part[k].off_subgroup;
+        undecodable |= part[k].undecodable;
     }
+    if (undecodable) { *verdict = 4; return G16_OK; }
     if (off_curve || (off_subgroup & 2)) { *verdict = 2; return G16_OK; }
     if (off_subgroup) { *verdict = 3; return G16_OK; }
     return agg_tail<C>(f, sc, st.data(), num_public, pvk->gamma_g2.data(), pvk->delta_g2.data(), pvk->gamma_abc_g1.data(), PP::load_gt(pvk->ab),
                        verdict, nullptr, nullptr);
+}
+
+int aggregate_bytes(g16_ctx* ctx, const g16_pvk* pvk, const uint8_t* proof_bytes, uint64_t n, const uint64_t* inputs, uint64_t num_public,
+                    const uint64_t* coeffs, uint8_t* verdict) {
+    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, nullptr, proof_bytes, n, inputs, num_public, coeffs, true, verdict)));
 }
 
 }  // namespace g16
@@ -447,7 +487,7 @@ int g16_verify_aggregate(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proof
     if (!ctx || !pvk || !verdict || (n && !proofs) || (n && num_public && !public_inputs)) return G16_ERR_BAD_ARG;
     if (num_public + 1 != pvk->n_gamma_abc) return G16_ERR_MALFORMED_VK;
     if (!n) { *verdict = 1; return G16_OK; }
-    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, n, public_inputs, num_public, coeffs, false, verdict)));
+    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, nullptr, n, public_inputs, num_public, coeffs, false, verdict)));
 }
 
 int g16_verify_aggregate_checked(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
@@ -455,7 +495,7 @@ int g16_verify_aggregate_checked(g16_ctx* ctx, const g16_pvk* pvk, const uint64_
     if (!ctx || !pvk || !verdict || (n && !proofs) || (n && num_public && !public_inputs)) return G16_ERR_BAD_ARG;
     if (num_public + 1 != pvk->n_gamma_abc) return G16_ERR_MALFORMED_VK;
     if (!n) { *verdict = 1; return G16_OK; }
-    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, n, public_inputs, num_public, coeffs, true, verdict)));
+    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, nullptr, n, public_inputs, num_public, coeffs, true, verdict)));
 }
 
 int g16_host_verify_aggregate(int curve, const g16_vk_view* vk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,

@@ -16,6 +16,16 @@ int ctx_devices(const g16_ctx* ctx, int* curve, std::vector<int>& devs, std::vec
 int subgroup_enqueue_proofs(hipStream_t s, int curve, const uint64_t* d_proofs, uint64_t n, uint8_t* d_point_flags, uint8_t* d_flags,
                             int* d_summary);
 
+// verify_decompress.hip: enqueue the decoding of n compressed proofs (A | B | C bytes, resident on the current device) into d_proofs
+// (n x (A | B | C) affine; a point that does not decode is written as the identity).  d_point_status: 3 n bytes of work space,
+// d_status: one byte per proof (1 / 0 as g16_decompress_proofs), *d_summary (may be null, zeroed by the caller) |= 1 if a proof does
+// not decode.
+int decompress_enqueue_proofs(hipStream_t s, int curve, const uint8_t* d_bytes, uint64_t n, uint64_t* d_proofs, uint8_t* d_point_status,
+                              uint8_t* d_status, int* d_summary);
+// verify_aggregate.hip: g16_verify_aggregate_bytes behind its argument checks (n >= 1)
+int aggregate_bytes(g16_ctx* ctx, const g16_pvk* pvk, const uint8_t* proof_bytes, uint64_t n, const uint64_t* inputs, uint64_t num_public,
+                    const uint64_t* coeffs, uint8_t* verdict);
+
 constexpr int VERIFY_BLOCK = 64;
 
 // host reads of caller memory: the point / field structs are 16-byte aligned, a caller's u64 buffer need not be

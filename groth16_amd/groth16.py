@@ -547,6 +547,30 @@ class Groth16:
         from .verifier import check_subgroups
         return check_subgroups(self._ctx, points, g2)
 
+    def decompress_points(self, data, g2: bool = False):
+        """compressed points (bytes or a uint8 array; G2 with g2=True) decoded on the GPU (g16_decompress_points) by the rules of
+        deserialize_points(compressed=True, validate=0): (points, status), status 1 decoded / 0 an invalid encoding, whose point
+        is the identity.  ValueError for a length that is no multiple of the encoding size"""
+        from .verifier import decompress_points
+        return decompress_points(self._ctx, data, g2)
+
+    def decompress_proofs(self, data):
+        """compressed proofs A | B | C (proof_to_bytes(compressed=True), concatenated) decoded on the GPU (g16_decompress_proofs):
+        (flat_proofs, status) -- the array verify_proofs takes and a byte per proof, 1 iff its three points decode"""
+        from .verifier import decompress_proofs
+        return decompress_proofs(self._ctx, data)
+
+    def verify_aggregate_bytes_verdict(self, pvk, data, public_inputs_list, coeffs=None) -> int:
+        """bytes to verdict (g16_verify_aggregate_bytes): the compressed proofs are uploaded, decoded, membership-tested and put
+        through the aggregate equation on the GPU without returning to the host.  1 / 0 / 3 as
+        verify_aggregate_verdict(check_subgroups=True), 4: some proof's bytes do not decode (decompress_proofs names it; 4 wins
+        over 3)"""
+        from .verifier import verify_aggregate_bytes
+        return verify_aggregate_bytes(self._ctx, pvk, data, public_inputs_list, coeffs)
+
+    def verify_proofs_aggregate_bytes(self, pvk, data, public_inputs_list, coeffs=None) -> bool:
+        return self.verify_aggregate_bytes_verdict(pvk, data, public_inputs_list, coeffs) == 1
+
     def check_proof_subgroups(self, proofs) -> np.ndarray:
         """the same per proof (g16_check_proof_subgroups): 2 if A, B or C is off its curve, otherwise 0 if one is outside its
         subgroup, otherwise 1"""

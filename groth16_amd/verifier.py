@@ -177,6 +177,82 @@ def check_proof_subgroups(ctx, proofs) -> np.ndarray:
     return flags
 
 
+def _encoded(data, size: int) -> np.ndarray:
+    """bytes or a uint8 array as a contiguous uint8 vector holding whole encodings of `size` bytes"""
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8:
+            raise ValueError("encoded points are bytes or a uint8 array")
+        a = np.ascontiguousarray(data).reshape(-1)
+    else:
+        a = np.frombuffer(bytes(data), dtype=np.uint8)
+    if a.size % size:
+        raise ValueError(f"{a.size} bytes are no whole number of {size}-byte encodings")
+    return a
+
+
+def _fq_bytes(curve: str) -> int:
+    return 48 if curve == "bls12_381" else 32
+
+
+def _u8ptr(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p) if a.size else None
+
+
+def decompress_points(ctx, data, g2: bool = False):
+    """g16_decompress_points: packed compressed points (G1, or G2 with g2=True) decoded on the GPU by the rules of
+    deserialize_points(compressed=True, validate=0).  (points, status): affine Montgomery limbs per point and a byte per point --
+    1 decoded, 0 an invalid encoding (its point is the identity)"""
+    L = FQ_LIMBS[ctx.curve]
+    enc = _encoded(data, _fq_bytes(ctx.curve) * (2 if g2 else 1))
+    n = enc.size // (_fq_bytes(ctx.curve) * (2 if g2 else 1))
+    out = np.zeros((n, (4 if g2 else 2) * L), dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_decompress_points(ctx.handle, int(bool(g2)), _u8ptr(enc), n, ptr64(out.reshape(-1)) if n else None, _u8ptr(status)))
+    return out, status
+
+
+def decompress_proofs(ctx, data):
+    """g16_decompress_proofs: n compressed proofs A | B | C (proof_to_bytes(compressed=True)) decoded on the GPU.
+    (flat_proofs, status): n x (A | B | C) affine as verify_batch takes them, and a byte per proof -- 1 iff A, B and C all decode"""
+    L = FQ_LIMBS[ctx.curve]
+    enc = _encoded(data, 4 * _fq_bytes(ctx.curve))
+    n = enc.size // (4 * _fq_bytes(ctx.curve))
+    out = np.zeros((n, 8 * L), dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_decompress_proofs(ctx.handle, _u8ptr(enc), n, ptr64(out.reshape(-1)) if n else None, _u8ptr(status)))
+    return out, status
+
+
+def decompress_points_host(curve: str, data, g2: bool = False):
+    """decompress_points on the CPU through g16_host_decompress_points (the same C++ templates, no GPU): (points, status)"""
+    L = FQ_LIMBS[curve]
+    size = _fq_bytes(curve) * (2 if g2 else 1)
+    enc = _encoded(data, size)
+    n = enc.size // size
+    out = np.zeros((n, (4 if g2 else 2) * L), dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_host_decompress_points(CURVE_ID[curve], int(bool(g2)), _u8ptr(enc), n, ptr64(out.reshape(-1)) if n else None,
+                                             _u8ptr(status)))
+    return out, status
+
+
+def verify_aggregate_bytes(ctx, pvk: PreparedVerifyingKey, data, public_inputs_list, coeffs=None) -> int:
+    """g16_verify_aggregate_bytes' verdict over compressed proofs, decoded and membership-tested on the GPU: 1 every proof holds,
+    0 the aggregate equation fails, 3 a point is outside its prime-order subgroup, 4 some proof's bytes do not decode (4 wins over 3)"""
+    enc = _encoded(data, 4 * _fq_bytes(pvk.curve))
+    n = enc.size // (4 * _fq_bytes(pvk.curve))
+    x, num_public = _flat_inputs(public_inputs_list, n, pvk.vk.num_public)
+    r = _flat_coeffs(coeffs, n)
+    v = np.zeros(1, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_verify_aggregate_bytes(ctx.handle, pvk.handle, _u8ptr(enc), n, ptr64(x) if x.size else None, num_public,
+                                             ptr64(r.reshape(-1)) if r is not None and n else None, v.ctypes.data_as(C.c_void_p)))
+    return int(v[0])
+
+
 def _host_aggregate_args(curve, vk, proofs, public_inputs_list, coeffs):
     vkk = as_vk(vk)
     flat = _flat_proofs(proofs, curve)

@@ -480,6 +480,31 @@ int g16_verify_aggregate_checked(g16_ctx* ctx, const g16_pvk* pvk, const uint64_
 /* g16_check_subgroups' templates on the CPU (no GPU needed); the point checks of Validate::Yes */
 int g16_host_check_subgroups(int curve, int g2, const uint64_t* points, uint64_t n, uint8_t* flags);
 
+/* ---- compressed points and proofs decoded on the GPU: what Proof::deserialize_compressed reads (data_structures.rs:8-16) ----
+ * The byte formats and rules are those of g16_deserialize_points(compressed = 1, validate = 0) (serialize.hip): BLS12-381 zcash
+ * form (48 / 96 bytes, big-endian, flags 0x80 / 0x40 / 0x20 in the first byte, Fq2 as c1 | c0), BN254 ark-serialize form (32 / 64
+ * bytes, little-endian, flags 0x80 / 0x40 in the last byte, Fq2 as c0 | c1).  One square root per point, one point per GPU lane
+ * (DESIGN.md 4.6).  Where that call answers G16_ERR_INVALID_DATA for the whole array -- a coordinate >= p, BLS12-381 without the
+ * compressed bit, the infinity flag with x != 0 or with the sign flag, an x with no point -- these answer per item: status 1 and the
+ * affine point (byte-equal to g16_deserialize_points' output; the identity all-zero), or status 0 and the identity.  No on-curve test
+ * is needed (a decoded point is on its curve by construction) and none for the subgroup is made: g16_check_subgroups does that.
+ * bytes: n packed encodings in host memory (g2 = 0: G1, 1: G2), points_out: n affine points, status: n bytes.  n = 0 is G16_OK.
+ * A multi-device ctx cuts the array into one chunk per device; outputs stay in input order. */
+int g16_decompress_points(g16_ctx* ctx, int g2, const uint8_t* bytes, uint64_t n, uint64_t* points_out, uint8_t* status);
+/* bytes: n compressed proofs A | B | C (192 / 128 bytes each; Proof<E>, data_structures.rs:8-16); proofs_out: n x (A | B | C) affine
+ * as g16_verify_batch takes them; status[i]: 1 iff A, B and C all decode (a point that does not is written as the identity). */
+int g16_decompress_proofs(g16_ctx* ctx, const uint8_t* bytes, uint64_t n, uint64_t* proofs_out, uint8_t* status);
+/* g16_decompress_points' templates on the CPU (no GPU needed), one status byte per point */
+int g16_host_decompress_points(int curve, int g2, const uint8_t* bytes, uint64_t n, uint64_t* points_out, uint8_t* status);
+/* Bytes to verdict: g16_verify_aggregate_checked over compressed proofs (data_structures.rs:8-16 by the serialize.hip rules above).
+ * Per device chunk the bytes are uploaded (a third of the affine form), decoded into a device buffer, and the membership tests and
+ * the aggregate equation run on that buffer and the same stream; nothing returns to the host in between.
+ * *verdict: 1 / 0 / 3 as g16_verify_aggregate_checked, plus 4: some proof's bytes do not decode (the equation's outcome is then not
+ * reported; g16_decompress_proofs names the proofs).  4 wins over 3, 3 over 0 / 1; 2 cannot occur.  n = 0 gives 1.  Arguments,
+ * coefficients, G16_ERR_MALFORMED_VK and multi-device chunking as g16_verify_aggregate. */
+int g16_verify_aggregate_bytes(g16_ctx* ctx, const g16_pvk* pvk, const uint8_t* proof_bytes, uint64_t n, const uint64_t* public_inputs,
+                               uint64_t num_public, const uint64_t* coeffs, uint8_t* verdict);
+
 const char* g16_strerror(int status);
 /* text of the last HIP error seen on this thread ("" if none) */
 const char* g16_last_error(void);

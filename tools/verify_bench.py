@@ -5,6 +5,7 @@
     python tools/verify_bench.py --curve bn254 --host [--reps 20]
     python tools/verify_bench.py --curve bls12_381 --n 65536 --aggregate [--reps 5]
     python tools/verify_bench.py --curve bls12_381 --n 65536 --subgroup [--reps 5]
+    python tools/verify_bench.py --curve bls12_381 --n 65536 --decompress [--reps 5] [--out profiles/decompress_mi355x.jsonl]
 
 --n: proofs per g16_verify_batch call (copies of rerandomised honest proofs of a small SYN circuit, one public input); the line
 reports the g16_pvk_load time, the best of --reps timed calls after one warm-up call (host clock around the call, which ends in a
@@ -15,7 +16,10 @@ g16_verify_batch for the same n; both get the public inputs as one (n, l, 4) arr
 proofs.  --subgroup: on one batch and in one process g16_verify_aggregate, g16_verify_aggregate_checked,
 g16_check_proof_subgroups alone, and the host path the last one replaces -- g16_deserialize_points(validate=2) over the same 3n
 points (uncompressed bytes, so no square root is in the figure) on the CPUs the process may use; the line reports the ratios
-checked / aggregate and host / GPU check.  `spread` is (slowest - fastest) / fastest of the --reps timed calls.  Run each step under its own time limit."""
+checked / aggregate and host / GPU check.  --decompress: on one batch of compressed proofs and in one process (a)
+g16_decompress_proofs, (b) the host's g16_deserialize_points(compressed, validate=0) over the same 3n points on the CPUs the process
+may use, (c) g16_verify_aggregate_bytes, (d) g16_verify_aggregate_checked on the already decoded proofs -- the floor of (c) -- and
+(e) the host path that (c) replaces: (b) followed by (d); --out appends the line to a file.  `spread` is (slowest - fastest) / fastest of the --reps timed calls.  Run each step under its own time limit."""
 import argparse
 import json
 import os
@@ -39,6 +43,8 @@ def main():
     ap.add_argument("--host", action="store_true")
     ap.add_argument("--aggregate", action="store_true")
     ap.add_argument("--subgroup", action="store_true")
+    ap.add_argument("--decompress", action="store_true")
+    ap.add_argument("--out", help="append the JSON line of --decompress to this file")
     a = ap.parse_args()
     vk, proofs, x, cp = oracle_case(a.curve)
     L = cp.fq_limbs64
@@ -55,6 +61,8 @@ def main():
                           for _ in range(7)]
     flat = np.ascontiguousarray(np.stack([base[i % len(base)] for i in range(a.n)]))
     xs = [x] * a.n
+    if a.decompress:
+        return decompress(a, vk, flat, np.ascontiguousarray(np.broadcast_to(x.reshape(1, -1, 4), (a.n,) + x.reshape(-1, 4).shape)), L)
     if a.subgroup:
         return subgroup(a, vk, flat, np.ascontiguousarray(np.broadcast_to(x.reshape(1, -1, 4), (a.n,) + x.reshape(-1, 4).shape)), L)
     if a.aggregate:
@@ -121,6 +129,52 @@ def subgroup(a, vk, flat, xs, L):
                           checked_ms=round(chk * 1e3, 3), checked_spread=round(chk_spread, 4), check_only_ms=round(sub * 1e3, 3),
                           check_only_spread=round(sub_spread, 4), host_validate_ms=round(hst * 1e3, 3), host_spread=round(hst_spread, 4),
                           checked_over_aggregate=round(chk / agg, 3), host_over_gpu_check=round(hst / sub, 1), reps=a.reps)))
+
+
+def decompress(a, vk, flat, xs, L):
+    from groth16_amd.serialize import deserialize_points, serialize_points
+    fb = 48 if a.curve == "bls12_381" else 32
+    data = np.zeros((a.n, 4 * fb), dtype=np.uint8)   # n x (A | B | C), the layout of proof_to_bytes(compressed=True)
+    for lo, hi, g2, at, size in ((0, 2 * L, False, 0, fb), (2 * L, 6 * L, True, fb, 2 * fb), (6 * L, 8 * L, False, 3 * fb, fb)):
+        data[:, at: at + size] = np.frombuffer(serialize_points(a.curve, np.ascontiguousarray(flat[:, lo:hi]), g2), dtype=np.uint8).reshape(a.n, size)
+    b1 = np.ascontiguousarray(np.concatenate([data[:, :fb], data[:, 3 * fb:]])).tobytes()
+    b2 = np.ascontiguousarray(data[:, fb: 3 * fb]).tobytes()
+
+    def host_decode():
+        deserialize_points(a.curve, b1, 2 * a.n, False, compressed=True, validate=0)
+        deserialize_points(a.curve, b2, a.n, True, compressed=True, validate=0)
+
+    with g.Groth16(a.curve, device=0) as prover:
+        pvk = prover.prepare_verifying_key(vk)
+        decoded, status = prover.decompress_proofs(data)
+        assert (status == 1).all() and decoded.tobytes() == flat.tobytes(), "the GPU decoded the benchmark batch differently"
+        assert prover.verify_aggregate_bytes_verdict(pvk, data, xs) == 1, "the benchmark batch was rejected"
+        dec, dec_spread = timed(lambda: prover.decompress_proofs(data), a.reps)
+        hst, hst_spread = timed(host_decode, a.reps)
+        fused, fused_spread = timed(lambda: prover.verify_aggregate_bytes_verdict(pvk, data, xs), a.reps)
+        chk, chk_spread = timed(lambda: prover.verify_aggregate_verdict(pvk, flat, xs, check_subgroups=True), a.reps)
+
+        def host_path():
+            host_decode()
+            prover.verify_aggregate_verdict(pvk, flat, xs, check_subgroups=True)
+
+        path, path_spread = timed(host_path, a.reps)
+        pvk.close()
+    line = json.dumps(dict(curve=a.curve, n=a.n, mode="decompress", cpus=len(os.sched_getaffinity(0)),
+                           gpu_decompress_ms=round(dec * 1e3, 3), gpu_decompress_spread=round(dec_spread, 4),
+                           gpu_decompress_proofs_per_s=round(a.n / dec, 1),
+                           host_decompress_ms=round(hst * 1e3, 3), host_decompress_spread=round(hst_spread, 4),
+                           host_decompress_proofs_per_s=round(a.n / hst, 1),
+                           bytes_to_verdict_ms=round(fused * 1e3, 3), bytes_to_verdict_spread=round(fused_spread, 4),
+                           bytes_to_verdict_proofs_per_s=round(a.n / fused, 1),
+                           checked_decoded_ms=round(chk * 1e3, 3), checked_decoded_spread=round(chk_spread, 4),
+                           host_decode_then_checked_ms=round(path * 1e3, 3), host_decode_then_checked_spread=round(path_spread, 4),
+                           host_over_gpu_decompress=round(hst / dec, 1), bytes_over_checked=round(fused / chk, 3),
+                           host_path_over_bytes=round(path / fused, 2), reps=a.reps))
+    print(line)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
