@@ -17,8 +17,8 @@
 //                           (point index | sign) by (window, bucket) -- order inside a bucket is
 //                           irrelevant because group addition commutes
 //      (1, 2, 4 as written serve ad-hoc bases -- g16_msm_g1 / _g2; proving-key MSMs use the merged-window variants below:
-//       class_count / class_partition, bucket_count_merged / bucket_wg_scan / bucket_scatter_merged -- no global atomics, 32 KB
-//       histograms that fit on a compute unit beside the bucket passes)
+//       class_count / class_partition, then sub_count / sub_partition / final_sort (4m) -- no global atomics, workgroups that fit on
+//       a compute unit beside the bucket passes; bucket_count_merged / bucket_wg_scan / bucket_scatter_merged serve padded regions)
 //   5. bucket_accumulate30_kernel  THE hot kernel: one lane (G1) / lane pair (G2) per 64-entry SEGMENT of the
 //                           sorted list gathers affine bases (96 B / 192 B each) and folds them with XYZZ
 //                           mixed additions (8M+2S, no inversion; Y3 under one reduction) in 30-bit lazy arithmetic
@@ -143,9 +143,11 @@ static __global__ __launch_bounds__(SORT_THREADS) void bucket_count_kernel(const
 //   class_count_kernel / class_partition_kernel   entries -> Q contiguous class regions (block-local LDS cursors on top
 //                           of scanned per-(class, block) counts); an entry is a u16 key (bucket in class | sign << 15)
 //                           and a u32 tag (point | window << 26)
-//   bucket_count_merged_kernel / bucket_wg_scan_kernel / bucket_scatter_merged_kernel   per class: an LDS counting sort over the
-//                           class region, its histograms exchanged through a [class][workgroup][bucket] matrix instead of global
-//                           atomics.   Sorted entry = point | window << 26 | sign << 31.
+//   sub_count_kernel / sub_partition_kernel / final_sort_kernel (4m below)   class region -> sub-class regions -> the sorted list,
+//                           its last write coalesced.   Sorted entry = point | window << 26 | sign << 31.
+//   bucket_count_merged_kernel / bucket_wg_scan_kernel / bucket_scatter_merged_kernel   padded bucket regions only
+//                           (G16_MSM_AFFINE_LEVELS > 0): per class an LDS counting sort over the class region, its histograms
+//                           exchanged through a [class][workgroup][bucket] matrix instead of global atomics.
 // ---------------------------------------------------------------------------------------------
 static constexpr int CLASS_THREADS = 256;
 static constexpr int MAX_CLASSES = 64;
@@ -361,6 +363,184 @@ static __global__ void bucket_slots_kernel(const uint32_t* __restrict__ offsets,
     const uint32_t np = hi > lo ? ((hi - 1) / lseg - lo / lseg + 1u) : 0u;
     nparts[b] = np;
     if (np > HEAVY_PARTS) heavy[1 + atomicAdd(&heavy[0], 1u)] = b;
+}
+
+// ---------------------------------------------------------------------------------------------
+// 4m. merged plan without padded bucket regions (affine_levels == 0): second partition level + LDS-resident final level.
+// The scatter above puts every word at a random position of a 3.4 MB class region -- a memory sector dirtied for 4 useful bytes,
+// 1.2 ms for 54.5 M entries, and the partial-line traffic slows the witness map's first sweep beside it.  Instead:
+//   sub_count_kernel / sub_partition_kernel   class region -> S sub-class regions of 2^sublog consecutive buckets (2^6 at 2^22, c = 20:
+//                           ~6.7 K entries each).  A workgroup stages a tile of SUB_TILE entries in LDS, ordered by sub-class, and
+//                           streams it out: every destination gets a run of consecutive words from consecutive lanes.  Cursors come
+//                           from a [class][sub-class][workgroup] count matrix and one prefix scan, as on the class level.
+//   final_sort_kernel       one workgroup per sub-class: LDS histogram of its <= 128 buckets -> counts[], scan, entries placed by
+//                           bucket in LDS, the slice of `sorted` streamed out coalesced.  With unpadded regions a bucket's offset is
+//                           the sub-class region's start + the scanned histogram, so this level needs neither `offsets` nor a count
+//                           pass of its own.  A sub-class with more than FINAL_CAP entries (repeated scalars; the top window's short
+//                           digit range doubles the load of the first 2^15 buckets) is detected from its region's bounds and scattered
+//                           directly through the same LDS cursors: 2^sublog open runs per workgroup instead of 2^13.
+// No global atomics.  <= 64 registers, <= 48 KB of LDS per 256-lane workgroup: the kernels run beside the G2 bucket pass like the
+// ones they replace (tests/test_sort_kernel_resources.py).
+// ---------------------------------------------------------------------------------------------
+static constexpr uint32_t MAX_SUBS = 256;        // sub-classes per class
+static constexpr uint32_t MAX_SUB_LOG = 7;       // buckets per sub-class <= 128
+static constexpr uint32_t SUB_TILE = 4096;       // entries staged per step of the sub-class partition: runs of ~32 per destination
+static constexpr uint32_t SUB_PER_LANE = SUB_TILE / SORT_M_THREADS;
+static constexpr uint32_t SUB_BATCH = 4;         // loads in flight per lane in the partition's loops
+static constexpr uint32_t FINAL_CAP = 10240;     // entries of a sub-class the final level holds in LDS (40 KB of sorted words)
+static constexpr uint32_t FINAL_BATCH = 4;       // loads in flight per lane in the final level's loops
+static_assert(SORT_M_THREADS == SCAN_THREADS && MAX_SUBS <= SCAN_THREADS && SUB_TILE <= 65536, "block_exclusive scans one value per lane");
+
+// One step of an LDS counter per valid lane, returning the value before the step.  A wave whose valid lanes all hit ONE counter
+// (a repeated scalar: every entry of the region in one bucket) takes its slots with a single atomic instead of 64 serialised ones.
+// Every lane of the wave must call it.
+__device__ __forceinline__ uint32_t lds_take(uint32_t* ctr, uint32_t idx, bool valid) {
+    const uint64_t act = __ballot(valid);
+    if (act == 0) return 0;
+    const int first = __ffsll((unsigned long long)act) - 1;
+    const uint32_t idx0 = (uint32_t)__shfl((int)idx, first);
+    if (__ballot(valid && idx == idx0) == act) {
+        const uint32_t lane = threadIdx.x & 63u;
+        uint32_t base = 0;
+        if ((int)lane == first) base = atomicAdd(&ctr[idx0], (uint32_t)__popcll(act));
+        base = (uint32_t)__shfl((int)base, first);
+        return base + (uint32_t)__popcll(act & (((uint64_t)1 << lane) - 1u));
+    }
+    return valid ? atomicAdd(&ctr[idx], 1u) : 0u;
+}
+
+// grid = (G, Q): workgroup (x, q) owns the tiles x, x + G, ... (SUB_TILE entries each) of class region q.
+// sub_counts[(q * S + s) * G + x] = its entries of sub-class s -- the order in which the exclusive scan of the matrix yields its cursors
+static __global__ __launch_bounds__(SORT_M_THREADS) void sub_count_kernel(const uint16_t* __restrict__ ent_key,
+                                                                          const uint32_t* __restrict__ class_off, uint32_t nb, uint32_t S,
+                                                                          uint32_t sublog, uint32_t* __restrict__ sub_counts) {
+    __shared__ uint32_t cnt[MAX_SUBS];
+    const uint32_t q = blockIdx.y;
+    const uint64_t lo = class_off[(uint64_t)q * nb], hi = class_off[(uint64_t)(q + 1) * nb];
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint64_t tlo = lo + (uint64_t)blockIdx.x * SUB_TILE; tlo < hi; tlo += (uint64_t)gridDim.x * SUB_TILE) {
+        uint32_t k[SUB_PER_LANE];
+        G16_UNROLL for (uint32_t j = 0; j < SUB_PER_LANE; ++j) {
+            const uint64_t p = tlo + j * SORT_M_THREADS + threadIdx.x;
+            k[j] = p < hi ? (uint32_t)ent_key[p] : 0xffffffffu;
+        }
+        G16_UNROLL for (uint32_t j = 0; j < SUB_PER_LANE; ++j) (void)lds_take(cnt, (k[j] & 0x7fffu) >> sublog, k[j] != 0xffffffffu);
+    }
+    __syncthreads();
+    if (threadIdx.x < S) sub_counts[((uint64_t)q * S + threadIdx.x) * gridDim.x + blockIdx.x] = cnt[threadIdx.x];
+}
+
+static __global__ __launch_bounds__(SORT_M_THREADS) void sub_partition_kernel(const uint16_t* __restrict__ ent_key,
+                                                                              const uint32_t* __restrict__ ent_tag,
+                                                                              const uint32_t* __restrict__ class_off, uint32_t nb, uint32_t S,
+                                                                              uint32_t sublog, const uint32_t* __restrict__ sub_off,
+                                                                              uint16_t* __restrict__ out_key, uint32_t* __restrict__ out_tag) {
+    __shared__ uint32_t cnt[MAX_SUBS], start[MAX_SUBS], cur[MAX_SUBS], gcur[MAX_SUBS], sa[SCAN_THREADS];
+    __shared__ uint32_t stag[SUB_TILE];
+    __shared__ uint16_t skey[SUB_TILE];
+    const uint32_t q = blockIdx.y;
+    const uint64_t lo = class_off[(uint64_t)q * nb], hi = class_off[(uint64_t)(q + 1) * nb];
+    if (lo + (uint64_t)blockIdx.x * SUB_TILE >= hi) return;
+    gcur[threadIdx.x] = threadIdx.x < S ? sub_off[((uint64_t)q * S + threadIdx.x) * gridDim.x + blockIdx.x] : 0u;
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint64_t tlo = lo + (uint64_t)blockIdx.x * SUB_TILE; tlo < hi; tlo += (uint64_t)gridDim.x * SUB_TILE) {
+        const uint32_t tn = (uint32_t)min((uint64_t)SUB_TILE, hi - tlo);
+        // two rolled loops, SUB_BATCH loads in flight per lane: count the tile, scan, then take the staging slots from the scanned
+        // cursors (the keys come from the cache the second time; ranks kept in registers would cost sixteen of them)
+        _Pragma("unroll 1") for (uint32_t i0 = 0; i0 < tn; i0 += SUB_BATCH * SORT_M_THREADS) {
+            uint32_t k[SUB_BATCH];
+            G16_UNROLL for (uint32_t j = 0; j < SUB_BATCH; ++j) {
+                const uint32_t i = i0 + j * SORT_M_THREADS + threadIdx.x;
+                k[j] = i < tn ? (uint32_t)ent_key[tlo + i] : 0xffffffffu;
+            }
+            G16_UNROLL for (uint32_t j = 0; j < SUB_BATCH; ++j) (void)lds_take(cnt, (k[j] & 0x7fffu) >> sublog, k[j] != 0xffffffffu);
+        }
+        __syncthreads();
+        uint32_t tot;
+        const uint32_t mine = cnt[threadIdx.x], ex = block_exclusive(mine, sa, &tot);
+        start[threadIdx.x] = ex;
+        cur[threadIdx.x] = ex;
+        __syncthreads();
+        _Pragma("unroll 1") for (uint32_t i0 = 0; i0 < tn; i0 += SUB_BATCH * SORT_M_THREADS) {
+            uint32_t k[SUB_BATCH], t[SUB_BATCH];
+            G16_UNROLL for (uint32_t j = 0; j < SUB_BATCH; ++j) {
+                const uint32_t i = i0 + j * SORT_M_THREADS + threadIdx.x;
+                k[j] = i < tn ? (uint32_t)ent_key[tlo + i] : 0xffffffffu;
+                t[j] = i < tn ? ent_tag[tlo + i] : 0u;
+            }
+            G16_UNROLL for (uint32_t j = 0; j < SUB_BATCH; ++j) {
+                const bool valid = k[j] != 0xffffffffu;
+                const uint32_t pos = lds_take(cur, (k[j] & 0x7fffu) >> sublog, valid);
+                if (valid) {
+                    skey[pos] = (uint16_t)k[j];
+                    stag[pos] = t[j];
+                }
+            }
+        }
+        __syncthreads();
+        // staged position i belongs to sub-class s at rank i - start[s]: consecutive lanes, consecutive words of s's region
+        _Pragma("unroll 1") for (uint32_t i = threadIdx.x; i < tn; i += SORT_M_THREADS) {
+            const uint32_t key = skey[i], s = (key & 0x7fffu) >> sublog;
+            const uint32_t g = gcur[s] + (i - start[s]);
+            out_key[g] = (uint16_t)key;
+            out_tag[g] = stag[i];
+        }
+        __syncthreads();
+        gcur[threadIdx.x] += mine;
+        cnt[threadIdx.x] = 0;
+        __syncthreads();
+    }
+}
+
+// grid = Q * S: workgroup u owns sub-class u = buckets [u << sublog, (u + 1) << sublog), entries [sub_off[u * G], sub_off[(u + 1) * G])
+static __global__ __launch_bounds__(SORT_M_THREADS) void final_sort_kernel(const uint16_t* __restrict__ ent_key,
+                                                                           const uint32_t* __restrict__ ent_tag,
+                                                                           const uint32_t* __restrict__ sub_off, uint32_t G, uint32_t sublog,
+                                                                           uint32_t* __restrict__ counts, uint32_t* __restrict__ sorted) {
+    __shared__ uint32_t cnt[1u << MAX_SUB_LOG], cur[1u << MAX_SUB_LOG], sa[SCAN_THREADS];
+    __shared__ uint32_t out[FINAL_CAP];
+    const uint32_t u = blockIdx.x, NB = 1u << sublog;
+    const uint64_t lo = sub_off[(uint64_t)u * G], hi = sub_off[(uint64_t)(u + 1) * G];
+    if (threadIdx.x < NB) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint64_t base = lo; base < hi; base += 2 * FINAL_BATCH * SORT_M_THREADS) {
+        uint32_t k[2 * FINAL_BATCH];
+        G16_UNROLL for (uint32_t j = 0; j < 2 * FINAL_BATCH; ++j) {
+            const uint64_t p = base + j * SORT_M_THREADS + threadIdx.x;
+            k[j] = p < hi ? (uint32_t)ent_key[p] : 0xffffffffu;
+        }
+        G16_UNROLL for (uint32_t j = 0; j < 2 * FINAL_BATCH; ++j) (void)lds_take(cnt, k[j] & (NB - 1u), k[j] != 0xffffffffu);
+    }
+    __syncthreads();
+    const uint32_t mine = threadIdx.x < NB ? cnt[threadIdx.x] : 0u;
+    if (threadIdx.x < NB) counts[((uint64_t)u << sublog) + threadIdx.x] = mine;
+    uint32_t tot;
+    const uint32_t ex = block_exclusive(mine, sa, &tot);
+    if (threadIdx.x < NB) cur[threadIdx.x] = ex;
+    __syncthreads();
+    const bool resident = hi - lo <= FINAL_CAP;   // workgroup-uniform
+    for (uint64_t base = lo; base < hi; base += FINAL_BATCH * SORT_M_THREADS) {
+        uint32_t k[FINAL_BATCH], t[FINAL_BATCH];
+        G16_UNROLL for (uint32_t j = 0; j < FINAL_BATCH; ++j) {
+            const uint64_t p = base + j * SORT_M_THREADS + threadIdx.x;
+            k[j] = p < hi ? (uint32_t)ent_key[p] : 0xffffffffu;
+            t[j] = p < hi ? ent_tag[p] : 0u;
+        }
+        G16_UNROLL for (uint32_t j = 0; j < FINAL_BATCH; ++j) {
+            const bool valid = k[j] != 0xffffffffu;
+            const uint32_t pos = lds_take(cur, k[j] & (NB - 1u), valid), word = t[j] | ((k[j] >> 15) << 31);
+            if (valid) {
+                if (resident) out[pos] = word;
+                else sorted[lo + pos] = word;
+            }
+        }
+    }
+    if (!resident) return;
+    __syncthreads();
+    const uint32_t N = (uint32_t)(hi - lo);
+    for (uint32_t i = threadIdx.x; i < N; i += SORT_M_THREADS) sorted[lo + i] = out[i];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1046,7 +1226,25 @@ int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Aren
     }
     const unsigned nchunks = (unsigned)((n + plan.chunk - 1) / plan.chunk);
     const uint32_t blog = plan.merged ? slog : (uint32_t)ilog2(plan.B);
-    const uint32_t max_scan = std::max(M, plan.merged ? Q * nb : 0u);
+    // merged plan, unpadded bucket regions: second partition level + LDS-resident final level (4m above).  Sub-classes of 2^sublog
+    // buckets, the largest size whose EXPECTED load leaves a quarter of the final level's LDS list free (2^6 at 2^22, c = 20); what
+    // exceeds the list anyway is scattered directly by the same kernel.  Padded regions (G16_MSM_AFFINE_LEVELS > 0) keep the
+    // histogram-matrix scatter, which places entries by `offsets`.
+    const bool two_level = plan.merged && R == 0;
+    uint32_t sublog = 0, S = 1;
+    unsigned gx2 = 1;
+    if (two_level) {
+        const uint64_t mean_x4 = 4 * (nw / (uint64_t)plan.shard_n) / M + 1;   // 4 x the mean bucket load
+        const uint32_t lo_log = slog > 8 ? slog - 8 : 0u;                     // S <= MAX_SUBS
+        sublog = std::min<uint32_t>(slog, MAX_SUB_LOG);
+        while (sublog > lo_log && (mean_x4 << sublog) > 3 * (uint64_t)FINAL_CAP) --sublog;
+        if (sublog > MAX_SUB_LOG) return G16_ERR_INTERNAL;
+        S = Bs >> sublog;
+        // ~4096 workgroups of 256 lanes over the class regions, a tile of SUB_TILE entries at a time
+        gx2 = std::max(1u, std::min(std::min(4096u / Q, 256u), (unsigned)((nw + SUB_TILE - 1) / SUB_TILE)));
+    }
+    const uint32_t sub_cells = two_level ? Q * S * gx2 : 0u;
+    const uint32_t max_scan = std::max(std::max(M, plan.merged ? Q * nb : 0u), sub_cells);
     G16_TRY(arena.alloc_n((size_t)(max_scan + SCAN_TILE - 1) / SCAN_TILE, &block_sums));
     auto prefix_scan = [&](const uint32_t* vals, uint32_t* prefix, uint32_t count, uint32_t padmask = 0) -> int {
         const uint32_t nblocks = (count + SCAN_TILE - 1) / SCAN_TILE;
@@ -1061,12 +1259,20 @@ int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Aren
     // merged plan: ~4096 workgroups of 256 lanes over the class regions (a class region may hold anything between nothing and all
     // entries), at most 256 per class: every workgroup zeroes, stores and re-reads a histogram row whatever it counts
     unsigned gx = std::max(1u, std::min(std::min(4096u / Q, 256u), (unsigned)((nw + SORT_M_THREADS - 1) / SORT_M_THREADS)));
-    if (const char* e = getenv("G16_SORT_GX")) {   // experiments: workgroups per class of the merged counting sort
+    if (const char* e = getenv("G16_SORT_GX")) {   // experiments: workgroups per class of the histogram-matrix scatter (padded regions)
         const int v = atoi(e);
         if (v >= 1 && v <= 4096) gx = (unsigned)v;
     }
-    uint32_t* wg_counts = nullptr;   // merged plan: [class][workgroup][bucket] histograms, then their prefixes over the workgroups
-    if (plan.merged) G16_TRY(arena.alloc_n((size_t)Q * gx * Bs, &wg_counts));
+    uint32_t* wg_counts = nullptr;   // merged plan, padded regions: [class][workgroup][bucket] histograms, then their prefixes over the workgroups
+    if (plan.merged && !two_level) G16_TRY(arena.alloc_n((size_t)Q * gx * Bs, &wg_counts));
+    uint16_t* sub_key = nullptr;     // two-level plan: entry keys and tags, sub-class-partitioned
+    uint32_t *sub_tag = nullptr, *sub_cnt = nullptr, *sub_off = nullptr;
+    if (two_level) {
+        G16_TRY(arena.alloc_n(nw ? nw : 1, &sub_key));
+        G16_TRY(arena.alloc_n(nw ? nw : 1, &sub_tag));
+        G16_TRY(arena.alloc_n((size_t)sub_cells + 1, &sub_cnt));
+        G16_TRY(arena.alloc_n((size_t)sub_cells + 1, &sub_off));
+    }
     if (n) {
         if (plan.merged) {
             hipLaunchKernelGGL((class_count_kernel<Fr>), dim3(nb), dim3(CLASS_THREADS), 0, st, d_scalars, n, pd, blog, Q, class_cnt);
@@ -1075,9 +1281,22 @@ int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Aren
             hipLaunchKernelGGL((class_partition_kernel<Fr>), dim3(nb), dim3(CLASS_THREADS), 0, st, d_scalars, n, pd, blog, Q, class_off, planes,
                                ent_tag);
             G16_LAUNCH_CHECK();
-            hipLaunchKernelGGL(bucket_count_merged_kernel, dim3(gx, Q), dim3(SORT_M_THREADS), lds, st, planes, class_off, nb, Bs, wg_counts);
-            G16_LAUNCH_CHECK();
-            hipLaunchKernelGGL(bucket_wg_scan_kernel, dim3((M + 255) / 256), dim3(256), 0, st, wg_counts, gx, Bs, M, counts);
+            if (two_level) {
+                hipLaunchKernelGGL(sub_count_kernel, dim3(gx2, Q), dim3(SORT_M_THREADS), 0, st, planes, class_off, nb, S, sublog, sub_cnt);
+                G16_LAUNCH_CHECK();
+                G16_TRY(prefix_scan(sub_cnt, sub_off, sub_cells));
+                hipLaunchKernelGGL(sub_partition_kernel, dim3(gx2, Q), dim3(SORT_M_THREADS), 0, st, planes, ent_tag, class_off, nb, S, sublog,
+                                   sub_off, sub_key, sub_tag);
+                G16_LAUNCH_CHECK();
+                // writes counts[] AND the sorted list: what follows only derives offsets, slots and the heavy list from the counts
+                hipLaunchKernelGGL(final_sort_kernel, dim3(Q * S), dim3(SORT_M_THREADS), 0, st, sub_key, sub_tag, sub_off, gx2, sublog, counts,
+                                   out->sorted);
+            } else {
+                hipLaunchKernelGGL(bucket_count_merged_kernel, dim3(gx, Q), dim3(SORT_M_THREADS), lds, st, planes, class_off, nb, Bs,
+                                   wg_counts);
+                G16_LAUNCH_CHECK();
+                hipLaunchKernelGGL(bucket_wg_scan_kernel, dim3((M + 255) / 256), dim3(256), 0, st, wg_counts, gx, Bs, M, counts);
+            }
         } else {
             hipLaunchKernelGGL((digits_kernel<Fr>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, n, pd, planes);
             G16_LAUNCH_CHECK();
@@ -1091,7 +1310,7 @@ int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Aren
                        out->heavy);
     G16_LAUNCH_CHECK();
     G16_TRY(prefix_scan(nparts, out->task_off, M));
-    if (n) {
+    if (n && !two_level) {
         if (plan.merged)
             hipLaunchKernelGGL(bucket_scatter_merged_kernel, dim3(gx, Q), dim3(SORT_M_THREADS), lds, st, planes, ent_tag, class_off, nb, Bs,
                                out->offsets, wg_counts, out->sorted);
