@@ -9,6 +9,8 @@ Reference interface mirrored (paths relative to /root/reference):
   Groth16.create_proof_with_reduction_no_zk          src/prover.rs:155-168 (matrices form)
   Groth16.create_random_proof_with_reduction         src/prover.rs:138-150 (matrices form)
   LibsnarkReduction.witness_map_from_matrices        src/r1cs_to_qap.rs:172-235
+  Groth16(curve, device, qap=...) / CircomReduction  trait R1CSToQAP, src/r1cs_to_qap.rs:71-120 (Groth16<E, QAP>); the second
+      implementor is ark-circom's, restated from its published source
   ProvingKey / Proof / ConstraintMatrices            src/data_structures.rs:8-16,125-143
   SynthesisError.PolynomialDegreeTooLarge            src/r1cs_to_qap.rs:178-179
   Groth16.generate_parameters_with_qap               src/generator.rs:47-208 (matrices form)
@@ -20,7 +22,7 @@ Reference interface mirrored (paths relative to /root/reference):
   VerifyingKey / PreparedVerifyingKey               src/data_structures.rs:31-66
 """
 from .binding import (G16Error, Lib, PolynomialDegreeTooLarge, SynthesisError, UnexpectedIdentity, lib, FQ_LIMBS, CURVE_ID)  # noqa: F401
-from .groth16 import (ConstraintMatrices, Groth16, LibsnarkReduction, PipelinedProver, Proof, ProvingKey, ShardedProver, finalize_host,  # noqa: F401
+from .groth16 import (CircomReduction, ConstraintMatrices, Groth16, LibsnarkReduction, PipelinedProver, Proof, ProvingKey, ShardedProver, finalize_host,  # noqa: F401
                       rerandomize_proof, shard_ranges)
 from .binding import MalformedVerifyingKey  # noqa: F401
 from .verifier import (PreparedVerifyingKey, VerifyingKey, check_subgroups_host, decompress_points_host, host_pairing, verify_proof_host,  # noqa: F401
@@ -28,7 +30,7 @@ from .verifier import (PreparedVerifyingKey, VerifyingKey, check_subgroups_host,
 from .r1cs import AssignmentMissing, ConstraintSynthesizer, ConstraintSystem, LinearCombination, Variable, lc  # noqa: F401
 
 __all__ = [
-    "Groth16", "LibsnarkReduction", "ConstraintMatrices", "ProvingKey", "Proof", "ShardedProver", "PipelinedProver", "G16Error", "SynthesisError",
+    "Groth16", "LibsnarkReduction", "CircomReduction", "ConstraintMatrices", "ProvingKey", "Proof", "ShardedProver", "PipelinedProver", "G16Error", "SynthesisError",
     "PolynomialDegreeTooLarge", "UnexpectedIdentity", "lib", "ConstraintSystem", "ConstraintSynthesizer", "Variable", "LinearCombination",
     "lc", "AssignmentMissing", "VerifyingKey", "PreparedVerifyingKey", "MalformedVerifyingKey", "verify_proof_host", "verify_proofs_aggregate_host", "check_subgroups_host", "host_pairing",
     "decompress_points_host",

@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("G16_LIB", os.path.join(HERE, "libg16_mi355x.so"))  # G16_LIB: A/B-test another build
 
 CURVE_ID = {"bls12_381": 0, "bn254": 1}
+QAP_LIBSNARK, QAP_CIRCOM = 0, 1   # g16_qap
 FQ_LIMBS = {"bls12_381": 6, "bn254": 4}
 
 u64p = C.POINTER(C.c_uint64)
@@ -126,6 +127,7 @@ EXPORTS = [
     "g16_dev_fp30_op", "g16_host_fp30_op",
     "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
     "g16_decompress_points", "g16_decompress_proofs", "g16_host_decompress_points", "g16_verify_aggregate_bytes",
+    "g16_circuit_load_qap", "g16_circuit_qap", "g16_generate_parameters_qap", "g16_h_query_len", "g16_host_h_query_scalars",
 ]
 
 
@@ -185,6 +187,8 @@ class Lib:
         c.g16_msm_bucket_shard.argtypes = [C.c_void_p, C.c_int, u64p, u64p, C.c_uint64, C.c_int, C.c_int, u64p]
         c.g16_host_msm_model_shard.argtypes = [C.c_int, C.c_int, u64p, u64p, C.c_uint64, C.c_int, C.c_int, C.c_int, u64p]
         c.g16_circuit_load.argtypes = [C.c_void_p, C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
+        c.g16_circuit_load_qap.argtypes = [C.c_void_p, C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+        c.g16_circuit_qap.argtypes = [C.c_void_p]
         c.g16_circuit_free.argtypes = [C.c_void_p]
         c.g16_circuit_free.restype = None
         c.g16_prove.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, u64p, u64p, C.POINTER(ProofC)]
@@ -221,6 +225,11 @@ class Lib:
         c.g16_host_msm_model.argtypes = [C.c_int, C.c_int, u64p, u64p, C.c_uint64, C.c_int, u64p]
         c.g16_generate_parameters.argtypes = [C.c_void_p, C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(ToxicWasteC),
                                               u64p, u64p, C.POINTER(ParamsViewC)]
+        c.g16_generate_parameters_qap.argtypes = [C.c_void_p, C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
+                                                  C.POINTER(ToxicWasteC), u64p, u64p, C.POINTER(ParamsViewC)]
+        c.g16_h_query_len.argtypes = [C.c_int, C.c_uint64]
+        c.g16_h_query_len.restype = C.c_uint64
+        c.g16_host_h_query_scalars.argtypes = [C.c_int, C.c_int, C.c_uint64, u64p, u64p, u64p]
         c.g16_serialized_point_size.restype = C.c_uint64
         c.g16_serialized_point_size.argtypes = [C.c_int, C.c_int, C.c_int]
         c.g16_serialize_points.argtypes = [C.c_int, C.c_int, C.c_int, u64p, C.c_uint64, C.c_char_p]

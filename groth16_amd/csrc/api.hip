@@ -428,8 +428,22 @@ void g16_pk_free(g16_pk* pk) {
 
 int g16_circuit_load(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints, uint64_t num_variables,
                      g16_circuit** out) {
+    return g16_circuit_load_qap(ctx, abc, num_inputs, num_constraints, num_variables, G16_QAP_LIBSNARK, out);
+}
+
+int g16_circuit_qap(const g16_circuit* c) { return c ? c->qap : -1; }
+
+int g16_circuit_load_qap(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints, uint64_t num_variables,
+                         int qap, g16_circuit** out) {
     if (!ctx || !abc || !out) return G16_ERR_BAD_ARG;
+    if (qap != G16_QAP_LIBSNARK && qap != G16_QAP_CIRCOM) return G16_ERR_BAD_ARG;
     if (!ctx->subs.empty()) {
+        // the multi-device key loader gathers h_query in the distributed map's block order before it knows the circuit, and that map
+        // is the Libsnark one: a Circom circuit is refused here rather than proved against a key cut for another h
+        if (qap != G16_QAP_LIBSNARK) {
+            g_last_error = "a Circom circuit cannot be loaded on a multi-device context (use one context per GPU and g16_prove_partial)";
+            return G16_ERR_BAD_ARG;
+        }
         const int n = (int)ctx->subs.size();
         g16_circuit* h = new (std::nothrow) g16_circuit{ctx->curve, ctx, nullptr, 0};
         if (!h) return G16_ERR_OOM;
@@ -459,7 +473,7 @@ int g16_circuit_load(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_input
         return G16_OK;
     }
     G16_HIP_TRY(hipSetDevice(ctx->device));
-    G16_DISPATCH(ctx->curve, I::circuit_load(ctx, abc, num_inputs, num_constraints, num_variables, out));
+    G16_DISPATCH(ctx->curve, I::circuit_load(ctx, abc, num_inputs, num_constraints, num_variables, qap, out));
 }
 
 void g16_circuit_free(g16_circuit* c) {
@@ -706,6 +720,10 @@ int g16_prove_partial_h(g16_ctx* ctx, const g16_pk* pk, const g16_circuit* circu
 
 int g16_dwm_create(g16_ctx* ctx, const g16_circuit* circuit, int rank, int world, g16_dwm** out) {
     if (!ctx || !circuit || !out || circuit->curve != ctx->curve || circuit->ctx != ctx || !ctx->subs.empty()) return G16_ERR_BAD_ARG;
+    if (circuit->qap != G16_QAP_LIBSNARK) {
+        g_last_error = "the distributed witness map is the Libsnark reduction's: a Circom circuit runs the replicated map (g16_prove_partial)";
+        return G16_ERR_BAD_ARG;
+    }
     G16_HIP_TRY(hipSetDevice(ctx->device));
     void* dw = nullptr;
     int rc;
@@ -850,19 +868,44 @@ int g16_host_msm_model_shard(int curve, int g2, const uint64_t* bases, const uin
 
 int g16_generate_parameters(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints, uint64_t num_variables,
                             const g16_toxic_waste* tw, const uint64_t* g1_generator, const uint64_t* g2_generator, const g16_params_view* out) {
+    return g16_generate_parameters_qap(ctx, abc, num_inputs, num_constraints, num_variables, G16_QAP_LIBSNARK, tw, g1_generator, g2_generator, out);
+}
+
+uint64_t g16_h_query_len(int qap, uint64_t domain_size) {
+    if (domain_size == 0) return 0;
+    return qap == G16_QAP_LIBSNARK ? domain_size - 1 : qap == G16_QAP_CIRCOM ? domain_size : 0;
+}
+
+int g16_host_h_query_scalars(int curve, int qap, uint64_t domain_size, const uint64_t t[4], const uint64_t delta_inverse[4], uint64_t* out) {
+    if (!t || !delta_inverse || !out) return G16_ERR_BAD_ARG;
+    if (qap != G16_QAP_LIBSNARK && qap != G16_QAP_CIRCOM) return G16_ERR_BAD_ARG;
+    try {
+        if (curve == G16_BLS12_381) return h_query_scalars_host<Bls12_381>(qap, domain_size, t, delta_inverse, out);
+        if (curve == G16_BN254) return h_query_scalars_host<Bn254>(qap, domain_size, t, delta_inverse, out);
+    } catch (const std::bad_alloc&) {
+        return G16_ERR_OOM;
+    }
+    return G16_ERR_BAD_ARG;
+}
+
+int g16_generate_parameters_qap(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints, uint64_t num_variables,
+                                int qap, const g16_toxic_waste* tw, const uint64_t* g1_generator, const uint64_t* g2_generator,
+                                const g16_params_view* out) {
     if (!ctx || !abc || !tw || !g1_generator || !g2_generator || !out) return G16_ERR_BAD_ARG;
+    if (qap != G16_QAP_LIBSNARK && qap != G16_QAP_CIRCOM) return G16_ERR_BAD_ARG;
     if (!out->alpha_g1 || !out->beta_g1 || !out->delta_g1 || !out->beta_g2 || !out->delta_g2 || !out->gamma_g2) return G16_ERR_BAD_ARG;
     if (!ctx->subs.empty())
-        return g16_generate_parameters(ctx->subs[0], abc, num_inputs, num_constraints, num_variables, tw, g1_generator, g2_generator, out);
+        return g16_generate_parameters_qap(ctx->subs[0], abc, num_inputs, num_constraints, num_variables, qap, tw, g1_generator, g2_generator,
+                                           out);
     G16_HIP_TRY(hipSetDevice(ctx->device));
     if (ctx->prep.valid) (void)hipStreamSynchronize(ctx->stream2);   // a dropped prepared sort still owns arena buffers
     ctx->prep.valid = false;   // the generator resets the arena
     try {
         if (ctx->curve == G16_BLS12_381)
-            return generate_parameters_device<Bls12_381>(ctx->stream, ctx->arena, abc, num_inputs, num_constraints, num_variables, tw,
+            return generate_parameters_device<Bls12_381>(ctx->stream, ctx->arena, abc, num_inputs, num_constraints, num_variables, qap, tw,
                                                          g1_generator, g2_generator, out);
         if (ctx->curve == G16_BN254)
-            return generate_parameters_device<Bn254>(ctx->stream, ctx->arena, abc, num_inputs, num_constraints, num_variables, tw,
+            return generate_parameters_device<Bn254>(ctx->stream, ctx->arena, abc, num_inputs, num_constraints, num_variables, qap, tw,
                                                      g1_generator, g2_generator, out);
     } catch (const std::bad_alloc&) {
         return G16_ERR_OOM;

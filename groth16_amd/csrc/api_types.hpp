@@ -190,6 +190,7 @@ struct g16_circuit {
     std::vector<g16_circuit*> subs;   // multi-device context: the circuit replicated on every device (dc == nullptr)
     std::vector<DwmSlot> dist;        // multi-device context whose device count admits the distributed witness map
     uint64_t num_variables = 0;
+    int qap = G16_QAP_LIBSNARK;       // g16_qap the circuit was loaded for (DeviceCircuit::qap)
 };
 
 // The host-side half of a key: the eight fixed points the glue of prover.rs:76-131 reads and the multiples of delta_g1 / delta_g2

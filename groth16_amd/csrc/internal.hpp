@@ -90,7 +90,8 @@ struct Domain {
     Fr* g_pow = nullptr;     // g^k natural          (unit-level coset fft only; lazily built)
     Fr n_inv, zinv;          // 1/n ; 1/(g^n - 1)
 };
-template <class C> int domain_create(int log_n, hipStream_t st, Domain<C>** out);
+// coset_tables = false leaves s1_br and s2 out (a Circom circuit shifts by rho, not g, and owns that table itself)
+template <class C> int domain_create(int log_n, hipStream_t st, Domain<C>** out, bool coset_tables = true);
 template <class C> void domain_destroy(Domain<C>* d);
 template <class C> int domain_ensure_gpow(Domain<C>* d, hipStream_t st);
 
@@ -117,6 +118,9 @@ template <class C> int scale_by_table(typename C::Fr* data, const typename C::Fr
 // out[i] = scale * base^i for i < n, in the w*R' form of the 30-bit kernels (r30_form) or in the standard Montgomery form
 template <class C> int gen_power_table(typename C::Fr* out, size_t n, const typename C::Fr& base, const typename C::Fr& scale, bool r30_form,
                                        hipStream_t st);
+// out[i] = scale * base^bitrev(i) for i < 2^log_n, canonical, in the w*R' form: a pre-scale table for ntt_dif_dit_batch (like s1_br)
+template <class C> int gen_bitrev_power_table(typename C::Fr* out, int log_n, const typename C::Fr& base, const typename C::Fr& scale,
+                                              hipStream_t st);
 
 // ---- R1CS on device + witness map (witness_map.hip) -------------------------------------------
 template <class C>
@@ -133,6 +137,11 @@ struct DeviceCircuit {
     // sparse mat-vec of row block k starts as soon as the piece holding need_col[k] has landed (ZUpload below).
     static constexpr int Z_CHUNKS = 8;
     uint64_t need_col[Z_CHUNKS] = {};
+    // R1CSToQAP implementor the circuit was loaded for (g16_qap).  G16_QAP_CIRCOM: the C matrix is neither read nor held (row_ptr[2],
+    // col[2], val[2] stay null, need_col covers A and B), dom has no coset tables, and circom_pre = n^-1 rho^bitrev(i), rho the
+    // generator of the 2n-point domain (rho^2 = w), takes s1_br's place between the inverse and the forward transform
+    int qap = G16_QAP_LIBSNARK;
+    Fr* circom_pre = nullptr;
 };
 // a host assignment on its way to the device: witness_map_device issues the copies itself (in DeviceCircuit::Z_CHUNKS pieces on
 // `copy_stream`, one event each) and interleaves them with the row blocks of the mat-vec that each piece unlocks
@@ -143,6 +152,8 @@ struct ZUpload {
     int pieces = 0;                  // out: how many pieces were used
 };
 // d_z: full assignment on device; d_h: n Fr out (natural order).  Scratch comes from the arena.
+// Follows ck->qap: the Libsnark map (quotient coefficients) or the Circom map (A.B - C on the odd coset of the 2n-point domain; six
+// transforms, all under ntt_timers[0])
 // after the CSR upload: flag the unit coefficients in the DEVICE column indices (bit 31), see witness_map.hip
 template <class C> int mark_unit_coefficients(DeviceCircuit<C>* ck, hipStream_t st);
 // up != nullptr: d_z is an empty device buffer and the assignment still lies in host memory (ZUpload)
@@ -285,8 +296,11 @@ template <class F> size_t window_table_park_bytes(uint64_t n, int W);
 
 // ---- CRS generation (setup.hip) -------------------------------------------------------------------
 template <class C>
-int generate_parameters_device(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv,
+int generate_parameters_device(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int qap,
                                const g16_toxic_waste* tw, const uint64_t* g1_gen, const uint64_t* g2_gen, const g16_params_view* out);
+// QAP::h_query_scalars on the host, the code the generator itself runs: g16_h_query_len(qap, n) scalars
+template <class C>
+int h_query_scalars_host(int qap, uint64_t domain_size, const uint64_t* t, const uint64_t* delta_inverse, uint64_t* out);
 template <class C>
 int qap_evaluations_host(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, const uint64_t* t, uint64_t* a_out, uint64_t* b_out,
                          uint64_t* c_out, uint64_t* zt_out);

@@ -219,12 +219,16 @@ struct KeyLoader {
     static void circuit_free(DeviceCircuit<C>* dc) {
         if (!dc) return;
         for (int m = 0; m < 3; ++m) { (void)hipFree(dc->row_ptr[m]); (void)hipFree(dc->col[m]); (void)hipFree(dc->val[m]); }
+        (void)hipFree(dc->circom_pre);
         domain_destroy<C>(dc->dom);
         delete dc;
     }
 
+    // qap (g16_qap): the Circom reduction reads A and B only -- abc[2] is not looked at and nothing of it is held on the device
     static int circuit_load(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints, uint64_t num_variables,
-                            g16_circuit** out) {
+                            int qap, g16_circuit** out) {
+        if (qap != G16_QAP_LIBSNARK && qap != G16_QAP_CIRCOM) return G16_ERR_BAD_ARG;
+        const int n_mat = qap == G16_QAP_CIRCOM ? 2 : 3;
         if (num_inputs == 0 || num_variables < num_inputs) return G16_ERR_BAD_LENGTH;
         // D::new(num_constraints + num_inputs), r1cs_to_qap.rs:178-179
         const uint64_t need = num_constraints + num_inputs;
@@ -235,18 +239,23 @@ struct KeyLoader {
         }
         if (log_n > C::TWO_ADICITY) return G16_ERR_DEGREE_TOO_LARGE;
         if (log_n > 30) return G16_ERR_DEGREE_TOO_LARGE;  // 32-bit indices inside the kernels
+        if (qap == G16_QAP_CIRCOM && log_n + 1 > C::TWO_ADICITY) return G16_ERR_DEGREE_TOO_LARGE;   // the 2n-point domain of rho
         DeviceCircuit<C>* dc = new (std::nothrow) DeviceCircuit<C>();
         if (!dc) return G16_ERR_OOM;
         dc->num_inputs = num_inputs;
         dc->num_constraints = num_constraints;
         dc->num_variables = num_variables;
+        dc->qap = qap;
         auto fail = [&](int code) { circuit_free(dc); return code; };
-        for (int m = 0; m < 3; ++m) {
+        for (int m = 0; m < n_mat; ++m) {
             if (!abc[m].row_ptr) return fail(G16_ERR_BAD_ARG);
             // a malformed CSR would send spmv3_kernel out of bounds on the device: row_ptr must start at 0 and never decrease
             if (abc[m].row_ptr[0] != 0) return fail(G16_ERR_BAD_LENGTH);
             for (uint64_t i = 0; i < num_constraints; ++i)
                 if (abc[m].row_ptr[i] > abc[m].row_ptr[i + 1]) return fail(G16_ERR_BAD_LENGTH);
+            if (qap == G16_QAP_CIRCOM)   // spmv_circom_kernel counts a row's terms in 32 bits
+                for (uint64_t i = 0; i < num_constraints; ++i)
+                    if (abc[m].row_ptr[i + 1] - abc[m].row_ptr[i] >= ((uint64_t)1 << 32)) return fail(G16_ERR_BAD_LENGTH);
             const uint64_t nnz = abc[m].row_ptr[num_constraints];
             dc->nnz[m] = nnz;
             if (nnz && (!abc[m].col || !abc[m].val)) return fail(G16_ERR_BAD_ARG);
@@ -271,7 +280,7 @@ struct KeyLoader {
             uint64_t run = 0;
             for (int k = 0; k < ZC; ++k) {
                 const uint64_t r_lo = n_dom * (uint64_t)k / ZC, r_hi = n_dom * (uint64_t)(k + 1) / ZC;
-                for (int m = 0; m < 3; ++m) {
+                for (int m = 0; m < n_mat; ++m) {
                     const uint64_t a = std::min(r_lo, num_constraints), b = std::min(r_hi, num_constraints);
                     for (uint64_t e = abc[m].row_ptr[a]; e < abc[m].row_ptr[b]; ++e) run = std::max<uint64_t>(run, abc[m].col[e]);
                 }
@@ -281,11 +290,21 @@ struct KeyLoader {
         }
         int rc = mark_unit_coefficients<C>(dc, ctx->stream);
         if (rc) return fail(rc);
-        rc = domain_create<C>(log_n, ctx->stream, &dc->dom);
+        rc = domain_create<C>(log_n, ctx->stream, &dc->dom, /*coset_tables=*/qap == G16_QAP_LIBSNARK);
         if (rc) return fail(rc);
+        if (qap == G16_QAP_CIRCOM) {
+            // n^-1 rho^bitrev(i), rho = the generator of the 2n-point domain (rho^2 = the domain's w): this circuit's pre-scale
+            // between the inverse and the forward transform, in s1_br's place (which a Circom circuit's domain leaves out)
+            Fr rho = C::two_adic_root();
+            for (int k = log_n + 1; k < C::TWO_ADICITY; ++k) rho = rho.sqr();
+            if (hipMalloc((void**)&dc->circom_pre, ((size_t)1 << log_n) * sizeof(Fr)) != hipSuccess) return fail(G16_ERR_OOM);
+            rc = gen_bitrev_power_table<C>(dc->circom_pre, log_n, rho, Fr::from_u64((uint64_t)1 << log_n).inverse(), ctx->stream);
+            if (rc) return fail(rc);
+        }
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(G16_ERR_HIP);
         g16_circuit* h = new (std::nothrow) g16_circuit{C::CURVE_ID, ctx, dc, (uint64_t)1 << log_n};
         if (!h) return fail(G16_ERR_OOM);
+        h->qap = qap;
         *out = h;
         return G16_OK;
     }

@@ -526,7 +526,12 @@ int gen_power_table(typename C::Fr* out, size_t n, const typename C::Fr& base, c
 }
 
 template <class C>
-int domain_create(int log_n, hipStream_t st, Domain<C>** out) {
+int gen_bitrev_power_table(typename C::Fr* out, int log_n, const typename C::Fr& base, const typename C::Fr& scale, hipStream_t st) {
+    return gen_powers30<typename C::Fr>(out, (size_t)1 << log_n, base, scale, log_n, st);
+}
+
+template <class C>
+int domain_create(int log_n, hipStream_t st, Domain<C>** out, bool coset_tables) {
     typedef typename C::Fr Fr;
     if (log_n > C::TWO_ADICITY || log_n > 31) return G16_ERR_DEGREE_TOO_LARGE;
     Domain<C>* d = new Domain<C>();
@@ -555,16 +560,16 @@ int domain_create(int log_n, hipStream_t st, Domain<C>** out) {
     if (hipMalloc((void**)&d->tw_fwd, ntw * sizeof(TwE)) != hipSuccess) return fail(G16_ERR_OOM);
     if (hipMalloc((void**)&d->tw_inv, ntw * sizeof(TwE)) != hipSuccess) return fail(G16_ERR_OOM);
     if (hipMalloc((void**)&tw_tmp, ntw * sizeof(Fr)) != hipSuccess) return fail(G16_ERR_OOM);
-    if (hipMalloc((void**)&d->s1_br, n * sizeof(Fr)) != hipSuccess) return fail(G16_ERR_OOM);
-    if (hipMalloc((void**)&d->s2, n * sizeof(Fr)) != hipSuccess) return fail(G16_ERR_OOM);
+    if (coset_tables && hipMalloc((void**)&d->s1_br, n * sizeof(Fr)) != hipSuccess) return fail(G16_ERR_OOM);
+    if (coset_tables && hipMalloc((void**)&d->s2, n * sizeof(Fr)) != hipSuccess) return fail(G16_ERR_OOM);
     for (int dir = 0; dir < 2; ++dir) {
         if ((rc = gen_powers30<Fr>(tw_tmp, ntw, dir ? omega_inv : omega, Fr::one(), 0, st, log_n)) != G16_OK) return fail(rc);
         hipLaunchKernelGGL((tw_convert_kernel<typename Fr::Params>), dim3((unsigned)((ntw + 255) / 256)), dim3(256), 0, st, tw_tmp,
                            reinterpret_cast<TwE*>(dir ? d->tw_inv : d->tw_fwd), ntw);
         if (hipGetLastError() != hipSuccess) return fail(G16_ERR_HIP);
     }
-    if ((rc = gen_powers30<Fr>(d->s1_br, n, g, n_inv, log_n, st)) != G16_OK) return fail(rc);
-    if ((rc = gen_powers30<Fr>(d->s2, n, g_inv, n_inv, 0, st)) != G16_OK) return fail(rc);
+    if (coset_tables && (rc = gen_powers30<Fr>(d->s1_br, n, g, n_inv, log_n, st)) != G16_OK) return fail(rc);
+    if (coset_tables && (rc = gen_powers30<Fr>(d->s2, n, g_inv, n_inv, 0, st)) != G16_OK) return fail(rc);
     if (hipStreamSynchronize(st) != hipSuccess) return fail(G16_ERR_HIP);
     (void)hipFree(tw_tmp);
     *out = d;
@@ -587,7 +592,8 @@ void domain_destroy(Domain<C>* d) {
 }
 
 #define G16_INSTANTIATE_NTT(C)                                                                                     \
-    template int domain_create<C>(int, hipStream_t, Domain<C>**);                                                  \
+    template int domain_create<C>(int, hipStream_t, Domain<C>**, bool);                                            \
+    template int gen_bitrev_power_table<C>(typename C::Fr*, int, const typename C::Fr&, const typename C::Fr&, hipStream_t); \
     template void domain_destroy<C>(Domain<C>*);                                                                   \
     template int domain_ensure_gpow<C>(Domain<C>*, hipStream_t);                                                   \
     template int ntt_dif<C>(const Domain<C>*, typename C::Fr*, bool, hipStream_t);                                 \

@@ -109,6 +109,47 @@ struct Setup {
         return G16_OK;
     }
 
+    // QAP::h_query_scalars(n - 1, t, zt, delta_inverse) (generator.rs:168), n = 2^log_n.
+    //   Libsnark (r1cs_to_qap.rs:243-245): zt / delta * t^i, i < n - 1.
+    //   Circom: the odd-indexed entries of the size-2n inverse transform of delta^-1 t^i (i < 2n - 1, zero-padded) -- n scalars.  Each
+    //   entry is a geometric sum:  out[j] = delta^-1 (2n)^-1 (t^(2n-1) rho^j - 1) / (t rho^-j - 1),  rho the generator of the 2n-point
+    //   domain; one batch inversion, like the Lagrange coefficients above.  Undefined (0 / 0) when t = rho^j for an odd j.
+    static int h_query_scalars(int qap, int log_n, const Fr& t, const Fr& zt, const Fr& delta_inv, std::vector<Fr>& hs) {
+        const uint64_t n = (uint64_t)1 << log_n;
+        if (qap == G16_QAP_LIBSNARK) {
+            hs.resize(n - 1);
+            const Fr base = zt * delta_inv;
+            Fr p = Fr::one();
+            for (uint64_t i = 0; i + 1 < n; ++i) { hs[i] = base * p; p = p * t; }
+            return G16_OK;
+        }
+        if (qap != G16_QAP_CIRCOM) return G16_ERR_BAD_ARG;
+        if (log_n + 1 > C::TWO_ADICITY) return G16_ERR_DEGREE_TOO_LARGE;   // D::new(2n) fails
+        Fr rho = C::two_adic_root();
+        for (int k = log_n + 1; k < C::TWO_ADICITY; ++k) rho = rho.sqr();
+        const Fr rho_inv = rho.inverse(), w = rho.sqr(), w_inv = rho_inv.sqr();
+        const Fr t_top = t.pow_u64(2 * n - 1);
+        std::vector<Fr> den(n), pre(n);
+        hs.resize(n);
+        Fr rj = rho, rinvj = rho_inv, run = Fr::one();   // rho^j, rho^-j for j = 2k + 1
+        for (uint64_t k = 0; k < n; ++k) {
+            hs[k] = t_top * rj - Fr::one();
+            den[k] = t * rinvj - Fr::one();
+            if (den[k].is_zero()) return G16_ERR_BAD_ARG;
+            pre[k] = run;
+            run = run * den[k];
+            rj = rj * w;
+            rinvj = rinvj * w_inv;
+        }
+        Fr inv = run.inverse();
+        const Fr scale = delta_inv * Fr::from_u64(2 * n).inverse();
+        for (uint64_t k = n; k-- > 0;) {
+            hs[k] = hs[k] * (inv * pre[k]) * scale;
+            inv = inv * den[k];
+        }
+        return G16_OK;
+    }
+
     template <class F>
     static int batch_mul(const Affine<F>* d_table, const std::vector<Fr>& sc, Arena& arena, hipStream_t st, uint64_t* out, bool out_on_device) {
         typedef Affine<F> A;
@@ -128,24 +169,25 @@ struct Setup {
         return G16_OK;
     }
 
-    static int generate(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv,
+    static int generate(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int qap,
                         const g16_toxic_waste* tw, const uint64_t* g1_gen, const uint64_t* g2_gen, const g16_params_view* out) {
         const Fr alpha = load_fr(tw->alpha), beta = load_fr(tw->beta), gamma = load_fr(tw->gamma), delta = load_fr(tw->delta),
                  t = load_fr(tw->t);
         if (gamma.is_zero() || delta.is_zero()) return G16_ERR_UNEXPECTED_IDENTITY;   // generator.rs:110-111
+        if (qap != G16_QAP_LIBSNARK && qap != G16_QAP_CIRCOM) return G16_ERR_BAD_ARG;
         std::vector<Fr> a, b, c;
         Fr zt;
         uint64_t n = 0;
         G16_TRY(qap_evaluations(abc, ni, nc, nv, t, a, b, c, &zt, &n));
         const Fr gamma_inv = gamma.inverse(), delta_inv = delta.inverse();
-        std::vector<Fr> gabc(ni), l(nv - ni), hs(n - 1);
+        std::vector<Fr> gabc(ni), l(nv - ni), hs;
         for (uint64_t i = 0; i < ni; ++i) gabc[i] = (beta * a[i] + alpha * b[i] + c[i]) * gamma_inv;          // generator.rs:113-117
         for (uint64_t i = ni; i < nv; ++i) l[i - ni] = (beta * a[i] + alpha * b[i] + c[i]) * delta_inv;      // :119-123
         {
             std::vector<Fr>().swap(c);
-            const Fr base = zt * delta_inv;                                                                   // r1cs_to_qap.rs:243-245
-            Fr p = Fr::one();
-            for (uint64_t i = 0; i + 1 < n; ++i) { hs[i] = base * p; p = p * t; }
+            int log_n = 0;
+            while (((uint64_t)1 << log_n) < n) ++log_n;
+            G16_TRY(h_query_scalars(qap, log_n, t, zt, delta_inv, hs));                                       // generator.rs:168
         }
         arena.reset();
         Affine<Fq>* t1 = nullptr;
@@ -184,9 +226,25 @@ struct Setup {
 };
 
 template <class C>
-int generate_parameters_device(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv,
+int generate_parameters_device(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int qap,
                                const g16_toxic_waste* tw, const uint64_t* g1_gen, const uint64_t* g2_gen, const g16_params_view* out) {
-    return Setup<C>::generate(st, arena, abc, ni, nc, nv, tw, g1_gen, g2_gen, out);
+    return Setup<C>::generate(st, arena, abc, ni, nc, nv, qap, tw, g1_gen, g2_gen, out);
+}
+
+template <class C>
+int h_query_scalars_host(int qap, uint64_t domain_size, const uint64_t* t_, const uint64_t* delta_inverse, uint64_t* out) {
+    typedef typename C::Fr Fr;
+    if (domain_size == 0 || (domain_size & (domain_size - 1))) return G16_ERR_BAD_ARG;
+    int log_n = 0;
+    while (((uint64_t)1 << log_n) < domain_size) ++log_n;
+    if (log_n > C::TWO_ADICITY || log_n > 30) return G16_ERR_DEGREE_TOO_LARGE;
+    const Fr t = Setup<C>::load_fr(t_);
+    Fr tn = t;
+    for (int k = 0; k < log_n; ++k) tn = tn.sqr();
+    std::vector<Fr> hs;
+    G16_TRY(Setup<C>::h_query_scalars(qap, log_n, t, tn - Fr::one(), Setup<C>::load_fr(delta_inverse), hs));
+    if (!hs.empty()) memcpy(out, hs.data(), hs.size() * sizeof(Fr));
+    return G16_OK;
 }
 
 template <class C>
@@ -205,8 +263,9 @@ int qap_evaluations_host(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, ui
 }
 
 #define G16_INSTANTIATE_SETUP(C)                                                                                                        \
-    template int generate_parameters_device<C>(hipStream_t, Arena&, const g16_csr_view*, uint64_t, uint64_t, uint64_t,                  \
+    template int generate_parameters_device<C>(hipStream_t, Arena&, const g16_csr_view*, uint64_t, uint64_t, uint64_t, int,             \
                                                const g16_toxic_waste*, const uint64_t*, const uint64_t*, const g16_params_view*);       \
+    template int h_query_scalars_host<C>(int, uint64_t, const uint64_t*, const uint64_t*, uint64_t*);                                   \
     template int qap_evaluations_host<C>(const g16_csr_view*, uint64_t, uint64_t, uint64_t, const uint64_t*, uint64_t*, uint64_t*,      \
                                          uint64_t*, uint64_t*);
 G16_INSTANTIATE_SETUP(Bls12_381)

@@ -26,10 +26,17 @@ struct UnitApi {
         G16_TRY(Prover<C>::stage_assignment(ctx, z, n_assign, on_device, &d_z));
         Fr* d_h = nullptr;
         G16_TRY(ctx->arena.alloc_n(ck->dom->n, &d_h));
-        G16_TRY((witness_map_device<C>(ck, d_z, d_h, ctx->arena, ctx->stream)));
+        // the map alone between two events (g16_timings.witness_map_ms / ntt_ms, as g16_prove records them): neither the staging of a
+        // host assignment before it nor the download of h after it
+        ctx->t_ntt[0].used = ctx->t_ntt[1].used = false;
+        G16_TRY(ctx->t_wm.start(ctx->stream));
+        G16_TRY((witness_map_device<C>(ck, d_z, d_h, ctx->arena, ctx->stream, ctx->t_ntt)));
+        G16_TRY(ctx->t_wm.stop(ctx->stream));
         G16_HIP_TRY(hipMemcpyAsync(h_out, d_h, ck->dom->n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
         G16_HIP_TRY(hipStreamSynchronize(ctx->stream));
         drain.dismiss();
+        ctx->tm.witness_map_ms = ctx->t_wm.ms();
+        ctx->tm.ntt_ms = ctx->t_ntt[0].ms() + ctx->t_ntt[1].ms();
         return G16_OK;
     }
 

@@ -1,4 +1,5 @@
-// R1CS -> QAP witness map on gfx950: h = (A z * B z - C z) / Z over the coset.
+// R1CS -> QAP witness map on gfx950: h = (A z * B z - C z) / Z over the coset (LibsnarkReduction), and beside it the Circom
+// reduction's map (ark-circom's CircomReduction, restated from its published source): A z * B z - c on the odd coset of the 2n domain.
 //
 // Restates LibsnarkReduction::witness_map_from_matrices, /root/reference/src/r1cs_to_qap.rs:172-235
 // (row evaluation: evaluate_constraint, :28-67), with the seven size-n transforms of :201-232
@@ -63,10 +64,163 @@ __global__ void quotient_kernel(Fr* __restrict__ a, const Fr* __restrict__ b, co
     a[i] = (a[i] * b[i] - c[i]) * zinv;
 }
 
+// ---- Circom reduction ---------------------------------------------------------------------------------------------------
+// <M_row, z> of one CSR row, with the unit-coefficient fast path of spmv3_kernel
+template <class Fr>
+__device__ __forceinline__ Fr csr_row_dot(const uint64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, const Fr* __restrict__ val,
+                                          const Fr* __restrict__ z, uint64_t row) {
+    Fr acc = Fr::zero();
+    const Fr one = Fr::one();
+    // (a row has fewer than 2^32 terms -- g16_circuit_load_qap checks -- so the walk counts in one register)
+    const uint64_t b = row_ptr[row];
+    const uint32_t len = (uint32_t)(row_ptr[row + 1] - b);
+    col += b;
+    val += b;
+    for (uint32_t k = 0; k < len; ++k) {
+        const uint32_t c = col[k];
+        if (c >> 31) {
+            acc = acc + z[c & 0x7fffffffu];
+        } else {
+            const Fr coeff = val[k];
+            const Fr v = z[c];
+            acc = acc + ((coeff == one) ? v : v * coeff);
+        }
+    }
+    return acc;
+}
+
+// rows [row0, row0 + rows) of the Circom map's first two steps, one lane per row, each stored at its own row index:
+//   a = <A_row, z> (rows < nc), z[row - nc] (the num_inputs rows after them), 0 above;  b = <B_row, z> or 0;  c = a * b.
+// The C matrix is not read.  The two rows are walked one after the other by ONE copy of spmv3_kernel's loop, each sum parked in its
+// output slot, and c is the product of the two slots read back (the lane's own writes, 64 B per row beside a gather-bound walk).
+// Holding a in registers across b's walk instead costs 72 registers against spmv3_kernel's 62, the budget this kernel is held to
+// (tests/test_circom_kernel_resources.py); parked, a lane never holds more than that kernel's accumulator, coefficient and operand.
+template <class Fr>
+struct CircomSpmvArgs {
+    const uint64_t* row_ptr[2];
+    const uint32_t* col[2];
+    const Fr* val[2];
+    Fr* out[3];
+};
+template <class Fr>
+__global__ __launch_bounds__(256) void spmv_circom_kernel(CircomSpmvArgs<Fr> args, const Fr* __restrict__ z, uint64_t num_inputs, uint64_t nc, uint64_t row0,
+                                   uint64_t rows) {
+    // (a domain has at most 2^30 rows: 32-bit row indices, the only per-lane index alive across the walks)
+    const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
+    if (li >= rows) return;
+    const uint32_t row = (uint32_t)row0 + li;
+    if (row < nc) {
+#pragma unroll 1
+        for (int m = 0; m < 2; ++m) args.out[m][row] = csr_row_dot<Fr>(args.row_ptr[m], args.col[m], args.val[m], z, row);
+        args.out[2][row] = args.out[0][row] * args.out[1][row];
+    } else {
+        args.out[0][row] = (row - nc < num_inputs) ? z[row - nc] : Fr::zero();
+        args.out[1][row] = Fr::zero();
+        args.out[2][row] = Fr::zero();
+    }
+}
+
+// h = a * b - c, natural order, straight into d_h (inputs canonical, as the last DIT sweep's canonical_quick stores them)
+template <class Fr>
+__global__ void circom_h_kernel(Fr* __restrict__ h, const Fr* __restrict__ a, const Fr* __restrict__ b, const Fr* __restrict__ c, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    h[i] = a[i] * b[i] - c[i];
+}
+
+template <class C>
+static int launch_spmv_circom(const DeviceCircuit<C>* ck, const typename C::Fr* d_z, typename C::Fr* a, typename C::Fr* b, typename C::Fr* c,
+                              uint64_t row0, uint64_t rows, hipStream_t st) {
+    typedef typename C::Fr Fr;
+    if (!rows) return G16_OK;
+    CircomSpmvArgs<Fr> args;
+    for (int m = 0; m < 2; ++m) {
+        args.row_ptr[m] = ck->row_ptr[m];
+        args.col[m] = ck->col[m];
+        args.val[m] = ck->val[m];
+    }
+    args.out[0] = a; args.out[1] = b; args.out[2] = c;
+    hipLaunchKernelGGL((spmv_circom_kernel<Fr>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, args, d_z, ck->num_inputs,
+                       ck->num_constraints, row0, rows);
+    G16_LAUNCH_CHECK();
+    return G16_OK;
+}
+
+// The assignment is still on the host (full_assignment: &[F], prover.rs:33).  Everything after the mat-vec needs all of a, b, c,
+// but the mat-vec itself does not need all of z: piece by piece on the copy stream, and after each piece the row blocks it
+// unlocks (need_col, computed at load time over the matrices the circuit's map reads: circuits allocate their variables as they emit
+// constraints, so row block k mostly reads piece <= k -- exactly so for the benchmark's product chain; a circuit whose first row
+// reads the last variable simply gets no overlap).  Hides most of the mat-vec (0.44 ms at 2^22) behind the 2.4 ms a 128 MiB upload
+// takes at 55 GB/s; the rest of the proof -- every transform needs all of a, b, c, every sort all of z -- cannot start before the
+// last byte has landed.  launch_rows(row0, rows) enqueues the map's row kernel over that row range on st.
+template <class C, class LaunchRows>
+static int upload_pieces_and_rows(const DeviceCircuit<C>* ck, const typename C::Fr* d_z, size_t n, hipStream_t st, ZUpload* up, LaunchRows launch_rows) {
+    typedef typename C::Fr Fr;
+    constexpr int ZC = DeviceCircuit<C>::Z_CHUNKS;
+    const uint64_t nz = ck->num_variables;
+    const int pieces = (int)std::min<uint64_t>(4, std::max<uint64_t>(1, nz >> 16));   // >= 2 MiB per piece; four of them
+    up->pieces = pieces;
+    const uint64_t per = (nz + pieces - 1) / pieces;
+    // all the copies first, back to back (pinned memory: each call returns at once, the pieces follow each other on the copy
+    // engine with ~10 us between them; enqueued in turn with the launches they unlock the host's ~45 us per round of calls sat
+    // BETWEEN the copies and cost more than the overlap gave -- kernel + copy trace of round 5, profiles/r05_upload_timeline.txt)
+    for (int k = 0; k < pieces; ++k) {
+        const uint64_t lo = per * k, hi = std::min(nz, per * (k + 1));
+        if (hi > lo)
+            G16_HIP_TRY(hipMemcpyAsync(const_cast<Fr*>(d_z) + lo, static_cast<const Fr*>(up->host) + lo, (hi - lo) * sizeof(Fr),
+                                       hipMemcpyHostToDevice, up->copy_stream));
+        G16_HIP_TRY(hipEventRecord(up->landed[k], up->copy_stream));
+    }
+    int next_block = 0;
+    for (int k = 0; k < pieces; ++k) {
+        const uint64_t hi = std::min(nz, per * (k + 1));
+        int last_block = next_block;
+        while (last_block < ZC && (k == pieces - 1 || ck->need_col[last_block] < hi)) ++last_block;
+        if (last_block > next_block) {
+            const uint64_t r_lo = n * (uint64_t)next_block / ZC, r_hi = n * (uint64_t)last_block / ZC;
+            G16_HIP_TRY(hipStreamWaitEvent(st, up->landed[k], 0));
+            if (r_hi > r_lo) G16_TRY(launch_rows(r_lo, r_hi - r_lo));
+            next_block = last_block;
+        }
+    }
+    return G16_OK;
+}
+
+// CircomReduction::witness_map_from_matrices: rows (a, b, c = a b), then for each of a, b, c  ifft, * rho^i, fft  -- inverse DIF,
+// n^-1 rho^bitrev(i) (ck->circom_pre), forward DIT, the same fused chain as the Libsnark map's first six transforms -- and
+// h = a b - c: six transforms, no division by Z, no seventh transform.
+template <class C>
+static int witness_map_circom(const DeviceCircuit<C>* ck, const typename C::Fr* d_z, typename C::Fr* d_h, Arena& arena, hipStream_t st,
+                              EventTimer* ntt_timers, ZUpload* up) {
+    typedef typename C::Fr Fr;
+    const Domain<C>* dom = ck->dom;
+    const size_t n = dom->n;
+    Fr *a = nullptr, *b = nullptr, *c = nullptr;
+    G16_TRY(arena.alloc_n(n, &a));
+    G16_TRY(arena.alloc_n(n, &b));
+    G16_TRY(arena.alloc_n(n, &c));
+    Fr* outs[3] = {a, b, c};
+    if (!up) {
+        G16_TRY((launch_spmv_circom<C>(ck, d_z, a, b, c, 0, n, st)));
+    } else {
+        G16_TRY((upload_pieces_and_rows<C>(ck, d_z, n, st, up, [&](uint64_t r0, uint64_t rows) -> int { return launch_spmv_circom<C>(ck, d_z, a, b, c, r0, rows, st); })));
+    }
+    if (ntt_timers) {
+        ntt_timers[1].used = false;   // all six transforms are under the first timer
+        G16_TRY(ntt_timers[0].start(st));
+    }
+    if (dom->log_n > 0) G16_TRY((ntt_dif_dit_batch<C>(dom, outs, 3, /*dif_inverse=*/true, ck->circom_pre, st)));   // (one point: rho^0 = 1)
+    if (ntt_timers) G16_TRY(ntt_timers[0].stop(st));
+    hipLaunchKernelGGL((circom_h_kernel<Fr>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_h, a, b, c, n);
+    G16_LAUNCH_CHECK();
+    return G16_OK;
+}
+
 template <class C>
 int witness_map_device(const DeviceCircuit<C>* ck, const typename C::Fr* d_z, typename C::Fr* d_h, Arena& arena, hipStream_t st,
                        EventTimer* ntt_timers, ZUpload* up) {
     typedef typename C::Fr Fr;
+    if (ck->qap == G16_QAP_CIRCOM) return witness_map_circom<C>(ck, d_z, d_h, arena, st, ntt_timers, up);
     const Domain<C>* dom = ck->dom;
     const size_t n = dom->n;
     Fr *a = nullptr, *b = nullptr, *c = nullptr;
@@ -86,43 +240,12 @@ int witness_map_device(const DeviceCircuit<C>* ck, const typename C::Fr* d_z, ty
                            ck->num_constraints, (uint64_t)0, (uint64_t)1, (uint64_t)n, 0, (uint64_t)0);
         G16_LAUNCH_CHECK();
     } else {
-        // The assignment is still on the host (full_assignment: &[F], prover.rs:33).  Everything after the mat-vec needs all of a, b, c,
-        // but the mat-vec itself does not need all of z: piece by piece on the copy stream, and after each piece the row blocks it
-        // unlocks (need_col, computed at load time: circuits allocate their variables as they emit constraints, so row block k
-        // mostly reads piece <= k -- exactly so for the benchmark's product chain; a circuit whose first row reads the last variable
-        // simply gets no overlap).  Hides most of the mat-vec (0.44 ms at 2^22) behind the 2.4 ms a 128 MiB upload takes at 55 GB/s; the
-        // rest of the proof -- every transform needs all of a, b, c, every sort all of z -- cannot start before the last byte has landed.
-        constexpr int ZC = DeviceCircuit<C>::Z_CHUNKS;
-        const uint64_t nz = ck->num_variables;
-        const int pieces = (int)std::min<uint64_t>(4, std::max<uint64_t>(1, nz >> 16));   // >= 2 MiB per piece; four of them
-        up->pieces = pieces;
-        const uint64_t per = (nz + pieces - 1) / pieces;
-        // all the copies first, back to back (pinned memory: each call returns at once, the pieces follow each other on the copy
-        // engine with ~10 us between them; enqueued in turn with the launches they unlock the host's ~45 us per round of calls sat
-        // BETWEEN the copies and cost more than the overlap gave -- kernel + copy trace of round 5, profiles/r05_upload_timeline.txt)
-        for (int k = 0; k < pieces; ++k) {
-            const uint64_t lo = per * k, hi = std::min(nz, per * (k + 1));
-            if (hi > lo)
-                G16_HIP_TRY(hipMemcpyAsync(const_cast<Fr*>(d_z) + lo, static_cast<const Fr*>(up->host) + lo, (hi - lo) * sizeof(Fr),
-                                           hipMemcpyHostToDevice, up->copy_stream));
-            G16_HIP_TRY(hipEventRecord(up->landed[k], up->copy_stream));
-        }
-        int next_block = 0;
-        for (int k = 0; k < pieces; ++k) {
-            const uint64_t hi = std::min(nz, per * (k + 1));
-            int last_block = next_block;
-            while (last_block < ZC && (k == pieces - 1 || ck->need_col[last_block] < hi)) ++last_block;
-            if (last_block > next_block) {
-                const uint64_t r_lo = n * (uint64_t)next_block / ZC, r_hi = n * (uint64_t)last_block / ZC;
-                G16_HIP_TRY(hipStreamWaitEvent(st, up->landed[k], 0));
-                if (r_hi > r_lo) {
-                    hipLaunchKernelGGL((spmv3_kernel<Fr>), dim3((unsigned)((r_hi - r_lo + 255) / 256), 3), dim3(256), 0, st, args, d_z, ck->num_inputs,
-                                       ck->num_constraints, r_lo, (uint64_t)1, r_hi - r_lo, 0, r_lo);
-                    G16_LAUNCH_CHECK();
-                }
-                next_block = last_block;
-            }
-        }
+        G16_TRY((upload_pieces_and_rows<C>(ck, d_z, n, st, up, [&](uint64_t r0, uint64_t rows) -> int {
+            hipLaunchKernelGGL((spmv3_kernel<Fr>), dim3((unsigned)((rows + 255) / 256), 3), dim3(256), 0, st, args, d_z, ck->num_inputs,
+                               ck->num_constraints, r0, (uint64_t)1, rows, 0, r0);
+            G16_LAUNCH_CHECK();
+            return G16_OK;
+        })));
     }
     // ntt_timers (optional, two of them): the six transforms of :201-207,220-221, then the seventh (:232) with its un-permute
     if (ntt_timers) G16_TRY(ntt_timers[0].start(st));
@@ -205,6 +328,7 @@ void dwm_destroy(DistWm<C>* d) {
 template <class C>
 int dwm_create(const DeviceCircuit<C>* ck, int rank, int world, hipStream_t st, DistWm<C>** out) {
     typedef typename C::Fr Fr;
+    if (ck->qap != G16_QAP_LIBSNARK) return G16_ERR_BAD_ARG;   // the distributed map is the Libsnark map (no coset tables, no C matrix here)
     const int log_n = ck->dom->log_n;
     int lw = 0;
     while ((1 << lw) < world) ++lw;
@@ -333,7 +457,7 @@ template <class C>
 int mark_unit_coefficients(DeviceCircuit<C>* ck, hipStream_t st) {
     if (ck->num_variables >= (1ull << 31)) return G16_OK;
     for (int m = 0; m < 3; ++m) {
-        if (!ck->nnz[m]) continue;
+        if (!ck->nnz[m] || !ck->col[m]) continue;   // (a Circom circuit holds no C matrix)
         hipLaunchKernelGGL((mark_unit_kernel<typename C::Fr>), dim3((unsigned)((ck->nnz[m] + 255) / 256)), dim3(256), 0, st, ck->col[m], ck->val[m],
                            ck->nnz[m]);
         G16_LAUNCH_CHECK();

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .binding import (CURVE_ID, FQ_LIMBS, CsrViewC, ParamsViewC, PartialC, PkInfoC, PkViewC, ProofC, QueryC, TimingsC, ToxicWasteC, lib,
+from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CsrViewC, ParamsViewC, PartialC, PkInfoC, PkViewC, ProofC, QueryC, TimingsC, ToxicWasteC, lib,
                       ptr32, ptr64, u64p)
 
 _MODULUS_R = {
@@ -239,13 +239,22 @@ def _csr_views(m: "ConstraintMatrices"):
 
 
 class _DeviceCircuit:
-    def __init__(self, ctx: _Ctx, m: ConstraintMatrices):
+    def __init__(self, ctx: _Ctx, m: ConstraintMatrices, qap_id: int = QAP_LIBSNARK):
         self.ctx = ctx
         self.handle = C.c_void_p()
         self.num_variables = m.num_instance_variables + m.num_witness_variables
         views, self._keep = _csr_views(m)
-        ctx.lib.check(ctx.lib.c.g16_circuit_load(ctx.handle, views, m.num_instance_variables, m.num_constraints, self.num_variables,
-                                                 C.byref(self.handle)))
+        if qap_id == QAP_LIBSNARK:
+            ctx.lib.check(ctx.lib.c.g16_circuit_load(ctx.handle, views, m.num_instance_variables, m.num_constraints, self.num_variables,
+                                                     C.byref(self.handle)))
+        else:
+            ctx.lib.check(ctx.lib.c.g16_circuit_load_qap(ctx.handle, views, m.num_instance_variables, m.num_constraints, self.num_variables,
+                                                         qap_id, C.byref(self.handle)))
+
+    @property
+    def qap(self) -> int:
+        """g16_circuit_qap: the reduction the device copy was loaded for"""
+        return int(self.ctx.lib.c.g16_circuit_qap(self.handle))
 
     @property
     def domain_size(self) -> int:
@@ -257,26 +266,68 @@ class _DeviceCircuit:
             self.handle = C.c_void_p()
 
 
-class LibsnarkReduction:
-    """R1CSToQAP default reduction (src/r1cs_to_qap.rs:123-248), witness side only."""
+class R1CSToQAP:
+    """trait R1CSToQAP (src/r1cs_to_qap.rs:71-120): what the two reductions share.  Not a reduction itself -- Groth16(qap=...) takes one
+    of the two sibling classes below, which differ in QAP_ID alone."""
 
-    @staticmethod
-    def witness_map_from_matrices(prover: "Groth16", matrices: ConstraintMatrices, num_inputs: int, num_constraints: int,
+    QAP_ID: Optional[int] = None
+
+    @classmethod
+    def witness_map_from_matrices(cls, prover: "Groth16", matrices: ConstraintMatrices, num_inputs: int, num_constraints: int,
                                   full_assignment: np.ndarray) -> np.ndarray:
+        """the map on the GPU; `prover` must be a Groth16 over this reduction (the device circuit is loaded for one)"""
+        if prover.qap.QAP_ID != cls.QAP_ID:
+            raise ValueError(f"the prover was made for {prover.qap.__name__}, not {cls.__name__}")
         return prover.witness_map_from_matrices(matrices, num_inputs, num_constraints, full_assignment)
+
+    @classmethod
+    def h_query_len(cls, domain_size: int) -> int:
+        """bases in h_query for a domain of that size (g16_h_query_len)"""
+        return int(lib().c.g16_h_query_len(cls.QAP_ID, domain_size))
+
+    @classmethod
+    def h_query_scalars(cls, curve: str, domain_size: int, t: np.ndarray, delta_inverse: np.ndarray) -> np.ndarray:
+        """QAP::h_query_scalars(domain_size - 1, t, zt, delta_inverse) on the host (g16_host_h_query_scalars: the code setup runs;
+        zt = t^n - 1 is computed there): (h_query_len, 4) Montgomery limbs"""
+        out = np.zeros((cls.h_query_len(domain_size), 4), dtype=np.uint64)
+        lb = lib()
+        lb.check(lb.c.g16_host_h_query_scalars(CURVE_ID[curve], cls.QAP_ID, domain_size, ptr64(_c(t).reshape(4)),
+                                               ptr64(_c(delta_inverse).reshape(4)), ptr64(out) if out.size else ptr64(np.zeros(4, dtype=np.uint64))))
+        return out
+
+
+class LibsnarkReduction(R1CSToQAP):
+    """R1CSToQAP default reduction (src/r1cs_to_qap.rs:123-248): h = the coefficients of (A.B - C) / Z, h_query = n - 1 bases."""
+
+    QAP_ID = QAP_LIBSNARK
+
+
+class CircomReduction(R1CSToQAP):
+    """ark-circom's CircomReduction, the R1CSToQAP implementor snarkjs-compatible keys are made for (restated from its published
+    source, not pinned against it): h = the n evaluations of A.B - C on the odd coset of the 2n-point domain -- c = a .* b (the C
+    matrix is not read), each of a, b, c through ifft, * rho^i, fft, then a.b - c -- and h_query = n bases, the odd-indexed entries
+    of the size-2n inverse transform of delta^-1 t^i.  instance_map_with_evaluation is the Libsnark one.  One GPU per context:
+    a multi-device context and the distributed witness map refuse a Circom circuit."""
+
+    QAP_ID = QAP_CIRCOM
 
 
 class Groth16:
-    """``Groth16::<E, LibsnarkReduction>`` prover methods for E in {Bls12_381, Bn254} on one MI355X (``device=0``) or on
-    several GPUs of the node behind the same calls (``device=[0, 1, ...]``: the library shards the key and folds the partial sums).
+    """``Groth16::<E, QAP>`` prover methods for E in {Bls12_381, Bn254} and QAP in {LibsnarkReduction (the default), CircomReduction}
+    on one MI355X (``device=0``) or on several GPUs of the node behind the same calls (``device=[0, 1, ...]``: the library shards the
+    key and folds the partial sums; Libsnark only).  The reduction chosen here drives circuit loading, generate_parameters* / setup
+    and every create_proof* / prove.
 
     Device-resident copies of proving keys and constraint matrices are cached per object
     (they are per-circuit constants, like ``&pk`` in the reference)."""
 
-    def __init__(self, curve: str = "bls12_381", device=0):
+    def __init__(self, curve: str = "bls12_381", device=0, qap=LibsnarkReduction):
         if curve not in CURVE_ID:
             raise ValueError(f"unsupported curve {curve}")
+        if qap not in (LibsnarkReduction, CircomReduction):
+            raise ValueError("qap is LibsnarkReduction or CircomReduction")
         self.curve = curve
+        self.qap = qap
         self._ctx = _Ctx(curve, device)
         self._pks: Dict[Tuple[int, Tuple[int, int]], _DevicePk] = {}
         self._cks: Dict[int, _DeviceCircuit] = {}
@@ -290,12 +341,17 @@ class Groth16:
         object's proofs; keys and circuits are loaded -- and evicted -- through the owner only."""
         if owner.curve != self.curve:
             raise ValueError("the two provers are for different curves")
+        if owner.qap.QAP_ID != self.qap.QAP_ID:
+            raise ValueError("the two provers are for different reductions")
         self._owner = owner
 
     # -- handles -------------------------------------------------------------------------
     def _pk(self, pk: ProvingKey, num_inputs: int, shard=(0, 1), dist_h: bool = False) -> _DevicePk:
         if self._owner is not None:
             return self._owner._pk(pk, num_inputs, shard, dist_h)
+        if dist_h and self.qap is not LibsnarkReduction:
+            # the block-order gather takes n = len(h_query) + 1 and feeds the distributed map, which is the Libsnark one
+            raise ValueError("dist_h key shards (prove_partial_h, prove_partial_prepare(dist_h=True)) are for LibsnarkReduction only")
         key = (id(pk), shard) if not dist_h else (id(pk), shard, "dist_h")
         if key not in self._pks:
             if pk.curve != self.curve:
@@ -308,7 +364,7 @@ class Groth16:
         if self._owner is not None:
             return self._owner._ck(m)
         if id(m) not in self._cks:
-            self._cks[id(m)] = (m, _DeviceCircuit(self._ctx, m))
+            self._cks[id(m)] = (m, _DeviceCircuit(self._ctx, m, self.qap.QAP_ID))
         return self._cks[id(m)][1]
 
     def evict_pk(self, pk: ProvingKey, shard=(0, 1)):
@@ -351,7 +407,7 @@ class Groth16:
             n <<= 1
         g1 = lambda k: np.zeros((k, 2 * L), dtype=np.uint64)  # noqa: E731
         g2 = lambda k: np.zeros((k, 4 * L), dtype=np.uint64)  # noqa: E731
-        pk = ProvingKey(self.curve, g1(1), g1(1), g1(1), g2(1), g2(1), g1(nv), g1(nv), g2(nv), g1(n - 1), g1(nv - ni), g2(1), g1(ni))
+        pk = ProvingKey(self.curve, g1(1), g1(1), g1(1), g2(1), g2(1), g1(nv), g1(nv), g2(nv), g1(self.qap.h_query_len(n)), g1(nv - ni), g2(1), g1(ni))
         tw = ToxicWasteC()
         for name, v in (("alpha", alpha), ("beta", beta), ("gamma", gamma), ("delta", delta), ("t", t)):
             getattr(tw, name)[:] = [int(x) for x in _c(v).reshape(4)]
@@ -360,8 +416,13 @@ class Groth16:
                           ptr64(pk.gamma_abc_g1), vp(pk.a_query), vp(pk.b_g1_query), vp(pk.b_g2_query), vp(pk.h_query), vp(pk.l_query), 0)
         views, keep = _csr_views(matrices)   # `keep` owns the (possibly converted) arrays until the call returns
         lb = self._ctx.lib
-        lb.check(lb.c.g16_generate_parameters(self._ctx.handle, views, ni, matrices.num_constraints, nv, C.byref(tw),
-                                              ptr64(_c(g1_generator).reshape(-1)), ptr64(_c(g2_generator).reshape(-1)), C.byref(out)))
+        if self.qap.QAP_ID == QAP_LIBSNARK:
+            lb.check(lb.c.g16_generate_parameters(self._ctx.handle, views, ni, matrices.num_constraints, nv, C.byref(tw),
+                                                  ptr64(_c(g1_generator).reshape(-1)), ptr64(_c(g2_generator).reshape(-1)), C.byref(out)))
+        else:
+            lb.check(lb.c.g16_generate_parameters_qap(self._ctx.handle, views, ni, matrices.num_constraints, nv, self.qap.QAP_ID, C.byref(tw),
+                                                      ptr64(_c(g1_generator).reshape(-1)), ptr64(_c(g2_generator).reshape(-1)),
+                                                      C.byref(out)))
         return pk
 
     # -- generator.rs:20-45 (+ lib.rs:63-74 circuit_specific_setup) -------------------------------
@@ -392,7 +453,7 @@ class Groth16:
         while True:   # domain.sample_element_outside_domain(rng), generator.rs:90
             t = _rand_fr(self.curve, rng, nonzero=True)
             tv = int.from_bytes(t.tobytes(), "little") * rinv % p
-            if pow(tv, n, p) != 1:
+            if pow(tv, n, p) != 1 and (self.qap.QAP_ID == QAP_LIBSNARK or pow(tv, 2 * n, p) != 1):   # Circom: nor t = rho^odd
                 break
         alpha, beta, gamma, delta = (_rand_fr(self.curve, rng, nonzero=True) for _ in range(4))
         return self.generate_parameters_with_qap(matrices, alpha, beta, gamma, delta, rand_generator(False), rand_generator(True), t)
@@ -623,7 +684,7 @@ class Groth16:
         return self.create_proof_with_reduction_and_matrices(pk, _rand_fr(self.curve, rng), _rand_fr(self.curve, rng), matrices, num_inputs,
                                                              num_constraints, full_assignment)
 
-    # -- r1cs_to_qap.rs:172-235 --------------------------------------------------------------
+    # -- r1cs_to_qap.rs:172-235 (QAP::witness_map_from_matrices: this object's reduction) -------
     def witness_map_from_matrices(self, matrices: ConstraintMatrices, num_inputs: int, num_constraints: int,
                                   full_assignment: np.ndarray) -> np.ndarray:
         dck = self._ck(matrices)
@@ -898,14 +959,14 @@ class PipelinedProver:
     """Throughput mode on one GPU: two contexts over ONE device-resident key / circuit, two worker threads.  `submit` returns a
     `concurrent.futures.Future` of the proof; with two proofs in flight the witness map / sort of one and the reductions / host glue of
     the other run under each other's bucket passes (bench.py reports the effect as `pipelined`: +3.9 % proofs per second at 2^22).
-    Latency per proof roughly doubles -- use a plain `Groth16` when that matters."""
+    Latency per proof roughly doubles -- use a plain `Groth16` when that matters.  `qap` as for `Groth16`."""
 
-    def __init__(self, curve: str = "bls12_381", device: int = 0):
+    def __init__(self, curve: str = "bls12_381", device: int = 0, qap=LibsnarkReduction):
         import queue
         import threading
 
-        self._owner = Groth16(curve, device)
-        self._second = Groth16(curve, device)
+        self._owner = Groth16(curve, device, qap=qap)
+        self._second = Groth16(curve, device, qap=qap)
         self._second.share_device_data_of(self._owner)
         self._lock = threading.Lock()           # key / circuit loads go through the owner's caches: one at a time
         self._jobs: "queue.Queue" = queue.Queue()

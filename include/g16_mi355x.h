@@ -212,6 +212,24 @@ int g16_pk_get_info(const g16_pk* pk, g16_pk_info* out);
 /* num_variables = num_instance_variables + num_witness_variables (len of full_assignment) */
 int g16_circuit_load(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints,
                      uint64_t num_variables, g16_circuit** out);
+/* ---- the R1CS -> QAP reduction (trait R1CSToQAP, src/r1cs_to_qap.rs:71-120; Groth16<E, QAP>) ----
+ * G16_QAP_LIBSNARK: the reference's LibsnarkReduction -- h = coefficients of (A.B - C) / Z, h_query = domain_size - 1 bases.
+ * G16_QAP_CIRCOM:   ark-circom's CircomReduction (snarkjs-compatible keys), restated from its published source and NOT pinned
+ *                   against it: rows as above but c = a .* b (the C matrix is not read), each of a, b, c through ifft, times rho^i
+ *                   (rho the generator of the 2n-point domain, rho^2 = w), fft; h[i] = a[i] b[i] - c[i] -- the n evaluations of
+ *                   A.B - C on the odd coset, natural order, no division by Z.  h_query = domain_size bases, the odd-indexed
+ *                   entries of the size-2n inverse transform of delta^-1 t^i (i < 2n - 1).  G16_ERR_DEGREE_TOO_LARGE if 2n exceeds
+ *                   the field's two-adicity.
+ * g16_circuit_load is g16_circuit_load_qap with qap = 0.  A Circom circuit keeps A and B on the device only: abc[2] may be all-NULL.
+ * Refused with G16_ERR_BAD_ARG: a Circom circuit on a multi-device context, and g16_dwm_create over a Circom circuit (the multi-device
+ * key loader gathers h_query in the distributed map's block order before it knows the circuit).  Everything else -- g16_witness_map
+ * (still domain_size Fr out), g16_prove, g16_prove_partial over base-range and bucket-space shards, g16_prove_finalize -- follows the
+ * circuit's reduction.  A key must come from the same reduction: a Circom circuit proved with a Libsnark key of the same circuit
+ * passes the length rules (domain_size - 1 <= domain_size bases) and yields a proof the verifier rejects. */
+typedef enum { G16_QAP_LIBSNARK = 0, G16_QAP_CIRCOM = 1 } g16_qap;
+int g16_circuit_load_qap(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints,
+                         uint64_t num_variables, int qap, g16_circuit** out);
+int g16_circuit_qap(const g16_circuit* c); /* g16_qap of a loaded circuit; -1 for NULL */
 void g16_circuit_free(g16_circuit* c);
 uint64_t g16_circuit_domain_size(const g16_circuit* c);
 
@@ -289,7 +307,8 @@ int g16_diag_valu(g16_ctx* ctx, g16_diag* out);
 
 /* ---- unit-level entry points (parity tests, micro-benchmarks) ---- */
 
-/* h_out: domain_size Fr, natural order */
+/* h_out: domain_size Fr, natural order.  Leaves g16_timings.witness_map_ms / ntt_ms of this call behind (HIP events around the map
+ * alone: neither the staging of a host assignment nor the download of h_out, which the call's wall time includes) */
 int g16_witness_map(g16_ctx* ctx, const g16_circuit* circuit, const uint64_t* full_assignment, uint64_t n_assign,
                     int on_device, uint64_t* h_out);
 /* bases affine, scalars Fr in Montgomery form (into_bigint is applied on the GPU, prover.rs:63-65);
@@ -330,7 +349,7 @@ typedef struct {
     uint64_t* gamma_abc_g1;                  /* num_inputs G1, host memory (VerifyingKey, data_structures.rs:39)  */
     uint64_t *a_query, *b_g1_query;          /* num_variables G1 each; entry 0 belongs to the constant-one variable */
     uint64_t* b_g2_query;                    /* num_variables G2                                                  */
-    uint64_t* h_query;                       /* domain_size - 1 G1                                                */
+    uint64_t* h_query;                       /* g16_h_query_len(qap, domain_size) G1: domain_size - 1 (Libsnark)   */
     uint64_t* l_query;                       /* num_variables - num_inputs G1                                     */
     uint32_t flags;
 } g16_params_view;
@@ -340,6 +359,19 @@ typedef struct {
 int g16_generate_parameters(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints,
                             uint64_t num_variables, const g16_toxic_waste* toxic_waste, const uint64_t* g1_generator,
                             const uint64_t* g2_generator, const g16_params_view* out);
+/* The same with the reduction chosen (g16_qap): g16_generate_parameters is this with qap = 0.  Circom: h_query has domain_size
+ * entries (QAP::h_query_scalars, generator.rs:168), abc[2] is still read (gamma_abc / l need C(t)); G16_ERR_BAD_ARG also if
+ * t = rho^j for an odd j, where the h scalars' closed form is undefined. */
+int g16_generate_parameters_qap(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints,
+                                uint64_t num_variables, int qap, const g16_toxic_waste* toxic_waste,
+                                const uint64_t* g1_generator, const uint64_t* g2_generator, const g16_params_view* out);
+/* entries of h_query: domain_size - 1 (Libsnark), domain_size (Circom); 0 for an unknown qap or domain_size == 0 */
+uint64_t g16_h_query_len(int qap, uint64_t domain_size);
+/* CPU only, the code the generator runs: QAP::h_query_scalars(domain_size - 1, t, zt, delta_inverse) -- g16_h_query_len Fr out.
+ * Libsnark: zt delta^-1 t^i with zt = t^n - 1 computed here.  G16_ERR_BAD_ARG: unknown qap, domain_size no power of two, Circom
+ * with t = rho^j for an odd j; G16_ERR_DEGREE_TOO_LARGE as the generator. */
+int g16_host_h_query_scalars(int curve, int qap, uint64_t domain_size, const uint64_t t[4], const uint64_t delta_inverse[4],
+                             uint64_t* out);
 /* CPU only: LibsnarkReduction::instance_map_with_evaluation (r1cs_to_qap.rs:120-170) -- a, b, c: num_variables Fr each */
 int g16_host_qap_evaluations(int curve, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints,
                              uint64_t num_variables, const uint64_t t[4], uint64_t* a_out, uint64_t* b_out,
