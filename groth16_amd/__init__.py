@@ -26,12 +26,12 @@ from .groth16 import (CircomReduction, ConstraintMatrices, Groth16, LibsnarkRedu
                       rerandomize_proof, shard_ranges)
 from .binding import MalformedVerifyingKey  # noqa: F401
 from .verifier import (PreparedVerifyingKey, VerifyingKey, check_subgroups_host, decompress_points_host, host_pairing, verify_proof_host,  # noqa: F401
-                       verify_proofs_aggregate_host)
+                       verify_proofs_aggregate_host, verify_proofs_aggregate_mixed_host)
 from .r1cs import AssignmentMissing, ConstraintSynthesizer, ConstraintSystem, LinearCombination, Variable, lc  # noqa: F401
 
 __all__ = [
     "Groth16", "LibsnarkReduction", "CircomReduction", "ConstraintMatrices", "ProvingKey", "Proof", "ShardedProver", "PipelinedProver", "G16Error", "SynthesisError",
     "PolynomialDegreeTooLarge", "UnexpectedIdentity", "lib", "ConstraintSystem", "ConstraintSynthesizer", "Variable", "LinearCombination",
-    "lc", "AssignmentMissing", "VerifyingKey", "PreparedVerifyingKey", "MalformedVerifyingKey", "verify_proof_host", "verify_proofs_aggregate_host", "check_subgroups_host", "host_pairing",
+    "lc", "AssignmentMissing", "VerifyingKey", "PreparedVerifyingKey", "MalformedVerifyingKey", "verify_proof_host", "verify_proofs_aggregate_host", "verify_proofs_aggregate_mixed_host", "check_subgroups_host", "host_pairing",
     "decompress_points_host",
 ]

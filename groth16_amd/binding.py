@@ -127,6 +127,7 @@ EXPORTS = [
     "g16_dev_fp30_op", "g16_host_fp30_op",
     "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
     "g16_decompress_points", "g16_decompress_proofs", "g16_host_decompress_points", "g16_verify_aggregate_bytes",
+    "g16_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed_gt",
     "g16_circuit_load_qap", "g16_circuit_qap", "g16_generate_parameters_qap", "g16_h_query_len", "g16_host_h_query_scalars",
 ]
 
@@ -256,6 +257,12 @@ class Lib:
         c.g16_decompress_proofs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p]
         c.g16_host_decompress_points.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_uint64, u64p, C.c_void_p]
         c.g16_verify_aggregate_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_void_p]
+        c.g16_verify_aggregate_mixed.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint64, u32p, u64p, C.c_uint64, u64p, C.c_uint64, u64p,
+                                                 C.c_int, C.c_void_p]
+        c.g16_host_verify_aggregate_mixed.argtypes = [C.c_int, C.POINTER(VkViewC), C.c_uint64, u32p, u64p, C.c_uint64, u64p, C.c_uint64, u64p,
+                                                      C.c_void_p]
+        c.g16_host_verify_aggregate_mixed_gt.argtypes = [C.c_int, C.POINTER(VkViewC), C.c_uint64, u32p, u64p, C.c_uint64, u64p, C.c_uint64, u64p,
+                                                         u64p, u64p]
         c.g16_dev_fp30_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_fp30_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
 

@@ -1,5 +1,6 @@
-// What verify.hip (one verify_proof per lane) and verify_aggregate.hip (one equation per batch) share: the prepared key, its
-// per-device part, the window-table form of prepare_inputs and the curve dispatch of the entry points.
+// What verify.hip (one verify_proof per lane), verify_aggregate.hip (one equation per batch under one key) and verify_mixed.hip (one
+// equation per batch that mixes keys) share: the prepared key, its per-device part, the window-table form of prepare_inputs, the
+// per-proof stage and the wave / workgroup reductions of the aggregate forms, and the curve dispatch of the entry points.
 #pragma once
 #include "internal.hpp"
 #include "pairing.hpp"
@@ -103,6 +104,93 @@ __device__ __host__ inline Aff1<C> prepare_inputs_tab(const typename C::G1A& gab
         }
     }
     return acc.to_affine();
+}
+
+// ---- shared by the aggregate forms (verify_aggregate.hip: one key per call, verify_mixed.hip: keys mixed in one call) ----------
+constexpr int AGG_MAX_PER_LANE = 4;   // proofs that may share a lane's accumulator
+
+// the caller's coefficients (none may be zero) or fresh ones from the operating system's generator (verify_aggregate.hip)
+int agg_coeffs(const uint64_t* coeffs, uint64_t n, std::vector<uint64_t>& own, const uint64_t** out);
+
+// The per-proof stage for cnt <= AGG_MAX_PER_LANE proofs: f = prod ML'(r_i A_i, B_i) (the loop value before finish_loop),
+// sc = sum r_i C_i.  false: a point is off its curve (f and sc are then not used).
+template <class C>
+G16_HD bool agg_terms(const uint64_t* proofs, const uint64_t* coeffs, int cnt, typename Pairing<C>::F12& f,
+                      XYZZ<typename Pairing<C>::F>& sc) {
+    typedef Pairing<C> PP;
+    typedef typename PP::F F;
+    constexpr int L = C::Fq::N / 2;
+    typename PP::LiveQ lq[AGG_MAX_PER_LANE];
+    typename PP::A1 pa[AGG_MAX_PER_LANE];
+    bool live[AGG_MAX_PER_LANE];
+    bool on_curve = true, any = false;
+    f = PP::F12::one();
+    sc = XYZZ<F>::identity();
+    for (int k = 0; k < cnt; ++k) {
+        const uint64_t* pr = proofs + (size_t)k * 8 * L;
+        const typename C::G1A A = ld_any<typename C::G1A>(pr);
+        const typename C::G2A B = ld_any<typename C::G2A>(pr + 2 * L);
+        const typename C::G1A Cc = ld_any<typename C::G1A>(pr + 6 * L);
+        live[k] = false;
+        if (!PP::g1_on_curve(A) || !PP::g2_on_curve(B) || !PP::g1_on_curve(Cc)) { on_curve = false; continue; }
+        const uint32_t r[4] = {(uint32_t)coeffs[2 * k], (uint32_t)(coeffs[2 * k] >> 32), (uint32_t)coeffs[2 * k + 1],
+                               (uint32_t)(coeffs[2 * k + 1] >> 32)};
+        if (!A.is_identity() && !B.is_identity()) {
+            const typename PP::A1 a = PP::g1_in(A);
+            const Aff1<C> ra = XYZZ<F>::from_affine(Aff1<C>{a.x, a.y}).mul_bits(r, 128).to_affine();
+            if (!ra.is_identity()) {   // r_i A_i = 0 only for an A outside the prime-order subgroup
+                live[k] = any = true;
+                pa[k] = {ra.x, ra.y};
+                lq[k].init(PP::g2_in(B));
+            }
+        }
+        if (!Cc.is_identity()) {
+            const typename PP::A1 c = PP::g1_in(Cc);
+            sc.add(XYZZ<F>::from_affine(Aff1<C>{c.x, c.y}).mul_bits(r, 128));
+        }
+    }
+    if (!on_curve) return false;
+    if (any)
+        PP::drive([&](int step) {
+                      for (int k = 0; k < cnt; ++k)
+                          if (live[k]) { const typename PP::Ell e = lq[k].next(step); PP::ell(f, e, pa[k]); }
+                  },
+                  [&](bool first) { if (!first) f = f.sqr(); });
+    return true;
+}
+
+template <class T>
+__device__ inline T wave_shfl_down(const T& v, int d) {
+    static_assert(sizeof(T) % 4 == 0, "moved as 32-bit words");
+    T r;
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(&v);
+    uint32_t* t = reinterpret_cast<uint32_t*>(&r);
+    // kept a loop over the words in scratch: unrolled, a whole Fq12 would sit in registers on either side of the move
+#pragma nounroll
+    for (int k = 0; k < (int)(sizeof(T) / 4); ++k) t[k] = (uint32_t)__shfl_down((int)s[k], d, 64);
+    return r;
+}
+
+// lane 0 ends with the product of the wave's f and the sum of its sc (the other lanes' values are not meaningful)
+template <class C>
+__device__ inline void wave_reduce(typename Pairing<C>::F12& f, XYZZ<typename Pairing<C>::F>& sc) {
+    for (int d = 32; d >= 1; d >>= 1) {
+        const typename Pairing<C>::F12 g = wave_shfl_down(f, d);
+        const XYZZ<typename Pairing<C>::F> h = wave_shfl_down(sc, d);
+        f = f * g;
+        sc.add(h);
+    }
+}
+
+template <class Fr>
+__device__ inline Fr agg_block_sum(Fr acc, Fr* sh) {
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (unsigned d = blockDim.x / 2; d >= 1; d >>= 1) {
+        if (threadIdx.x < d) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + d];
+        __syncthreads();
+    }
+    return sh[0];
 }
 
 }  // namespace g16

@@ -602,6 +602,36 @@ class Groth16:
             out[keep] = self.verify_proofs(pvk, flat[keep], [public_inputs_list[i] for i in keep])
         return out
 
+    def verify_aggregate_mixed_verdict(self, pvks, key_of, proofs, public_inputs_list, coeffs=None, check_subgroups: bool = False) -> int:
+        """g16_verify_aggregate_mixed: a batch whose proofs were made under several keys (proof i under pvks[key_of[i]], in any
+        order) in ONE randomised equation with one final exponentiation; the per-key pairs run on the GPU, one lane per key.
+        public_inputs_list[i] holds as many inputs as proof i's key takes.  Verdicts, coeffs and check_subgroups as
+        verify_aggregate_verdict.  A multi-device prover runs the call on its first device"""
+        from .verifier import verify_aggregate_mixed
+        return verify_aggregate_mixed(self._ctx, pvks, key_of, proofs, public_inputs_list, coeffs, check_subgroups)
+
+    def verify_proofs_aggregate_mixed(self, pvks, key_of, proofs, public_inputs_list, coeffs=None, check_subgroups: bool = False) -> bool:
+        return self.verify_aggregate_mixed_verdict(pvks, key_of, proofs, public_inputs_list, coeffs, check_subgroups) == 1
+
+    def verify_proofs_aggregate_mixed_or_each(self, pvks, key_of, proofs, public_inputs_list, check_subgroups: bool = False) -> np.ndarray:
+        """a bool per proof, in input order: the mixed aggregate check first, and only if it fails verify_verdicts once per key to
+        name the culprits.  With check_subgroups=True a proof with a point outside its subgroup (or off its curve) is answered
+        False"""
+        verdict = self.verify_aggregate_mixed_verdict(pvks, key_of, proofs, public_inputs_list, check_subgroups=check_subgroups)
+        n = len(public_inputs_list)
+        if verdict == 1:
+            return np.ones(n, dtype=bool)
+        from .verifier import _flat_proofs
+        flat = _flat_proofs(proofs, self.curve)
+        ko = np.asarray(key_of, dtype=np.int64).reshape(-1)
+        ok = self.check_proof_subgroups(flat) == 1 if check_subgroups else np.ones(n, dtype=bool)
+        out = np.zeros(n, dtype=bool)
+        for k in np.unique(ko):
+            idx = np.flatnonzero((ko == k) & ok)
+            if idx.size:
+                out[idx] = self.verify_verdicts(pvks[k], flat[idx], [public_inputs_list[i] for i in idx]) == 1
+        return out
+
     def check_subgroups(self, points, g2: bool = False) -> np.ndarray:
         """prime-order subgroup membership of affine points on the GPU (g16_check_subgroups): a uint8 per point -- 1 in the
         subgroup, 0 on the curve but outside it, 2 off the curve"""

@@ -1,13 +1,14 @@
 """Groth16 verification (src/verifier.rs:13-76, src/lib.rs:84-96) through the library's pairing: the batch form runs one proof per
 GPU lane (g16_verify_batch); ``verify_proof_host`` runs the same C++ templates on the CPU (g16_host_verify).  The aggregate form
-(g16_verify_aggregate / g16_host_verify_aggregate) checks a whole batch under one key in one randomised equation."""
+(g16_verify_aggregate / g16_host_verify_aggregate) checks a whole batch under one key in one randomised equation; the mixed form
+(g16_verify_aggregate_mixed / g16_host_verify_aggregate_mixed) does so for a batch whose proofs name their keys."""
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
 import numpy as np
 
-from .binding import CURVE_ID, FQ_LIMBS, VkViewC, lib, ptr64
+from .binding import CURVE_ID, FQ_LIMBS, VkViewC, lib, ptr32, ptr64
 
 
 def _c(a) -> np.ndarray:
@@ -288,6 +289,80 @@ def host_aggregate_gt(curve: str, vk, proofs, public_inputs_list, coeffs):
     lhs, rhs = np.zeros(12 * L, dtype=np.uint64), np.zeros(12 * L, dtype=np.uint64)
     lb = lib()
     lb.check(lb.c.g16_host_verify_aggregate_gt(*args, ptr64(lhs), ptr64(rhs)))
+    del keep
+    return lhs, rhs
+
+
+def _mixed_args(curve, key_of, proofs, public_inputs_list, coeffs):
+    """(key_of, flat proofs, n, ragged inputs as flat words, their count in Fr, coefficients) of a mixed batch.  A proof's input
+    vector is passed on as it is: whether its length suits its key is the library's check (G16_ERR_MALFORMED_VK)"""
+    flat = _flat_proofs(proofs, curve)
+    n = flat.shape[0]
+    ko = np.ascontiguousarray(np.asarray(key_of, dtype=np.int64).reshape(-1))
+    if ko.shape[0] != n:
+        raise ValueError("one key index per proof")
+    if n and (ko.min() < 0 or ko.max() >> 32):
+        raise ValueError("a key index is a 32-bit unsigned integer")
+    ko = ko.astype(np.uint32)
+    if len(public_inputs_list) != n:
+        raise ValueError("one public-input vector per proof")
+    if isinstance(public_inputs_list, np.ndarray) and public_inputs_list.dtype == np.uint64 and public_inputs_list.ndim == 3:
+        if public_inputs_list.shape[2] != 4:   # (n, l, 4): every key of the batch takes l inputs
+            raise ValueError("an Fr element is 4 words")
+        x = np.ascontiguousarray(public_inputs_list).reshape(-1)
+    else:
+        rows = [_c(x).reshape(-1, 4) if len(x) else np.zeros((0, 4), dtype=np.uint64) for x in public_inputs_list]
+        x = np.ascontiguousarray(np.concatenate(rows).reshape(-1)) if rows else np.zeros(0, dtype=np.uint64)
+    return ko, flat, n, x, x.size // 4, _flat_coeffs(coeffs, n)
+
+
+def verify_aggregate_mixed(ctx, pvks, key_of, proofs, public_inputs_list, coeffs=None, check_subgroups: bool = False) -> int:
+    """g16_verify_aggregate_mixed's verdict for proofs made under several keys (key_of[i] indexes pvks): 1 every proof holds under
+    its key, 0 the aggregate equation fails, 2 a point is off its curve, 3 (check_subgroups=True) a point is outside its subgroup"""
+    pvks = list(pvks)
+    curve = ctx.curve
+    ko, flat, n, x, n_public_total, r = _mixed_args(curve, key_of, proofs, public_inputs_list, coeffs)
+    handles = (C.c_void_p * max(len(pvks), 1))(*[p.handle if p is not None else None for p in pvks])
+    v = np.zeros(1, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_verify_aggregate_mixed(ctx.handle, handles, len(pvks), ptr32(ko) if n else None, ptr64(flat.reshape(-1)) if n else None, n,
+                                             ptr64(x) if x.size else None, n_public_total, ptr64(r.reshape(-1)) if r is not None and n else None,
+                                             int(bool(check_subgroups)), v.ctypes.data_as(C.c_void_p)))
+    return int(v[0])
+
+
+def _host_mixed_args(curve, vks, key_of, proofs, public_inputs_list, coeffs):
+    vkks = [as_vk(vk) for vk in vks]
+    ko, flat, n, x, n_public_total, r = _mixed_args(curve, key_of, proofs, public_inputs_list, coeffs)
+    views = [vk.view() for vk in vkks]
+    arr = (VkViewC * max(len(views), 1))(*[v for v, _ in views])
+    args = (CURVE_ID[curve], arr, len(views), ptr32(ko) if n else None, ptr64(flat.reshape(-1)) if n else None, n,
+            ptr64(x) if x.size else None, n_public_total, ptr64(r.reshape(-1)) if r is not None and n else None)
+    return args, (views, arr, ko, flat, x, r)
+
+
+def host_aggregate_mixed_verdict(curve: str, vks, key_of, proofs, public_inputs_list, coeffs=None) -> int:
+    """g16_host_verify_aggregate_mixed's verdict byte (1 / 0 / 2)"""
+    args, keep = _host_mixed_args(curve, vks, key_of, proofs, public_inputs_list, coeffs)
+    v = np.zeros(1, dtype=np.uint8)
+    lb = lib()
+    lb.check(lb.c.g16_host_verify_aggregate_mixed(*args, v.ctypes.data_as(C.c_void_p)))
+    del keep
+    return int(v[0])
+
+
+def verify_proofs_aggregate_mixed_host(curve: str, vks, key_of, proofs, public_inputs_list, coeffs=None) -> bool:
+    """the mixed-key aggregate equation on the CPU: True iff every proof of the batch is accepted under the key it names"""
+    return host_aggregate_mixed_verdict(curve, vks, key_of, proofs, public_inputs_list, coeffs) == 1
+
+
+def host_aggregate_mixed_gt(curve: str, vks, key_of, proofs, public_inputs_list, coeffs):
+    """(lhs, rhs): the two GT values the mixed-key equation compares, as arkworks' 12 Fq limbs"""
+    args, keep = _host_mixed_args(curve, vks, key_of, proofs, public_inputs_list, coeffs)
+    L = FQ_LIMBS[curve]
+    lhs, rhs = np.zeros(12 * L, dtype=np.uint64), np.zeros(12 * L, dtype=np.uint64)
+    lb = lib()
+    lb.check(lb.c.g16_host_verify_aggregate_mixed_gt(*args, ptr64(lhs), ptr64(rhs)))
     del keep
     return lhs, rhs
 

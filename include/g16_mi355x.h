@@ -491,6 +491,34 @@ int g16_host_verify_aggregate(int curve, const g16_vk_view* vk, const uint64_t* 
  * is off its curve, G16_ERR_UNEXPECTED_IDENTITY if the Miller product is 0 */
 int g16_host_verify_aggregate_gt(int curve, const g16_vk_view* vk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
                                  uint64_t num_public, const uint64_t* coeffs, uint64_t* lhs_fq12, uint64_t* rhs_fq12);
+/* The aggregate equation for a batch that MIXES verifying keys: key_of[i] < n_keys names the key of proof i,
+ *   FE(prod_i ML(r_i A_i, B_i) * prod_k [ML(S_IC_k, -gamma_k) * ML(S_C_k, -delta_k)]) == prod_k e(alpha_k, beta_k)^(s_k),
+ *   s_k = sum_{i in k} r_i, S_IC_k = sum_{i in k} r_i IC_i, S_C_k = sum_{i in k} r_i C_i -- one final exponentiation for the call,
+ * the per-key pairs and GT powers on the GPU, one lane per key.
+ * proofs: n x (A | B | C) affine in the caller's order; the keys may come in any order and with any group sizes, a key with no proof
+ * contributes nothing, and the same g16_pvk may be listed under several indices.
+ * public_inputs: the concatenation, in proof order, of every proof's inputs -- proof i brings n_gamma_abc(key_of[i]) - 1 Fr of four
+ * words; n_public_total: the caller's count of those Fr.  G16_ERR_MALFORMED_VK when it differs from the sum the keys imply (what
+ * num_public + 1 != n_gamma_abc is to g16_verify_aggregate).
+ * *verdict, its precedence (2 over 3 over 0 / 1), coeffs (explicit and non-zero, or NULL for getrandom(2)), the soundness contract
+ * and "n = 0 gives 1" exactly as g16_verify_aggregate / g16_verify_aggregate_checked; check_subgroups != 0 runs the membership tests
+ * first, on the same uploaded copy of the proofs and the same stream (verdict 3).  With n_keys = 1 the verdict is
+ * g16_verify_aggregate[_checked]'s on the same coefficients.
+ * G16_ERR_BAD_ARG: a key_of entry >= n_keys, n > 0 with n_keys = 0, a NULL key, a key of another curve or one loaded on another
+ * context, n >= 2^32, a zero coefficient.
+ * A multi-device ctx runs the whole call on its FIRST device (as g16_pairing does); a mixed batch is not cut over devices. */
+int g16_verify_aggregate_mixed(g16_ctx* ctx, const g16_pvk* const* pvks, uint64_t n_keys, const uint32_t* key_of, const uint64_t* proofs,
+                               uint64_t n, const uint64_t* public_inputs, uint64_t n_public_total, const uint64_t* coeffs,
+                               int check_subgroups, uint8_t* verdict);
+/* the same templates on the CPU (vks: n_keys views; verdicts 1 / 0 / 2) */
+int g16_host_verify_aggregate_mixed(int curve, const g16_vk_view* vks, uint64_t n_keys, const uint32_t* key_of, const uint64_t* proofs,
+                                    uint64_t n, const uint64_t* public_inputs, uint64_t n_public_total, const uint64_t* coeffs,
+                                    uint8_t* verdict);
+/* the two GT values that equation compares, for explicit coefficients and n >= 1; errors as g16_host_verify_aggregate_gt.  With
+ * n_keys = 1 they are byte-equal to g16_host_verify_aggregate_gt's. */
+int g16_host_verify_aggregate_mixed_gt(int curve, const g16_vk_view* vks, uint64_t n_keys, const uint32_t* key_of, const uint64_t* proofs,
+                                       uint64_t n, const uint64_t* public_inputs, uint64_t n_public_total, const uint64_t* coeffs,
+                                       uint64_t* lhs_fq12, uint64_t* rhs_fq12);
 
 /* ---- prime-order subgroup membership on the GPU (the point checks of Validate::Yes, without the byte formats) ----
  * Endomorphism tests with public constants: BLS12-381 G1 phi(P) = -[x^2]P, BLS12-381 G2 psi(Q) = [x]Q,

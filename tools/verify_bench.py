@@ -6,6 +6,7 @@
     python tools/verify_bench.py --curve bls12_381 --n 65536 --aggregate [--reps 5]
     python tools/verify_bench.py --curve bls12_381 --n 65536 --subgroup [--reps 5]
     python tools/verify_bench.py --curve bls12_381 --n 65536 --decompress [--reps 5] [--out profiles/decompress_mi355x.jsonl]
+    python tools/verify_bench.py --curve bls12_381 --n 65536 --mixed 1 64 4096 [--reps 3] [--out profiles/verify_mixed_mi355x.jsonl]
 
 --n: proofs per g16_verify_batch call (copies of rerandomised honest proofs of a small SYN circuit, one public input); the line
 reports the g16_pvk_load time, the best of --reps timed calls after one warm-up call (host clock around the call, which ends in a
@@ -19,7 +20,13 @@ points (uncompressed bytes, so no square root is in the figure) on the CPUs the 
 checked / aggregate and host / GPU check.  --decompress: on one batch of compressed proofs and in one process (a)
 g16_decompress_proofs, (b) the host's g16_deserialize_points(compressed, validate=0) over the same 3n points on the CPUs the process
 may use, (c) g16_verify_aggregate_bytes, (d) g16_verify_aggregate_checked on the already decoded proofs -- the floor of (c) -- and
-(e) the host path that (c) replaces: (b) followed by (d); --out appends the line to a file.  `spread` is (slowest - fastest) / fastest of the --reps timed calls.  Run each step under its own time limit."""
+(e) the host path that (c) replaces: (b) followed by (d); --out appends the line to a file.  --mixed K ..: a stream of n proofs that interleaves K verifying keys (key_of[i] = i mod K; four prepared keys with their own
+trapdoors listed in turn to reach K, which is the same work).  Per K, in one process: g16_verify_aggregate_mixed through the C ABI
+(best of --reps after a warm-up), and what the library offered before it for the same batch, already split by key outside the
+clock -- one g16_verify_aggregate per key, and one g16_verify_batch per key (each loop timed once after a warm-up call; at K = 4096
+they take seconds to minutes) -- and g16_verify_aggregate on n proofs under ONE key as the K = 1 yardstick.  `speedup` is the
+faster of the two loops over the mixed call; --out appends the lines to a file (default profiles/verify_mixed_mi355x.jsonl).
+`spread` is (slowest - fastest) / fastest of the --reps timed calls.  Run each step under its own time limit."""
 import argparse
 import json
 import os
@@ -44,8 +51,11 @@ def main():
     ap.add_argument("--aggregate", action="store_true")
     ap.add_argument("--subgroup", action="store_true")
     ap.add_argument("--decompress", action="store_true")
-    ap.add_argument("--out", help="append the JSON line of --decompress to this file")
+    ap.add_argument("--mixed", type=int, nargs="+", metavar="K", help="numbers of keys to interleave in one batch")
+    ap.add_argument("--out", help="append the JSON line of --decompress / the lines of --mixed to this file")
     a = ap.parse_args()
+    if a.mixed:
+        return mixed(a)
     vk, proofs, x, cp = oracle_case(a.curve)
     L = cp.fq_limbs64
     if a.host:
@@ -175,6 +185,68 @@ def decompress(a, vk, flat, xs, L):
     if a.out:
         with open(a.out, "a") as f:
             f.write(line + "\n")
+
+
+def mixed(a):
+    import ctypes as C
+
+    from groth16_amd.binding import lib, ptr32, ptr64
+    from mixed_key_cases import mixed_keys
+    cases = [mixed_keys(a.curve, 8)[k] for k in (0, 1, 2, 7)]   # three set-ups and a derived key, the same input count
+    n = a.n
+    out = a.out or os.path.join(ROOT, "profiles", "verify_mixed_mi355x.jsonl")
+    lb = lib()
+    with g.Groth16(a.curve, device=0) as prover:
+        prepared = [prover.prepare_verifying_key(c.vk) for c in cases]
+        single = np.ascontiguousarray(np.stack([cases[0].proofs[i % 2] for i in range(n)]))
+        single_x = np.ascontiguousarray(np.broadcast_to(cases[0].vectors[0].reshape(1, -1, 4), (n,) + cases[0].vectors[0].reshape(-1, 4).shape))
+        assert prover.verify_aggregate_verdict(prepared[0], single, single_x) == 1
+        one_key, one_key_spread = timed(lambda: prover.verify_aggregate_verdict(prepared[0], single, single_x), a.reps)
+        for K in a.mixed:
+            assert 1 <= K <= n
+            key_of = (np.arange(n) % K).astype(np.uint32)
+            which = key_of % len(cases)
+            flat = np.ascontiguousarray(np.stack([cases[w].proofs[(i // K) % 2] for i, w in enumerate(which)]))
+            x = np.ascontiguousarray(np.stack([cases[w].vectors[0].reshape(-1, 4) for w in which]))   # (n, l, 4): equal counts here
+            handles = (C.c_void_p * K)(*[prepared[k % len(cases)].handle for k in range(K)])
+            v = np.zeros(1, dtype=np.uint8)
+
+            def call():
+                lb.check(lb.c.g16_verify_aggregate_mixed(prover._ctx.handle, handles, K, ptr32(key_of), ptr64(flat.reshape(-1)), n, ptr64(x.reshape(-1)),
+                                                         x.size // 4, None, 0, v.ctypes.data_as(C.c_void_p)))
+                assert v[0] == 1, "the benchmark batch was rejected"
+
+            mix, mix_spread = timed(call, a.reps)
+            parts = [(prepared[k % len(cases)], np.ascontiguousarray(flat[k::K]), np.ascontiguousarray(x[k::K])) for k in range(K)]
+
+            def loop(fn):
+                fn(*parts[0])   # warm-up
+                t = time.perf_counter()
+                for done, part in enumerate(parts):
+                    fn(*part)
+                    if done % 512 == 511:
+                        print(f"  K = {K}: {done + 1} per-key calls", file=sys.stderr, flush=True)
+                return time.perf_counter() - t
+
+            def agg_one(pvk, fl, xs):
+                assert prover.verify_aggregate_verdict(pvk, fl, xs) == 1
+
+            def batch_one(pvk, fl, xs):
+                assert (prover.verify_verdicts(pvk, fl, xs) == 1).all()
+
+            agg_loop, batch_loop = loop(agg_one), loop(batch_one)
+            best = min(agg_loop, batch_loop)
+            line = json.dumps(dict(curve=a.curve, n=n, mode="mixed", keys=K, distinct_keys=min(K, len(cases)),
+                                   mixed_ms=round(mix * 1e3, 3), mixed_spread=round(mix_spread, 4), mixed_proofs_per_s=round(n / mix, 1),
+                                   per_key_aggregate_loop_ms=round(agg_loop * 1e3, 3), per_key_batch_loop_ms=round(batch_loop * 1e3, 3),
+                                   speedup=round(best / mix, 3), one_key_aggregate_ms=round(one_key * 1e3, 3),
+                                   one_key_aggregate_spread=round(one_key_spread, 4), mixed_over_one_key_aggregate=round(mix / one_key, 3),
+                                   reps=a.reps))
+            print(line, flush=True)
+            with open(out, "a") as f:
+                f.write(line + "\n")
+        for p in prepared:
+            p.close()
 
 
 if __name__ == "__main__":
