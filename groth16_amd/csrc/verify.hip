@@ -114,8 +114,8 @@ __global__ __launch_bounds__(VERIFY_BLOCK) void verify_batch_kernel(const typena
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 template <class T>
-int dev_upload(const T* src, size_t n, T** dst) {
-    G16_HIP_TRY(hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)));
+int dev_upload(DevBufs& bufs, const T* src, size_t n, T** dst) {
+    G16_TRY(bufs.get(dst, n));
     if (n) G16_HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
     return G16_OK;
 }
@@ -133,63 +133,55 @@ int pvk_load_dev(int device, const g16_vk_view* vk, PvkDev<C>* d, uint64_t* ab_o
     d->id_flags = (qs[0].is_identity() ? 1 : 0) | (qs[1].is_identity() ? 2 : 0);
     G1A alpha = ld<G1A>(vk->alpha_g1);
     G2A beta = ld<G2A>(vk->beta_g2);
-    G2A* d_q = nullptr;
-    G1A* d_alpha = nullptr;
-    G2A* d_beta = nullptr;
-    G1A* d_bases = nullptr;
-    uint64_t* d_out = nullptr;
-    int* d_status = nullptr;
-    int rc = [&]() -> int {
-        G16_TRY(dev_upload(qs, 2, &d_q));
-        G16_TRY(dev_upload(&alpha, 1, &d_alpha));
-        G16_TRY(dev_upload(&beta, 1, &d_beta));
-        G16_TRY(dev_upload(gabc, 1, &d->gabc0));
-        G16_TRY(dev_upload(gabc + 1, (size_t)nb, &d_bases));
-        G16_HIP_TRY(hipMalloc((void**)&d->lines, 2 * PP::NCOEFF * sizeof(typename PP::Ell)));
-        G16_HIP_TRY(hipMemset(d->lines, 0, 2 * PP::NCOEFF * sizeof(typename PP::Ell)));
-        G16_HIP_TRY(hipMalloc((void**)&d->tables, std::max<uint64_t>(nb, 1) * WINDOWS * DIGITS * sizeof(Aff1<C>)));
-        G16_HIP_TRY(hipMalloc((void**)&d->ab, sizeof(typename PP::F12)));
-        G16_HIP_TRY(hipMalloc((void**)&d_out, 12 * (C::Fq::N / 2) * sizeof(uint64_t)));
-        G16_HIP_TRY(hipMalloc((void**)&d_status, sizeof(int)));
-        pairing_prepare_kernel<C><<<1, 2>>>(d_q, d->lines);
+    DevBufs tmp;   // the call's temporaries, freed on every way out
+    G2A *d_q, *d_beta;
+    G1A *d_alpha, *d_bases;
+    uint64_t* d_out;
+    int* d_status;
+    G16_TRY(dev_upload(tmp, qs, 2, &d_q));
+    G16_TRY(dev_upload(tmp, &alpha, 1, &d_alpha));
+    G16_TRY(dev_upload(tmp, &beta, 1, &d_beta));
+    G16_HIP_TRY(hipMalloc((void**)&d->gabc0, sizeof(G1A)));
+    G16_HIP_TRY(hipMemcpy(d->gabc0, gabc, sizeof(G1A), hipMemcpyHostToDevice));
+    G16_TRY(dev_upload(tmp, gabc + 1, (size_t)nb, &d_bases));
+    G16_HIP_TRY(hipMalloc((void**)&d->lines, 2 * PP::NCOEFF * sizeof(typename PP::Ell)));
+    G16_HIP_TRY(hipMemset(d->lines, 0, 2 * PP::NCOEFF * sizeof(typename PP::Ell)));
+    G16_HIP_TRY(hipMalloc((void**)&d->tables, std::max<uint64_t>(nb, 1) * WINDOWS * DIGITS * sizeof(Aff1<C>)));
+    G16_HIP_TRY(hipMalloc((void**)&d->ab, sizeof(typename PP::F12)));
+    G16_TRY(tmp.get(&d_out, 12 * (C::Fq::N / 2)));
+    G16_TRY(tmp.get(&d_status, 1));
+    pairing_prepare_kernel<C><<<1, 2>>>(d_q, d->lines);
+    G16_LAUNCH_CHECK();
+    pairing_product_kernel<C><<<1, 1>>>(d_alpha, d_beta, 1, d_out, d->ab, d_status);
+    G16_LAUNCH_CHECK();
+    if (nb) {
+        const uint64_t lanes = nb * WINDOWS * DIGITS;
+        verify_window_table_kernel<C><<<(unsigned)((lanes + 127) / 128), 128>>>(d_bases, nb, d->tables);
         G16_LAUNCH_CHECK();
-        pairing_product_kernel<C><<<1, 1>>>(d_alpha, d_beta, 1, d_out, d->ab, d_status);
-        G16_LAUNCH_CHECK();
-        if (nb) {
-            const uint64_t lanes = nb * WINDOWS * DIGITS;
-            verify_window_table_kernel<C><<<(unsigned)((lanes + 127) / 128), 128>>>(d_bases, nb, d->tables);
-            G16_LAUNCH_CHECK();
-        }
-        G16_HIP_TRY(hipDeviceSynchronize());
-        int st = 0;
-        G16_HIP_TRY(hipMemcpy(&st, d_status, sizeof(int), hipMemcpyDeviceToHost));
-        if (st) return G16_ERR_UNEXPECTED_IDENTITY;
-        G16_HIP_TRY(hipMemcpy(ab_out, d_out, 12 * (C::Fq::N / 2) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        return G16_OK;
-    }();
-    (void)hipFree(d_q); (void)hipFree(d_alpha); (void)hipFree(d_beta); (void)hipFree(d_bases); (void)hipFree(d_out); (void)hipFree(d_status);
-    return rc;
+    }
+    G16_HIP_TRY(hipDeviceSynchronize());
+    int st = 0;
+    G16_HIP_TRY(hipMemcpy(&st, d_status, sizeof(int), hipMemcpyDeviceToHost));
+    if (st) return G16_ERR_UNEXPECTED_IDENTITY;
+    G16_HIP_TRY(hipMemcpy(ab_out, d_out, 12 * (C::Fq::N / 2) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return G16_OK;
 }
 
 template <class C>
 int verify_chunk(hipStream_t s, const PvkDev<C>* d, const uint64_t* proofs, const uint64_t* inputs, uint64_t num_public,
-                 const uint64_t* prepared, uint64_t n, uint8_t* verdicts, void** bufs) {
+                 const uint64_t* prepared, uint64_t n, uint8_t* verdicts, DevBufs& bufs) {
     constexpr int L = C::Fq::N / 2;
     G16_HIP_TRY(hipSetDevice(d->device));
-    uint64_t *d_proofs = nullptr, *d_inputs = nullptr, *d_prep = nullptr;
-    uint8_t* d_v = nullptr;
-    G16_HIP_TRY(hipMalloc((void**)&d_proofs, n * 8 * L * sizeof(uint64_t)));
-    bufs[0] = d_proofs;
-    G16_HIP_TRY(hipMalloc((void**)&d_v, n));
-    bufs[1] = d_v;
+    uint64_t *d_proofs, *d_inputs = nullptr, *d_prep = nullptr;
+    uint8_t* d_v;
+    G16_TRY(bufs.get(&d_proofs, n * 8 * L));
+    G16_TRY(bufs.get(&d_v, n));
     G16_HIP_TRY(hipMemcpyAsync(d_proofs, proofs, n * 8 * L * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     if (prepared) {
-        G16_HIP_TRY(hipMalloc((void**)&d_prep, n * 2 * L * sizeof(uint64_t)));
-        bufs[2] = d_prep;
+        G16_TRY(bufs.get(&d_prep, n * 2 * L));
         G16_HIP_TRY(hipMemcpyAsync(d_prep, prepared, n * 2 * L * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     } else if (num_public) {
-        G16_HIP_TRY(hipMalloc((void**)&d_inputs, n * num_public * 4 * sizeof(uint64_t)));
-        bufs[2] = d_inputs;
+        G16_TRY(bufs.get(&d_inputs, n * num_public * 4));
         G16_HIP_TRY(hipMemcpyAsync(d_inputs, inputs, n * num_public * 4 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     }
     verify_batch_kernel<C><<<(unsigned)((n + VERIFY_BLOCK - 1) / VERIFY_BLOCK), VERIFY_BLOCK, 0, s>>>(
@@ -199,21 +191,34 @@ int verify_chunk(hipStream_t s, const PvkDev<C>* d, const uint64_t* proofs, cons
     return G16_OK;
 }
 
+// one lane of the first device: the product of n_pairs pairings
+template <class C>
+int pairing_any(int device, const uint64_t* g1s, const uint64_t* g2s, uint64_t n_pairs, uint64_t* out) {
+    constexpr int L = C::Fq::N / 2;
+    G16_HIP_TRY(hipSetDevice(device));
+    DevBufs bufs;
+    uint64_t *d1, *d2, *dout;
+    int* dst;
+    G16_TRY(dev_upload(bufs, g1s, n_pairs * 2 * L, &d1));
+    G16_TRY(dev_upload(bufs, g2s, n_pairs * 4 * L, &d2));
+    G16_TRY(bufs.get(&dout, 12 * L));
+    G16_TRY(bufs.get(&dst, 1));
+    pairing_product_kernel<C><<<1, 1>>>(reinterpret_cast<const typename C::G1A*>(d1), reinterpret_cast<const typename C::G2A*>(d2), n_pairs, dout,
+                                        nullptr, dst);
+    G16_LAUNCH_CHECK();
+    G16_HIP_TRY(hipDeviceSynchronize());
+    int st = 0;
+    G16_HIP_TRY(hipMemcpy(&st, dst, sizeof(int), hipMemcpyDeviceToHost));
+    if (st) return G16_ERR_UNEXPECTED_IDENTITY;
+    G16_HIP_TRY(hipMemcpy(out, dout, 12 * L * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return G16_OK;
+}
+
 template <class C>
 int host_pairing(const uint64_t* g1s, const uint64_t* g2s, uint64_t n, uint64_t* out) {
-    typedef Pairing<C> PP;
-    typename PP::F12 f = PP::F12::one();
-    for (uint64_t k = 0; k < n; ++k) {
-        typename PP::LiveQ lq;
-        typename PP::A1 pa;
-        bool skip;
-        const typename C::G1A p = ld<typename C::G1A>(g1s + k * C::Fq::N);
-        const typename C::G2A q = ld<typename C::G2A>(g2s + k * 2 * C::Fq::N);
-        f = f * PP::miller_live(&p, &q, 1, &lq, &pa, &skip);
-    }
-    typename PP::F12 e;
-    if (!PP::final_exp(f, e)) return G16_ERR_UNEXPECTED_IDENTITY;
-    PP::store_gt(e, out);
+    typename Pairing<C>::F12 e;
+    if (!host_pairing_product<C>(g1s, g2s, n, e)) return G16_ERR_UNEXPECTED_IDENTITY;
+    Pairing<C>::store_gt(e, out);
     return G16_OK;
 }
 
@@ -252,12 +257,9 @@ int host_verify(const g16_vk_view* vk, const uint64_t* proof, const uint64_t* x,
     typename PP::A1 pa[3];
     bool skip[3];
     const typename PP::F12 f = PP::miller_live(ps, qs, 3, lq, pa, skip);
-    const G1A alpha = ld<G1A>(vk->alpha_g1);
-    const G2A beta = ld<G2A>(vk->beta_g2);
-    const typename PP::F12 g = PP::miller_live(&alpha, &beta, 1, lq, pa, skip);
     typename PP::F12 ef, eg;
     if (!PP::final_exp(f, ef)) { *verdict = 0; return G16_OK; }
-    if (!PP::final_exp(g, eg)) return G16_ERR_UNEXPECTED_IDENTITY;
+    G16_TRY(host_alpha_beta<C>(vk, eg));
     *verdict = PP::equal(ef, eg) ? 1 : 0;
     return G16_OK;
 }
@@ -269,38 +271,22 @@ template <class C>
 int verify_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, const uint64_t* inputs, uint64_t num_public,
                const uint64_t* prepared, uint64_t n, uint8_t* verdicts) {
     constexpr int L = C::Fq::N / 2;
-    int curve = 0;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    G16_TRY(ctx_devices(ctx, &curve, devs, streams));
+    CtxView cv;
+    G16_TRY(cv.load(ctx));
     const std::vector<PvkDev<C>>& pd = devs_of<C>(const_cast<g16_pvk*>(pvk));
-    if (pd.size() != devs.size()) return G16_ERR_BAD_ARG;   // the key was loaded on another context
-    const uint64_t nd = devs.size();
-    std::vector<void*> bufs(3 * nd, nullptr);
-    int rc = G16_OK;
-    for (uint64_t k = 0; k < nd && rc == G16_OK; ++k) {   // equal chunks, one per device, all enqueued before any wait
-        const uint64_t lo = n * k / nd, hi = n * (k + 1) / nd;
-        if (hi == lo) continue;
-        rc = verify_chunk<C>(streams[k], &pd[k], proofs + lo * 8 * L, inputs ? inputs + lo * num_public * 4 : nullptr, num_public,
-                             prepared ? prepared + lo * 2 * L : nullptr, hi - lo, verdicts + lo, &bufs[3 * k]);
-    }
-    for (uint64_t k = 0; k < nd; ++k) {
-        (void)hipSetDevice(devs[k]);
-        if (hipStreamSynchronize(streams[k]) != hipSuccess && rc == G16_OK) rc = G16_ERR_HIP;
-        for (int b = 0; b < 3; ++b) (void)hipFree(bufs[3 * k + b]);
-    }
-    return rc;
+    if (pd.size() != cv.devs.size()) return G16_ERR_BAD_ARG;   // the key was loaded on another context
+    return for_each_chunk(cv, n, [&](uint64_t k, uint64_t lo, uint64_t cnt, DevBufs& bufs) -> int {
+        return verify_chunk<C>(cv.streams[k], &pd[k], proofs + lo * 8 * L, inputs ? inputs + lo * num_public * 4 : nullptr, num_public,
+                               prepared ? prepared + lo * 2 * L : nullptr, cnt, verdicts + lo, bufs);
+    });
 }
 }  // namespace
 
 template <class C>
-static int pvk_load_all(g16_ctx* ctx, const g16_vk_view* vk, g16_pvk** out) {
-    int curve = 0;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    G16_TRY(ctx_devices(ctx, &curve, devs, streams));
+static int pvk_load_all(const CtxView& cv, const g16_vk_view* vk, g16_pvk** out) {
+    const std::vector<int>& devs = cv.devs;
     g16_pvk* p = new g16_pvk();
-    p->curve = curve;
+    p->curve = cv.curve;
     p->n_gamma_abc = vk->n_gamma_abc;
     constexpr int L = C::Fq::N / 2;
     p->gamma_g2.assign(vk->gamma_g2, vk->gamma_g2 + 4 * L);
@@ -320,11 +306,9 @@ extern "C" {
 
 int g16_pvk_load(g16_ctx* ctx, const g16_vk_view* vk, g16_pvk** out) {
     if (!ctx || !out || !vk_view_ok(vk)) return G16_ERR_BAD_ARG;
-    int curve = 0;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    G16_TRY(ctx_devices(ctx, &curve, devs, streams));
-    G16_VERIFY_DISPATCH(curve, pvk_load_all<CC>(ctx, vk, out));
+    CtxView cv;
+    G16_TRY(cv.load(ctx));
+    G16_VERIFY_DISPATCH(cv.curve, pvk_load_all<CC>(cv, vk, out));
 }
 
 void g16_pvk_free(g16_pvk* pvk) { delete pvk; }
@@ -352,39 +336,9 @@ int g16_verify_batch_prepared(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* 
 
 int g16_pairing(g16_ctx* ctx, const uint64_t* g1s, const uint64_t* g2s, uint64_t n_pairs, uint64_t* out_fq12) {
     if (!ctx || !out_fq12 || (n_pairs && (!g1s || !g2s))) return G16_ERR_BAD_ARG;
-    int curve = 0;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    G16_TRY(ctx_devices(ctx, &curve, devs, streams));
-    G16_HIP_TRY(hipSetDevice(devs[0]));
-    const int L = curve == G16_BLS12_381 ? 6 : 4;
-    uint64_t *d1 = nullptr, *d2 = nullptr, *dout = nullptr;
-    int* dst = nullptr;
-    int rc = [&]() -> int {
-        G16_HIP_TRY(hipMalloc((void**)&d1, std::max<uint64_t>(n_pairs, 1) * 2 * L * sizeof(uint64_t)));
-        G16_HIP_TRY(hipMalloc((void**)&d2, std::max<uint64_t>(n_pairs, 1) * 4 * L * sizeof(uint64_t)));
-        G16_HIP_TRY(hipMalloc((void**)&dout, 12 * L * sizeof(uint64_t)));
-        G16_HIP_TRY(hipMalloc((void**)&dst, sizeof(int)));
-        if (n_pairs) {
-            G16_HIP_TRY(hipMemcpy(d1, g1s, n_pairs * 2 * L * sizeof(uint64_t), hipMemcpyHostToDevice));
-            G16_HIP_TRY(hipMemcpy(d2, g2s, n_pairs * 4 * L * sizeof(uint64_t), hipMemcpyHostToDevice));
-        }
-        if (curve == G16_BLS12_381)
-            pairing_product_kernel<Bls12_381><<<1, 1>>>(reinterpret_cast<const Bls12_381::G1A*>(d1), reinterpret_cast<const Bls12_381::G2A*>(d2),
-                                                       n_pairs, dout, nullptr, dst);
-        else
-            pairing_product_kernel<Bn254><<<1, 1>>>(reinterpret_cast<const Bn254::G1A*>(d1), reinterpret_cast<const Bn254::G2A*>(d2), n_pairs,
-                                                   dout, nullptr, dst);
-        G16_LAUNCH_CHECK();
-        G16_HIP_TRY(hipDeviceSynchronize());
-        int st = 0;
-        G16_HIP_TRY(hipMemcpy(&st, dst, sizeof(int), hipMemcpyDeviceToHost));
-        if (st) return G16_ERR_UNEXPECTED_IDENTITY;
-        G16_HIP_TRY(hipMemcpy(out_fq12, dout, 12 * L * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        return G16_OK;
-    }();
-    (void)hipFree(d1); (void)hipFree(d2); (void)hipFree(dout); (void)hipFree(dst);
-    return rc;
+    CtxView cv;
+    G16_TRY(cv.load(ctx));
+    G16_VERIFY_DISPATCH(cv.curve, pairing_any<CC>(cv.devs[0], g1s, g2s, n_pairs, out_fq12));
 }
 
 int g16_host_pairing(int curve, const uint64_t* g1s, const uint64_t* g2s, uint64_t n_pairs, uint64_t* out_fq12) {

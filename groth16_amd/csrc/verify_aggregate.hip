@@ -14,14 +14,14 @@
 //   verify_agg_scalar_reduce_kernel  adds the partial sums.
 //   (g16_verify_aggregate_checked runs the membership kernels of verify_subgroup.hip first, over the same uploaded proofs and on
 //   the same stream: verdict 3 when a point is on its curve but outside its prime-order subgroup)
-//   agg_tail (host)            once per call, on the host templates (a lone GPU lane runs this chain about ten times slower than
-//                              one host thread): S_IC, the two pairs with -gamma and -delta, finish_loop, ONE final
+//   agg_key_tail, agg_finish   once per call, on the host templates (a lone GPU lane runs this chain about ten times slower than
+//   (host)                     one host thread): S_IC, the two pairs with -gamma and -delta, finish_loop, ONE final
 //                              exponentiation, and e(alpha, beta)^s as a cyclotomic power of the stored GT value -- chosen over a
 //                              fourth pair (-s alpha, beta) because it needs nothing new in the prepared key and keeps the
 //                              comparison the one verify_proof makes.
 // g16_host_verify_aggregate runs the same per-proof function and the same tail on the CPU.
-// The per-proof function (agg_terms), the wave reduction and the workgroup sum live in verify_common.hpp: verify_mixed.hip, the
-// form for batches that mix verifying keys, uses them too.
+// The per-proof function (agg_terms), the wave reductions, the workgroup sum, the membership stage, the verdict precedence, the host
+// tail and the chunk loop live in verify_common.hpp: verify_mixed.hip, the form for batches that mix verifying keys, uses them too.
 #include "verify_common.hpp"
 #include <cerrno>
 #include <sys/random.h>
@@ -88,9 +88,7 @@ __global__ __launch_bounds__(AGG_SCALAR_BLOCK) void verify_agg_scalar_kernel(con
     const Fr* x = reinterpret_cast<const Fr*>(inputs);
     Fr acc = Fr::zero();
     for (uint64_t i = (uint64_t)blockIdx.x * AGG_SCALAR_BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * AGG_SCALAR_BLOCK) {
-        uint32_t k[Fr::N] = {(uint32_t)coeffs[2 * i], (uint32_t)(coeffs[2 * i] >> 32), (uint32_t)coeffs[2 * i + 1],
-                             (uint32_t)(coeffs[2 * i + 1] >> 32)};
-        const Fr r = Fr::from_canonical(k);
+        const Fr r = coeff_fr<Fr>(coeffs + 2 * i);
         acc = acc + (j ? r * x[i * num_public + (j - 1)] : r);
     }
     const Fr sum = agg_block_sum(acc, sh);
@@ -107,51 +105,6 @@ __global__ __launch_bounds__(VERIFY_BLOCK) void verify_agg_scalar_reduce_kernel(
     for (uint64_t b = threadIdx.x; b < rows; b += VERIFY_BLOCK) acc = acc + partial[b * cols + blockIdx.x];
     const Fr sum = agg_block_sum(acc, sh);
     if (threadIdx.x == 0) out[blockIdx.x] = sum;
-}
-
-// ---- the once-per-batch tail (host) ------------------------------------------------------------------------------------------
-// f: product of the per-proof loop values (before finish_loop), sc = sum r_i C_i, st = (s, t_1 .. t_num_public).
-// lhs / rhs (ark form) are written when given.  verdict 1 / 0.
-template <class C>
-int agg_tail(const typename Pairing<C>::F12& f, const XYZZ<typename Pairing<C>::F>& sc, const typename C::Fr* st, uint64_t num_public,
-             const uint64_t* gamma_g2, const uint64_t* delta_g2, const uint64_t* gamma_abc_g1, const typename Pairing<C>::F12& ab,
-             uint8_t* verdict, uint64_t* lhs_out, uint64_t* rhs_out) {
-    typedef Pairing<C> PP;
-    typedef typename PP::F F;
-    typedef typename C::G1A G1A;
-    typedef typename C::G2A G2A;
-    constexpr int L = C::Fq::N / 2;
-    XYZZ<F> sic = XYZZ<F>::identity();
-    for (uint64_t j = 0; j <= num_public; ++j) {
-        const G1A gj = ld<G1A>(gamma_abc_g1 + j * 2 * L);
-        if (gj.is_identity()) continue;
-        const typename PP::A1 g = PP::g1_in(gj);
-        uint32_t k[8];
-        st[j].to_canonical(k);
-        sic.add(XYZZ<F>::from_affine(Aff1<C>{g.x, g.y}).mul_bits(k, 256));
-    }
-    const Aff1<C> pts[2] = {sic.to_affine(), sc.to_affine()};
-    G1A ps[2] = {G1A::identity(), G1A::identity()};
-    for (int k = 0; k < 2; ++k)
-        if (!pts[k].is_identity()) { ps[k].x = pts[k].x.to_std(); ps[k].y = pts[k].y.to_std(); }
-    G2A qs[2] = {ld<G2A>(gamma_g2).neg(), ld<G2A>(delta_g2).neg()};
-    typename PP::LiveQ lq[2];
-    typename PP::A1 pa[2];
-    bool skip[2];
-    const typename PP::F12 g = PP::miller_live(ps, qs, 2, lq, pa, skip);
-    uint32_t s[8];
-    st[0].to_canonical(s);
-    const typename PP::F12 rhs = PP::cyc_pow_bits(ab, s, 256);
-    typename PP::F12 lhs;
-    if (!PP::final_exp(PP::finish_loop(f) * g, lhs)) {
-        if (lhs_out) return G16_ERR_UNEXPECTED_IDENTITY;
-        *verdict = 0;
-        return G16_OK;
-    }
-    if (lhs_out) PP::store_gt(lhs, lhs_out);
-    if (rhs_out) PP::store_gt(rhs, rhs_out);
-    if (verdict) *verdict = PP::equal(lhs, rhs) ? 1 : 0;
-    return G16_OK;
 }
 
 // the caller's coefficients (none may be zero) or fresh ones from the operating system's generator
@@ -206,8 +159,7 @@ int host_verify_aggregate(const g16_vk_view* vk, const uint64_t* proofs, uint64_
         sc.add(ci);
     }
     for (uint64_t i = 0; i < n; ++i) {
-        const uint32_t k[Fr::N] = {(uint32_t)r[2 * i], (uint32_t)(r[2 * i] >> 32), (uint32_t)r[2 * i + 1], (uint32_t)(r[2 * i + 1] >> 32)};
-        const Fr ri = Fr::from_canonical(k);
+        const Fr ri = coeff_fr<Fr>(r + 2 * i);
         st[0] = st[0] + ri;
         for (uint64_t j = 0; j < num_public; ++j) st[j + 1] = st[j + 1] + ri * ld<Fr>(inputs + (i * num_public + j) * 4);
     }
@@ -216,15 +168,10 @@ int host_verify_aggregate(const g16_vk_view* vk, const uint64_t* proofs, uint64_
         *verdict = 2;
         return G16_OK;
     }
-    // e(alpha, beta) as g16_host_verify computes it
-    typename PP::LiveQ lq;
-    typename PP::A1 pa;
-    bool skip;
-    const typename C::G1A alpha = ld<typename C::G1A>(vk->alpha_g1);
-    const typename C::G2A beta = ld<typename C::G2A>(vk->beta_g2);
-    typename PP::F12 ab;
-    if (!PP::final_exp(PP::miller_live(&alpha, &beta, 1, &lq, &pa, &skip), ab)) return G16_ERR_UNEXPECTED_IDENTITY;
-    return agg_tail<C>(f, sc, st.data(), num_public, vk->gamma_g2, vk->delta_g2, vk->gamma_abc_g1, ab, verdict, lhs_out, rhs_out);
+    typename PP::F12 ab, g, rhs;
+    G16_TRY(host_alpha_beta<C>(vk, ab));
+    agg_key_tail<C>(sc, st.data(), num_public + 1, vk->gamma_g2, vk->delta_g2, vk->gamma_abc_g1, ab, g, rhs);
+    return agg_finish<C>(f, g, rhs, verdict, lhs_out, rhs_out);
 }
 
 // ---- device side of g16_verify_aggregate ---------------------------------------------------------------------------------------
@@ -251,17 +198,17 @@ inline int agg_per_lane(int device, uint64_t n) {
 // The byte input of g16_verify_aggregate_bytes: uploads n compressed proofs (a third of the affine form), decodes them into a device
 // buffer on the same stream and hands that buffer to aggregate_chunk; an undecodable point is the identity there.
 template <class C>
-int decode_chunk(hipStream_t s, int device, const uint8_t* bytes, uint64_t n, AggPartial<C>* out, DevBufs* bufs, uint64_t** d_resident) {
+int decode_chunk(hipStream_t s, int device, const uint8_t* bytes, uint64_t n, AggPartial<C>* out, DevBufs& bufs, uint64_t** d_resident) {
     constexpr int L = C::Fq::N / 2;
     constexpr uint64_t PROOF_BYTES = 4 * ((C::Fq::Params::BITS + 7) / 8);
     G16_HIP_TRY(hipSetDevice(device));
     uint8_t *d_bytes, *d_pt, *d_status;
     int* d_bad;
-    G16_TRY(bufs->get(&d_bytes, n * PROOF_BYTES));
-    G16_TRY(bufs->get(d_resident, n * 8 * L));
-    G16_TRY(bufs->get(&d_pt, 3 * n));
-    G16_TRY(bufs->get(&d_status, n));
-    G16_TRY(bufs->get(&d_bad, 1));
+    G16_TRY(bufs.get(&d_bytes, n * PROOF_BYTES));
+    G16_TRY(bufs.get(d_resident, n * 8 * L));
+    G16_TRY(bufs.get(&d_pt, 3 * n));
+    G16_TRY(bufs.get(&d_status, n));
+    G16_TRY(bufs.get(&d_bad, 1));
     G16_HIP_TRY(hipMemcpyAsync(d_bytes, bytes, n * PROOF_BYTES, hipMemcpyHostToDevice, s));
     G16_HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
     G16_TRY(decompress_enqueue_proofs(s, C::CURVE_ID, d_bytes, n, *d_resident, d_pt, d_status, d_bad));
@@ -273,7 +220,7 @@ int decode_chunk(hipStream_t s, int device, const uint8_t* bytes, uint64_t n, Ag
 // work on s)
 template <class C>
 int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uint64_t* d_resident, const uint64_t* inputs, uint64_t num_public,
-                    const uint64_t* coeffs, uint64_t n, bool check, AggPartial<C>* out, DevBufs* bufs) {
+                    const uint64_t* coeffs, uint64_t n, bool check, AggPartial<C>* out, DevBufs& bufs) {
     typedef Pairing<C> PP;
     typedef XYZZ<typename PP::F> G1X;
     typedef typename C::Fr Fr;
@@ -291,32 +238,23 @@ int aggregate_chunk(hipStream_t s, int device, const uint64_t* proofs, const uin
     Fr *d_part, *d_st;
     int* d_off;
     if (!d_resident) {
-        G16_TRY(bufs->get(&d_upload, n * 8 * L));
+        G16_TRY(bufs.get(&d_upload, n * 8 * L));
         d_proofs = d_upload;
     }
-    G16_TRY(bufs->get(&d_coeffs, n * 2));
-    G16_TRY(bufs->get(&d_inputs, n * num_public * 4));
-    G16_TRY(bufs->get(&d_f[0], blocks));
-    G16_TRY(bufs->get(&d_f[1], blocks2));
-    G16_TRY(bufs->get(&d_c[0], blocks));
-    G16_TRY(bufs->get(&d_c[1], blocks2));
-    G16_TRY(bufs->get(&d_part, sgrid * cols));
-    G16_TRY(bufs->get(&d_st, cols));
-    G16_TRY(bufs->get(&d_off, 1));
+    G16_TRY(bufs.get(&d_coeffs, n * 2));
+    G16_TRY(bufs.get(&d_inputs, n * num_public * 4));
+    G16_TRY(bufs.get(&d_f[0], blocks));
+    G16_TRY(bufs.get(&d_f[1], blocks2));
+    G16_TRY(bufs.get(&d_c[0], blocks));
+    G16_TRY(bufs.get(&d_c[1], blocks2));
+    G16_TRY(bufs.get(&d_part, sgrid * cols));
+    G16_TRY(bufs.get(&d_st, cols));
+    G16_TRY(bufs.get(&d_off, 1));
     if (!d_resident) G16_HIP_TRY(hipMemcpyAsync(d_upload, proofs, n * 8 * L * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     G16_HIP_TRY(hipMemcpyAsync(d_coeffs, coeffs, n * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     if (num_public) G16_HIP_TRY(hipMemcpyAsync(d_inputs, inputs, n * num_public * 4 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     G16_HIP_TRY(hipMemsetAsync(d_off, 0, sizeof(int), s));
-    if (check) {   // the membership tests over the copy of the proofs the Miller stage is about to read
-        uint8_t *d_pt, *d_flags;
-        int* d_sub;
-        G16_TRY(bufs->get(&d_pt, 3 * n));
-        G16_TRY(bufs->get(&d_flags, n));
-        G16_TRY(bufs->get(&d_sub, 1));
-        G16_HIP_TRY(hipMemsetAsync(d_sub, 0, sizeof(int), s));
-        G16_TRY(subgroup_enqueue_proofs(s, C::CURVE_ID, d_proofs, n, d_pt, d_flags, d_sub));
-        G16_HIP_TRY(hipMemcpyAsync(&out->off_subgroup, d_sub, sizeof(int), hipMemcpyDeviceToHost, s));
-    }
+    if (check) G16_TRY(agg_membership_enqueue(s, C::CURVE_ID, d_proofs, n, bufs, &out->off_subgroup));
     verify_agg_scalar_kernel<C><<<dim3(sgrid, (unsigned)cols), AGG_SCALAR_BLOCK, 0, s>>>(d_coeffs, d_inputs, num_public, n, d_part);
     G16_LAUNCH_CHECK();
     verify_agg_scalar_reduce_kernel<C><<<(unsigned)cols, VERIFY_BLOCK, 0, s>>>(d_part, sgrid, cols, d_st);
@@ -347,31 +285,19 @@ int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, cons
     std::vector<uint64_t> own;
     const uint64_t* r = nullptr;
     G16_TRY(agg_coeffs(coeffs, n, own, &r));
-    int curve = 0;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    G16_TRY(ctx_devices(ctx, &curve, devs, streams));
-    if (devs_of<C>(const_cast<g16_pvk*>(pvk)).size() != devs.size()) return G16_ERR_BAD_ARG;   // the key was loaded on another context
-    const uint64_t nd = devs.size();
+    CtxView cv;
+    G16_TRY(cv.load(ctx));
+    const uint64_t nd = cv.devs.size();
+    if (devs_of<C>(const_cast<g16_pvk*>(pvk)).size() != nd) return G16_ERR_BAD_ARG;   // the key was loaded on another context
     std::vector<AggPartial<C>> part(nd);
-    std::vector<DevBufs> bufs(nd);
-    std::vector<char> used(nd, 0);
-    int rc = G16_OK;
-    for (uint64_t k = 0; k < nd && rc == G16_OK; ++k) {   // equal chunks, one per device, all enqueued before any wait
-        const uint64_t lo = n * k / nd, hi = n * (k + 1) / nd;
-        if (hi == lo) continue;
+    std::vector<char> used(nd, 0);   // an empty chunk contributes nothing to the product
+    const int rc = for_each_chunk(cv, n, [&](uint64_t k, uint64_t lo, uint64_t cnt, DevBufs& bufs) -> int {
         used[k] = 1;
         uint64_t* d_resident = nullptr;
-        if (bytes) rc = decode_chunk<C>(streams[k], devs[k], bytes + lo * PROOF_BYTES, hi - lo, &part[k], &bufs[k], &d_resident);
-        if (rc == G16_OK)
-            rc = aggregate_chunk<C>(streams[k], devs[k], bytes ? nullptr : proofs + lo * 8 * L, d_resident,
-                                    inputs ? inputs + lo * num_public * 4 : nullptr, num_public, r + 2 * lo, hi - lo, check, &part[k], &bufs[k]);
-    }
-    for (uint64_t k = 0; k < nd; ++k) {
-        (void)hipSetDevice(devs[k]);
-        if (hipStreamSynchronize(streams[k]) != hipSuccess && rc == G16_OK) rc = G16_ERR_HIP;
-        bufs[k].release();
-    }
+        if (bytes) G16_TRY(decode_chunk<C>(cv.streams[k], cv.devs[k], bytes + lo * PROOF_BYTES, cnt, &part[k], bufs, &d_resident));
+        return aggregate_chunk<C>(cv.streams[k], cv.devs[k], bytes ? nullptr : proofs + lo * 8 * L, d_resident,
+                                  inputs ? inputs + lo * num_public * 4 : nullptr, num_public, r + 2 * lo, cnt, check, &part[k], bufs);
+    });
     if (rc != G16_OK) return rc;
     typename PP::F12 f = PP::F12::one();
     XYZZ<typename PP::F> sc = XYZZ<typename PP::F>::identity();
@@ -386,16 +312,19 @@ int aggregate_any(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, cons
         off_subgroup |= part[k].off_subgroup;
         undecodable |= part[k].undecodable;
     }
-    if (undecodable) { *verdict = 4; return G16_OK; }
-    if (off_curve || (off_subgroup & 2)) { *verdict = 2; return G16_OK; }
-    if (off_subgroup) { *verdict = 3; return G16_OK; }
-    return agg_tail<C>(f, sc, st.data(), num_public, pvk->gamma_g2.data(), pvk->delta_g2.data(), pvk->gamma_abc_g1.data(), PP::load_gt(pvk->ab),
-                       verdict, nullptr, nullptr);
+    if (const uint8_t v = agg_early_verdict(undecodable, off_curve, off_subgroup)) { *verdict = v; return G16_OK; }
+    typename PP::F12 g, rhs;
+    agg_key_tail<C>(sc, st.data(), num_public + 1, pvk->gamma_g2.data(), pvk->delta_g2.data(), pvk->gamma_abc_g1.data(), PP::load_gt(pvk->ab), g,
+                    rhs);
+    return agg_finish<C>(f, g, rhs, verdict, nullptr, nullptr);
 }
 
-int aggregate_bytes(g16_ctx* ctx, const g16_pvk* pvk, const uint8_t* proof_bytes, uint64_t n, const uint64_t* inputs, uint64_t num_public,
-                    const uint64_t* coeffs, uint8_t* verdict) {
-    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, nullptr, proof_bytes, n, inputs, num_public, coeffs, true, verdict)));
+int aggregate_call(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, const uint8_t* bytes, uint64_t n, const uint64_t* inputs,
+                   uint64_t num_public, const uint64_t* coeffs, bool check, uint8_t* verdict) {
+    if (!ctx || !pvk || !verdict || (n && !proofs && !bytes) || (n && num_public && !inputs)) return G16_ERR_BAD_ARG;
+    if (num_public + 1 != pvk->n_gamma_abc) return G16_ERR_MALFORMED_VK;
+    if (!n) { *verdict = 1; return G16_OK; }
+    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, bytes, n, inputs, num_public, coeffs, check, verdict)));
 }
 
 }  // namespace g16
@@ -404,18 +333,12 @@ extern "C" {
 
 int g16_verify_aggregate(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
                          uint64_t num_public, const uint64_t* coeffs, uint8_t* verdict) {
-    if (!ctx || !pvk || !verdict || (n && !proofs) || (n && num_public && !public_inputs)) return G16_ERR_BAD_ARG;
-    if (num_public + 1 != pvk->n_gamma_abc) return G16_ERR_MALFORMED_VK;
-    if (!n) { *verdict = 1; return G16_OK; }
-    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, nullptr, n, public_inputs, num_public, coeffs, false, verdict)));
+    return aggregate_call(ctx, pvk, proofs, nullptr, n, public_inputs, num_public, coeffs, false, verdict);
 }
 
 int g16_verify_aggregate_checked(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
                                  uint64_t num_public, const uint64_t* coeffs, uint8_t* verdict) {
-    if (!ctx || !pvk || !verdict || (n && !proofs) || (n && num_public && !public_inputs)) return G16_ERR_BAD_ARG;
-    if (num_public + 1 != pvk->n_gamma_abc) return G16_ERR_MALFORMED_VK;
-    if (!n) { *verdict = 1; return G16_OK; }
-    G16_VERIFY_DISPATCH(pvk->curve, (aggregate_any<CC>(ctx, pvk, proofs, nullptr, n, public_inputs, num_public, coeffs, true, verdict)));
+    return aggregate_call(ctx, pvk, proofs, nullptr, n, public_inputs, num_public, coeffs, true, verdict);
 }
 
 int g16_host_verify_aggregate(int curve, const g16_vk_view* vk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,

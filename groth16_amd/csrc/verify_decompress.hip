@@ -88,49 +88,34 @@ int decompress_enqueue_proofs(hipStream_t s, int curve, const uint8_t* d_bytes, 
     return G16_ERR_BAD_ARG;
 }
 
-// items: packed encodings (G1 or G2) or whole proofs (proofs = true); per item the affine form and one status byte, in input order.
-// Equal chunks, one per device of the context, all enqueued before any wait.
+// items: packed encodings (G1 or G2) or whole proofs (proofs = true); per item the affine form and one status byte, in input order
 template <class C>
 int decode_any(g16_ctx* ctx, bool proofs, int g2, const uint8_t* bytes, uint64_t n, uint64_t* out, uint8_t* status) {
     constexpr int L = C::Fq::N / 2;
     constexpr uint64_t FB = Decompress<C>::FQ_BYTES;
     const uint64_t in_sz = proofs ? 4 * FB : (g2 ? 2 * FB : FB), words = proofs ? 8 * L : (g2 ? 4 * L : 2 * L);
-    int curve = 0;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    G16_TRY(ctx_devices(ctx, &curve, devs, streams));
-    if (curve != C::CURVE_ID) return G16_ERR_BAD_ARG;
-    const uint64_t nd = devs.size();
-    std::vector<DevBufs> bufs(nd);
-    auto chunk = [&](uint64_t k, uint64_t lo, uint64_t cnt) -> int {
-        G16_HIP_TRY(hipSetDevice(devs[k]));
+    CtxView cv;
+    G16_TRY(cv.load(ctx));
+    if (cv.curve != C::CURVE_ID) return G16_ERR_BAD_ARG;
+    return for_each_chunk(cv, n, [&](uint64_t k, uint64_t lo, uint64_t cnt, DevBufs& bufs) -> int {
+        hipStream_t s = cv.streams[k];
+        G16_HIP_TRY(hipSetDevice(cv.devs[k]));
         uint8_t *d_in, *d_status, *d_pt;
         uint64_t* d_out;
-        G16_TRY(bufs[k].get(&d_in, cnt * in_sz));
-        G16_TRY(bufs[k].get(&d_out, cnt * words));
-        G16_TRY(bufs[k].get(&d_status, cnt));
-        G16_HIP_TRY(hipMemcpyAsync(d_in, bytes + lo * in_sz, cnt * in_sz, hipMemcpyHostToDevice, streams[k]));
+        G16_TRY(bufs.get(&d_in, cnt * in_sz));
+        G16_TRY(bufs.get(&d_out, cnt * words));
+        G16_TRY(bufs.get(&d_status, cnt));
+        G16_HIP_TRY(hipMemcpyAsync(d_in, bytes + lo * in_sz, cnt * in_sz, hipMemcpyHostToDevice, s));
         if (proofs) {
-            G16_TRY(bufs[k].get(&d_pt, 3 * cnt));
-            G16_TRY(enqueue_decode_proofs<C>(streams[k], d_in, cnt, d_out, d_pt, d_status, nullptr));
+            G16_TRY(bufs.get(&d_pt, 3 * cnt));
+            G16_TRY(enqueue_decode_proofs<C>(s, d_in, cnt, d_out, d_pt, d_status, nullptr));
         } else {
-            G16_TRY(enqueue_decode_points<C>(streams[k], g2, d_in, in_sz, 0, d_out, words, 0, 1, cnt, d_status));
+            G16_TRY(enqueue_decode_points<C>(s, g2, d_in, in_sz, 0, d_out, words, 0, 1, cnt, d_status));
         }
-        G16_HIP_TRY(hipMemcpyAsync(out + lo * words, d_out, cnt * words * sizeof(uint64_t), hipMemcpyDeviceToHost, streams[k]));
-        G16_HIP_TRY(hipMemcpyAsync(status + lo, d_status, cnt, hipMemcpyDeviceToHost, streams[k]));
+        G16_HIP_TRY(hipMemcpyAsync(out + lo * words, d_out, cnt * words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        G16_HIP_TRY(hipMemcpyAsync(status + lo, d_status, cnt, hipMemcpyDeviceToHost, s));
         return G16_OK;
-    };
-    int rc = G16_OK;
-    for (uint64_t k = 0; k < nd && rc == G16_OK; ++k) {
-        const uint64_t lo = n * k / nd, hi = n * (k + 1) / nd;
-        if (hi > lo) rc = chunk(k, lo, hi - lo);
-    }
-    for (uint64_t k = 0; k < nd; ++k) {
-        (void)hipSetDevice(devs[k]);
-        if (hipStreamSynchronize(streams[k]) != hipSuccess && rc == G16_OK) rc = G16_ERR_HIP;
-        bufs[k].release();
-    }
-    return rc;
+    });
 }
 
 template <class C>
@@ -149,13 +134,6 @@ int host_decode(int g2, const uint8_t* bytes, uint64_t n, uint64_t* out, uint8_t
         }
     }
     return G16_OK;
-}
-
-static int ctx_curve(const g16_ctx* ctx) {
-    int curve = -1;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    return ctx_devices(ctx, &curve, devs, streams) == G16_OK ? curve : -1;
 }
 
 }  // namespace g16
@@ -183,10 +161,7 @@ int g16_host_decompress_points(int curve, int g2, const uint8_t* bytes, uint64_t
 
 int g16_verify_aggregate_bytes(g16_ctx* ctx, const g16_pvk* pvk, const uint8_t* proof_bytes, uint64_t n, const uint64_t* public_inputs,
                                uint64_t num_public, const uint64_t* coeffs, uint8_t* verdict) {
-    if (!ctx || !pvk || !verdict || (n && !proof_bytes) || (n && num_public && !public_inputs)) return G16_ERR_BAD_ARG;
-    if (num_public + 1 != pvk->n_gamma_abc) return G16_ERR_MALFORMED_VK;
-    if (!n) { *verdict = 1; return G16_OK; }
-    return aggregate_bytes(ctx, pvk, proof_bytes, n, public_inputs, num_public, coeffs, verdict);
+    return aggregate_call(ctx, pvk, nullptr, proof_bytes, n, public_inputs, num_public, coeffs, true, verdict);
 }
 
 }  // extern "C"

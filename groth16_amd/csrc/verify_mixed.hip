@@ -5,8 +5,8 @@
 //     s_k = sum_{i in k} r_i,  t_kj = sum_{i in k} r_i x_ij,  S_IC_k = s_k gamma_abc_k[0] + sum_j t_kj gamma_abc_k[j + 1],
 //     S_C_k = sum_{i in k} r_i C_i.
 //
-// The live pair per proof does not depend on the key and is the per-proof function of verify_aggregate.hip (agg_terms); what is per
-// key runs on the GPU too, one lane per key, because K host tails do not scale.  ONE path for every K:
+// The live pair per proof does not depend on the key and is the per-proof function of the single-key form (agg_terms,
+// verify_common.hpp); what is per key runs on the GPU too, one lane per key, because K host tails do not scale.  ONE path for every K:
 //
 //   host                        counting sort of the proofs by key (the proofs themselves stay in the caller's order, the kernels
 //                               read them through `order`), per-key ranges, per-proof offsets into the ragged public inputs, the
@@ -67,22 +67,11 @@ __global__ __launch_bounds__(MIXED_SCALAR_BLOCK) void verify_mixed_scalar_kernel
     Fr acc = Fr::zero();
     for (uint64_t g = lo + threadIdx.x; g < hi; g += MIXED_SCALAR_BLOCK) {
         const uint64_t i = order[g];
-        uint32_t k[Fr::N] = {(uint32_t)coeffs[2 * i], (uint32_t)(coeffs[2 * i] >> 32), (uint32_t)coeffs[2 * i + 1],
-                             (uint32_t)(coeffs[2 * i + 1] >> 32)};
-        const Fr r = Fr::from_canonical(k);
+        const Fr r = coeff_fr<Fr>(coeffs + 2 * i);
         acc = acc + (j ? r * x[x_off[i] + (j - 1)] : r);
     }
     const Fr sum = agg_block_sum(acc, sh);
     if (threadIdx.x == 0) st[keys[kc.key].st_off + j] = sum;
-}
-
-// lane 0 ends with the product of the wave's values
-template <class C>
-__device__ inline void wave_product(typename Pairing<C>::F12& f) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const typename Pairing<C>::F12 g = wave_shfl_down(f, d);
-        f = f * g;
-    }
 }
 
 // lane g: the proof order[g], whose key is gkey[g] (non-decreasing in g).  f_out[workgroup]: the product of the wave's loop values;
@@ -133,10 +122,7 @@ __global__ __launch_bounds__(VERIFY_BLOCK) void verify_mixed_csum_kernel(const M
     const uint64_t m = mixed_records(lo, hi);
     G1X acc = G1X::identity();
     for (uint64_t r = threadIdx.x; r < m; r += VERIFY_BLOCK) acc.add(rec[off + r]);
-    for (int d = 32; d >= 1; d >>= 1) {
-        const G1X h = wave_shfl_down(acc, d);
-        acc.add(h);
-    }
+    wave_sum<C>(acc);
     if (threadIdx.x == 0) sc_out[blockIdx.x] = acc;
 }
 
@@ -162,21 +148,9 @@ __global__ __launch_bounds__(VERIFY_BLOCK, 2) void verify_mixed_key_kernel(const
             const typename PP::A1 p = PP::g1_in(g0);
             acc = XYZZ<F>::from_affine(Aff1<C>{p.x, p.y}).mul_bits(s, 256);
         }
-        for (uint64_t j = 0; j < num_public; ++j) {
-            uint32_t k[8];
-            t[j + 1].to_canonical(k);
-            for (int w = 0; w < WINDOWS; ++w) {
-                const uint32_t d = (k[w >> 3] >> (4 * (w & 7))) & 0xfu;
-                if (d) acc.add_affine(tables[(j * WINDOWS + (uint64_t)w) * DIGITS + d - 1]);
-            }
-        }
+        for (uint64_t j = 0; j < num_public; ++j) tab_accumulate<C>(acc, tables, j, t[j + 1]);
         const Aff1<C> ic = acc.to_affine();
-        if (!ic.is_identity() && !(keys[a].id_flags & 1)) {
-            const typename PP::A1 p = {ic.x, ic.y};
-            const typename PP::Ell* gl = keys[a].lines;
-            int idx = 0;
-            PP::drive([&](int) { PP::ell(f, gl[idx], p); ++idx; }, [&](bool first) { if (!first) f = f.sqr(); });
-        }
+        if (!ic.is_identity() && !(keys[a].id_flags & 1)) miller_prepared<C>(f, keys[a].lines, {ic.x, ic.y});
         rhs = PP::cyc_pow_bits(*keys[a].ab, s, 256);
     }
     wave_product<C>(f);
@@ -197,12 +171,7 @@ __global__ __launch_bounds__(VERIFY_BLOCK, 2) void verify_mixed_delta_kernel(con
     typename PP::F12 f = PP::F12::one();
     if (a < n_active) {
         const Aff1<C> c = sc[a].to_affine();
-        if (!c.is_identity() && !(keys[a].id_flags & 2)) {
-            const typename PP::A1 p = {c.x, c.y};
-            const typename PP::Ell* dl = keys[a].lines + PP::NCOEFF;
-            int idx = 0;
-            PP::drive([&](int) { PP::ell(f, dl[idx], p); ++idx; }, [&](bool first) { if (!first) f = f.sqr(); });
-        }
+        if (!c.is_identity() && !(keys[a].id_flags & 2)) miller_prepared<C>(f, keys[a].lines + PP::NCOEFF, {c.x, c.y});
     }
     wave_product<C>(f);
     if (threadIdx.x == 0) f_out[blockIdx.x] = f;
@@ -248,38 +217,6 @@ int mixed_layout(const std::vector<uint64_t>& num_public, const uint32_t* key_of
 }
 
 // ---- host form ------------------------------------------------------------------------------------------------------------------
-// what agg_tail does per key, without the final exponentiation: g = ML(S_IC, -gamma) ML(sc, -delta) (finished loops), rhs = ab^s
-template <class C>
-void mixed_key_tail(const XYZZ<typename Pairing<C>::F>& sc, const typename C::Fr* st, const g16_vk_view* vk,
-                    const typename Pairing<C>::F12& ab, typename Pairing<C>::F12& g, typename Pairing<C>::F12& rhs) {
-    typedef Pairing<C> PP;
-    typedef typename PP::F F;
-    typedef typename C::G1A G1A;
-    typedef typename C::G2A G2A;
-    constexpr int L = C::Fq::N / 2;
-    XYZZ<F> sic = XYZZ<F>::identity();
-    for (uint64_t j = 0; j < vk->n_gamma_abc; ++j) {
-        const G1A gj = ld<G1A>(vk->gamma_abc_g1 + j * 2 * L);
-        if (gj.is_identity()) continue;
-        const typename PP::A1 p = PP::g1_in(gj);
-        uint32_t k[8];
-        st[j].to_canonical(k);
-        sic.add(XYZZ<F>::from_affine(Aff1<C>{p.x, p.y}).mul_bits(k, 256));
-    }
-    const Aff1<C> pts[2] = {sic.to_affine(), sc.to_affine()};
-    G1A ps[2] = {G1A::identity(), G1A::identity()};
-    for (int k = 0; k < 2; ++k)
-        if (!pts[k].is_identity()) { ps[k].x = pts[k].x.to_std(); ps[k].y = pts[k].y.to_std(); }
-    G2A qs[2] = {ld<G2A>(vk->gamma_g2).neg(), ld<G2A>(vk->delta_g2).neg()};
-    typename PP::LiveQ lq[2];
-    typename PP::A1 pa[2];
-    bool skip[2];
-    g = PP::miller_live(ps, qs, 2, lq, pa, skip);
-    uint32_t s[8];
-    st[0].to_canonical(s);
-    rhs = PP::cyc_pow_bits(ab, s, 256);
-}
-
 template <class C>
 int host_verify_mixed(const g16_vk_view* vks, uint64_t n_keys, const uint32_t* key_of, const uint64_t* proofs, uint64_t n,
                       const uint64_t* inputs, uint64_t n_public_total, const uint64_t* coeffs, uint8_t* verdict, uint64_t* lhs_out,
@@ -311,8 +248,7 @@ int host_verify_mixed(const g16_vk_view* vks, uint64_t n_keys, const uint32_t* k
                 memcpy(pbuf + (size_t)c * 8 * L, proofs + i * 8 * L, 8 * L * sizeof(uint64_t));
                 rbuf[2 * c] = r[2 * i];
                 rbuf[2 * c + 1] = r[2 * i + 1];
-                const uint32_t w[Fr::N] = {(uint32_t)r[2 * i], (uint32_t)(r[2 * i] >> 32), (uint32_t)r[2 * i + 1], (uint32_t)(r[2 * i + 1] >> 32)};
-                const Fr ri = Fr::from_canonical(w);
+                const Fr ri = coeff_fr<Fr>(r + 2 * i);
                 st[0] = st[0] + ri;
                 for (uint64_t j = 0; j < num_public[k]; ++j) st[j + 1] = st[j + 1] + ri * ld<Fr>(inputs + (lay.x_off[i] + j) * 4);
             }
@@ -323,14 +259,9 @@ int host_verify_mixed(const g16_vk_view* vks, uint64_t n_keys, const uint32_t* k
             sc.add(ci);
         }
         if (!on_curve) continue;
-        typename PP::LiveQ lq;
-        typename PP::A1 pa;
-        bool skip;
-        const typename C::G1A alpha = ld<typename C::G1A>(vks[k].alpha_g1);
-        const typename C::G2A beta = ld<typename C::G2A>(vks[k].beta_g2);
         typename PP::F12 ab, gk, rk;
-        if (!PP::final_exp(PP::miller_live(&alpha, &beta, 1, &lq, &pa, &skip), ab)) return G16_ERR_UNEXPECTED_IDENTITY;
-        mixed_key_tail<C>(sc, st.data(), &vks[k], ab, gk, rk);
+        G16_TRY(host_alpha_beta<C>(&vks[k], ab));
+        agg_key_tail<C>(sc, st.data(), vks[k].n_gamma_abc, vks[k].gamma_g2, vks[k].delta_g2, vks[k].gamma_abc_g1, ab, gk, rk);
         g = g * gk;
         rhs = rhs * rk;
     }
@@ -339,16 +270,7 @@ int host_verify_mixed(const g16_vk_view* vks, uint64_t n_keys, const uint32_t* k
         *verdict = 2;
         return G16_OK;
     }
-    typename PP::F12 lhs;
-    if (!PP::final_exp(PP::finish_loop(f) * g, lhs)) {
-        if (lhs_out) return G16_ERR_UNEXPECTED_IDENTITY;
-        *verdict = 0;
-        return G16_OK;
-    }
-    if (lhs_out) PP::store_gt(lhs, lhs_out);
-    if (rhs_out) PP::store_gt(rhs, rhs_out);
-    if (verdict) *verdict = PP::equal(lhs, rhs) ? 1 : 0;
-    return G16_OK;
+    return agg_finish<C>(f, g, rhs, verdict, lhs_out, rhs_out);
 }
 
 // ---- device side of g16_verify_aggregate_mixed ---------------------------------------------------------------------------------
@@ -360,15 +282,13 @@ int mixed_any(g16_ctx* ctx, const g16_pvk* const* pvks, uint64_t n_keys, const u
     typedef XYZZ<typename PP::F> G1X;
     typedef typename C::Fr Fr;
     constexpr int L = C::Fq::N / 2;
-    int curve = 0;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    G16_TRY(ctx_devices(ctx, &curve, devs, streams));
+    CtxView cv;
+    G16_TRY(cv.load(ctx));
     std::vector<uint64_t> num_public(n_keys);
     for (uint64_t k = 0; k < n_keys; ++k) {
-        if (!pvks[k] || pvks[k]->curve != curve) return G16_ERR_BAD_ARG;
+        if (!pvks[k] || pvks[k]->curve != cv.curve) return G16_ERR_BAD_ARG;
         const std::vector<PvkDev<C>>& pd = devs_of<C>(const_cast<g16_pvk*>(pvks[k]));
-        if (pd.size() != devs.size() || pd[0].device != devs[0]) return G16_ERR_BAD_ARG;   // the key was loaded on another context
+        if (pd.size() != cv.devs.size() || pd[0].device != cv.devs[0]) return G16_ERR_BAD_ARG;   // the key was loaded on another context
         num_public[k] = pvks[k]->n_gamma_abc - 1;
     }
     MixedLayout lay;
@@ -398,8 +318,8 @@ int mixed_any(g16_ctx* ctx, const g16_pvk* const* pvks, uint64_t n_keys, const u
     const uint64_t blocks = (n + VERIFY_BLOCK - 1) / VERIFY_BLOCK, kw = (n_active + VERIFY_BLOCK - 1) / VERIFY_BLOCK;
     const uint64_t n_f = blocks + 2 * kw;   // the loop values: per workgroup of the per-proof stage, of the delta stage, of the key stage
 
-    const int device = devs[0];
-    hipStream_t s = streams[0], side = nullptr;
+    const int device = cv.devs[0];
+    hipStream_t s = cv.streams[0], side = nullptr;
     hipEvent_t ev_st = nullptr, ev_key = nullptr;
     DevBufs bufs;
     std::vector<F12> h_f, h_rhs;
@@ -450,16 +370,7 @@ int mixed_any(g16_ctx* ctx, const g16_pvk* const* pvks, uint64_t n_keys, const u
         G16_LAUNCH_CHECK();
         G16_HIP_TRY(hipEventRecord(ev_key, side));
         G16_HIP_TRY(hipMemcpyAsync(d_proofs, proofs, n * 8 * L * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        if (check) {   // the membership tests over the copy of the proofs the Miller stage is about to read
-            uint8_t *d_pt, *d_flags;
-            int* d_sub;
-            G16_TRY(bufs.get(&d_pt, 3 * n));
-            G16_TRY(bufs.get(&d_flags, n));
-            G16_TRY(bufs.get(&d_sub, 1));
-            G16_HIP_TRY(hipMemsetAsync(d_sub, 0, sizeof(int), s));
-            G16_TRY(subgroup_enqueue_proofs(s, C::CURVE_ID, d_proofs, n, d_pt, d_flags, d_sub));
-            G16_HIP_TRY(hipMemcpyAsync(&off_subgroup, d_sub, sizeof(int), hipMemcpyDeviceToHost, s));
-        }
+        if (check) G16_TRY(agg_membership_enqueue(s, C::CURVE_ID, d_proofs, n, bufs, &off_subgroup));
         verify_mixed_miller_kernel<C><<<(unsigned)blocks, VERIFY_BLOCK, 0, s>>>(d_proofs, d_coeffs, d_order, d_gkey, d_keys, n, d_f[0], d_rec, d_off);
         G16_LAUNCH_CHECK();
         verify_mixed_csum_kernel<C><<<(unsigned)n_active, VERIFY_BLOCK, 0, s>>>(d_keys, d_rec, d_sc);
@@ -490,8 +401,7 @@ int mixed_any(g16_ctx* ctx, const g16_pvk* const* pvks, uint64_t n_keys, const u
     if (ev_key) (void)hipEventDestroy(ev_key);
     if (side) (void)hipStreamDestroy(side);
     if (rc != G16_OK) return rc;
-    if (off_curve || (off_subgroup & 2)) { *verdict = 2; return G16_OK; }
-    if (off_subgroup) { *verdict = 3; return G16_OK; }
+    if (const uint8_t v = agg_early_verdict(0, off_curve, off_subgroup)) { *verdict = v; return G16_OK; }
     F12 f = F12::one(), rhs = F12::one();
     for (const F12& v : h_f) f = f * v;
     for (const F12& v : h_rhs) rhs = rhs * v;
@@ -513,11 +423,7 @@ int g16_verify_aggregate_mixed(g16_ctx* ctx, const g16_pvk* const* pvks, uint64_
                                uint64_t n, const uint64_t* public_inputs, uint64_t n_public_total, const uint64_t* coeffs,
                                int check_subgroups, uint8_t* verdict) {
     if (!ctx || !verdict || !mixed_args_ok(pvks, n_keys, key_of, proofs, n, public_inputs, n_public_total)) return G16_ERR_BAD_ARG;
-    int curve = 0;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    G16_TRY(ctx_devices(ctx, &curve, devs, streams));
-    G16_VERIFY_DISPATCH(curve, (mixed_any<CC>(ctx, pvks, n_keys, key_of, proofs, n, public_inputs, n_public_total, coeffs,
+    G16_VERIFY_DISPATCH(ctx_curve(ctx), (mixed_any<CC>(ctx, pvks, n_keys, key_of, proofs, n, public_inputs, n_public_total, coeffs,
                                               check_subgroups != 0, verdict)));
 }
 

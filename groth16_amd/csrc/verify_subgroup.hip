@@ -77,46 +77,31 @@ int subgroup_enqueue_proofs(hipStream_t s, int curve, const uint64_t* d_proofs, 
     return G16_ERR_BAD_ARG;
 }
 
-// items: packed points (words = 2 L or 4 L each) or whole proofs (proofs = true, 8 L words); one flag byte per item, in input order.
-// Equal chunks, one per device of the context, all enqueued before any wait.
+// items: packed points (words = 2 L or 4 L each) or whole proofs (proofs = true, 8 L words); one flag byte per item, in input order
 template <class C>
 int check_any(g16_ctx* ctx, bool proofs, int g2, const uint64_t* items, uint64_t n, uint8_t* flags) {
     constexpr int L = C::Fq::N / 2;
     const uint64_t words = proofs ? 8 * L : (g2 ? 4 * L : 2 * L);
-    int curve = 0;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    G16_TRY(ctx_devices(ctx, &curve, devs, streams));
-    if (curve != C::CURVE_ID) return G16_ERR_BAD_ARG;
-    const uint64_t nd = devs.size();
-    std::vector<DevBufs> bufs(nd);
-    auto chunk = [&](uint64_t k, uint64_t lo, uint64_t cnt) -> int {
-        G16_HIP_TRY(hipSetDevice(devs[k]));
+    CtxView cv;
+    G16_TRY(cv.load(ctx));
+    if (cv.curve != C::CURVE_ID) return G16_ERR_BAD_ARG;
+    return for_each_chunk(cv, n, [&](uint64_t k, uint64_t lo, uint64_t cnt, DevBufs& bufs) -> int {
+        hipStream_t s = cv.streams[k];
+        G16_HIP_TRY(hipSetDevice(cv.devs[k]));
         uint64_t* d_items;
         uint8_t *d_flags, *d_pt;
-        G16_TRY(bufs[k].get(&d_items, cnt * words));
-        G16_TRY(bufs[k].get(&d_flags, cnt));
-        G16_HIP_TRY(hipMemcpyAsync(d_items, items + lo * words, cnt * words * sizeof(uint64_t), hipMemcpyHostToDevice, streams[k]));
+        G16_TRY(bufs.get(&d_items, cnt * words));
+        G16_TRY(bufs.get(&d_flags, cnt));
+        G16_HIP_TRY(hipMemcpyAsync(d_items, items + lo * words, cnt * words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
         if (proofs) {
-            G16_TRY(bufs[k].get(&d_pt, 3 * cnt));
-            G16_TRY(enqueue_proofs<C>(streams[k], d_items, cnt, d_pt, d_flags, nullptr));
+            G16_TRY(bufs.get(&d_pt, 3 * cnt));
+            G16_TRY(enqueue_proofs<C>(s, d_items, cnt, d_pt, d_flags, nullptr));
         } else {
-            G16_TRY(enqueue_points<C>(streams[k], g2, d_items, words, 0, 1, cnt, d_flags));
+            G16_TRY(enqueue_points<C>(s, g2, d_items, words, 0, 1, cnt, d_flags));
         }
-        G16_HIP_TRY(hipMemcpyAsync(flags + lo, d_flags, cnt, hipMemcpyDeviceToHost, streams[k]));
+        G16_HIP_TRY(hipMemcpyAsync(flags + lo, d_flags, cnt, hipMemcpyDeviceToHost, s));
         return G16_OK;
-    };
-    int rc = G16_OK;
-    for (uint64_t k = 0; k < nd && rc == G16_OK; ++k) {
-        const uint64_t lo = n * k / nd, hi = n * (k + 1) / nd;
-        if (hi > lo) rc = chunk(k, lo, hi - lo);
-    }
-    for (uint64_t k = 0; k < nd; ++k) {
-        (void)hipSetDevice(devs[k]);
-        if (hipStreamSynchronize(streams[k]) != hipSuccess && rc == G16_OK) rc = G16_ERR_HIP;
-        bufs[k].release();
-    }
-    return rc;
+    });
 }
 
 template <class C>
@@ -125,13 +110,6 @@ int host_check(int g2, const uint64_t* points, uint64_t n, uint8_t* flags) {
     for (uint64_t i = 0; i < n; ++i)
         flags[i] = g2 ? Subgroup<C>::g2_flag(ld_any<typename C::G2A>(points + i * 4 * L)) : Subgroup<C>::g1_flag(ld_any<typename C::G1A>(points + i * 2 * L));
     return G16_OK;
-}
-
-static int ctx_curve(const g16_ctx* ctx) {
-    int curve = -1;
-    std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    return ctx_devices(ctx, &curve, devs, streams) == G16_OK ? curve : -1;
 }
 
 }  // namespace g16

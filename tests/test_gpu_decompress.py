@@ -11,6 +11,7 @@ from subgroup_cases import model_groups
 from verify_cases import oracle_case, wrong_input
 
 import groth16_amd as g
+from groth16_amd.verifier import host_aggregate_verdict
 
 pytestmark = pytest.mark.gpu
 N_PROOFS = 67
@@ -109,6 +110,19 @@ def test_proofs_on_two_chunks(setup):
         _, encs, status, pts = cases(name, True)
         got, st = multi.decompress_points(blob(encs), True)
         assert (st == status).all() and got.tobytes() == pts.tobytes()
+        # n = 1: the first of the two chunks is empty.  One honest and one corrupted item, against the host twin
+        fb = fq_bytes(name)
+        data = proofs_to_bytes(name, honest)
+        bad, want, _ = corrupted(name, data)
+        for row, ok in ((data[0], 1), (bad[3], 0)):
+            parts = [g.decompress_points_host(name, row[lo:hi], g2) for lo, hi, g2 in ((0, fb, False), (fb, 3 * fb, True), (3 * fb, 4 * fb, False))]
+            flat, st = multi.decompress_proofs(row)
+            assert flat.tobytes() == b"".join(p.tobytes() for p, _ in parts)
+            assert list(st) == [min(int(s[0]) for _, s in parts)] == [ok]
+        for i in (int(np.argmax(status == 1)), int(np.argmax(status == 0))):
+            got, st = multi.decompress_points(blob(encs, [i]), True)
+            host, host_st = g.decompress_points_host(name, blob(encs, [i]), True)
+            assert got.tobytes() == host.tobytes() and list(st) == list(host_st) == [status[i]]
 
 
 def test_bytes_to_verdict(setup):
@@ -145,5 +159,9 @@ def test_bytes_to_verdict(setup):
         try:
             for d, xt, want in ((data, xs, 1), (data, bad_x, 0), (outside_bytes, xs, 3), (both, xs, 4)):
                 assert multi.verify_aggregate_bytes_verdict(pvk2, d, xt, coeffs) == want
+            # n = 1: the first of the two chunks is empty
+            for i, xt, want in ((0, xs[:1], 1), (66, bad_x[66:], 0)):
+                assert multi.verify_aggregate_bytes_verdict(pvk2, data[i], xt, coeffs[:1]) == want
+                assert host_aggregate_verdict(name, vk, honest[i: i + 1], xt, coeffs[:1]) == want
         finally:
             pvk2.close()

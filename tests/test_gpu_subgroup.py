@@ -13,6 +13,7 @@ from verify_cases import oracle_case, wrong_input
 
 import groth16_amd as g
 from groth16_amd.binding import ptr64
+from groth16_amd.verifier import host_aggregate_verdict
 
 pytestmark = pytest.mark.gpu
 N_PROOFS = 67
@@ -100,6 +101,15 @@ def test_proof_flags(setup):
         assert (multi.check_proof_subgroups(flat) == want).all()
         _, pts, flags = case_arrays(name, True)
         assert (multi.check_subgroups(pts, True) == flags).all()
+        # n = 1: the first of the two chunks is empty.  One honest and one tampered item, against the host twin
+        L = cp.fq_limbs64
+        for i in (0, 20):
+            a, b, c = (g.check_subgroups_host(name, flat[i, lo:hi].reshape(1, -1), g2)[0]
+                       for lo, hi, g2 in ((0, 2 * L, False), (2 * L, 6 * L, True), (6 * L, 8 * L, False)))
+            host = 2 if 2 in (a, b, c) else min(a, b, c)
+            assert list(multi.check_proof_subgroups(flat[i: i + 1])) == [host] == [want[i]]
+        for i in (int(np.argmax(flags == 1)), int(np.argmax(flags == 0))):
+            assert list(multi.check_subgroups(pts[i: i + 1], True)) == list(g.check_subgroups_host(name, pts[i: i + 1], True)) == [flags[i]]
 
 
 def direct_aggregate(prover, pvk, flat, xs, coeffs):
@@ -139,6 +149,11 @@ def test_checked_aggregate_verdicts(setup):
         try:
             for flat, xt, want in ((honest, xs, 1), (outside, xs, 3), (both, xs, 2), (honest, bad_x, 0)):
                 assert multi.verify_aggregate_verdict(pvk2, flat, xt, coeffs, check_subgroups=True) == want
+            # n = 1: the first of the two chunks is empty.  The host form has no membership stage: it answers for members only
+            for flat, xt, want in ((honest[:1], xs[:1], 1), (honest[66:], bad_x[66:], 0)):
+                assert multi.verify_aggregate_verdict(pvk2, flat, xt, coeffs[:1], check_subgroups=True) == want
+                assert host_aggregate_verdict(name, vk, flat, xt, coeffs[:1]) == want
+            assert multi.verify_aggregate_verdict(pvk2, outside[31:32], xs[:1], coeffs[:1], check_subgroups=True) == 3
         finally:
             pvk2.close()
 

@@ -135,6 +135,8 @@ def test_multi_device_context_keeps_input_order(setup):
         pvk = multi.prepare_verifying_key(vk)
         try:
             assert (multi.verify_verdicts(pvk, flat, xs) == want).all()
+            for label, p, xi, v in (cases[0], cases[3]):   # n = 1: the first of the two chunks is empty
+                assert list(multi.verify_verdicts(pvk, p[None], [xi])) == [host_verdict(name, vk, p, xi)] == [v], label
         finally:
             pvk.close()
 

@@ -181,6 +181,9 @@ def test_two_chunk_context_and_or_each(setup):
                     assert prover.verify_aggregate_verdict(pvk, flat, xt, r) == v
                     assert multi.verify_aggregate_verdict(pvk2, flat, xt, r) == v
             assert (multi.verify_proofs_aggregate_or_each(pvk2, two_bad, xt) == want).all()
+            for label, p, xi, v in (cases[0], cases[3]):   # n = 1: the first of the two chunks is empty
+                assert multi.verify_aggregate_verdict(pvk2, p[None], [xi], coeffs[:1]) == v, label
+                assert host_aggregate_verdict(name, vk, p[None], [xi], coeffs[:1]) == v, label
         finally:
             pvk2.close()
 
