@@ -20,11 +20,15 @@ Reference interface mirrored (paths relative to /root/reference):
   Groth16.prepare_verifying_key / prepare_inputs / verify_proof_with_prepared_inputs / verify_proof, process_vk /
       verify_with_processed_vk                      src/verifier.rs:13-76, src/lib.rs:84-96 (GPU batch: verify_proofs)
   VerifyingKey / PreparedVerifyingKey               src/data_structures.rs:31-66
+  Groth16.check_assignment / is_satisfied / which_is_unsatisfied, host_check_assignment, ConstraintSystem.which_is_unsatisfied,
+      check=True on create_proof* / prove / PipelinedProver.submit, Unsatisfiable
+                                                    debug_assert!(cs.is_satisfied().unwrap()), src/prover.rs:193 (ark-relations'
+      is_satisfied / which_is_unsatisfied, SynthesisError::Unsatisfiable) -- kept in "release": the check runs on the GPU
 """
 from .binding import (G16Error, Lib, PolynomialDegreeTooLarge, SynthesisError, UnexpectedIdentity, lib, FQ_LIMBS, CURVE_ID)  # noqa: F401
-from .groth16 import (CircomReduction, ConstraintMatrices, Groth16, LibsnarkReduction, PipelinedProver, Proof, ProvingKey, ShardedProver, finalize_host,  # noqa: F401
-                      rerandomize_proof, shard_ranges)
-from .binding import MalformedVerifyingKey  # noqa: F401
+from .groth16 import (CheckResult, CircomReduction, ConstraintMatrices, Groth16, LibsnarkReduction, PipelinedProver, Proof, ProvingKey, ShardedProver, finalize_host,  # noqa: F401
+                      host_check_assignment, rerandomize_proof, shard_ranges)
+from .binding import MalformedVerifyingKey, Unsatisfiable  # noqa: F401
 from .verifier import (PreparedVerifyingKey, VerifyingKey, check_subgroups_host, decompress_points_host, host_pairing, verify_proof_host,  # noqa: F401
                        verify_proofs_aggregate_host, verify_proofs_aggregate_mixed_host)
 from .r1cs import AssignmentMissing, ConstraintSynthesizer, ConstraintSystem, LinearCombination, Variable, lc  # noqa: F401
@@ -33,5 +37,5 @@ __all__ = [
     "Groth16", "LibsnarkReduction", "CircomReduction", "ConstraintMatrices", "ProvingKey", "Proof", "ShardedProver", "PipelinedProver", "G16Error", "SynthesisError",
     "PolynomialDegreeTooLarge", "UnexpectedIdentity", "lib", "ConstraintSystem", "ConstraintSynthesizer", "Variable", "LinearCombination",
     "lc", "AssignmentMissing", "VerifyingKey", "PreparedVerifyingKey", "MalformedVerifyingKey", "verify_proof_host", "verify_proofs_aggregate_host", "verify_proofs_aggregate_mixed_host", "check_subgroups_host", "host_pairing",
-    "decompress_points_host",
+    "decompress_points_host", "CheckResult", "Unsatisfiable", "host_check_assignment",
 ]

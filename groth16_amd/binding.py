@@ -40,6 +40,18 @@ class MalformedVerifyingKey(SynthesisError):
     """public inputs + 1 != gamma_abc_g1 (verifier.rs:29-31)"""
 
 
+class Unsatisfiable(SynthesisError):
+    """SynthesisError::Unsatisfiable: the assignment fails a constraint (status 12, g16_prove_checked).  `.row` is the first failing
+    row (which_is_unsatisfied), `.n_unsatisfied` how many rows fail, `.a` / `.b` / `.c` the three sums of that row as Montgomery limbs
+    (None when the status came without a g16_check_result)"""
+
+    def __init__(self, status: int, msg: str, result: "Optional[CheckResultC]" = None):
+        super().__init__(status, msg)
+        self.row = int(result.first_row) if result is not None else None
+        self.n_unsatisfied = int(result.n_unsatisfied) if result is not None else None
+        self.a, self.b, self.c = (np.array(list(getattr(result, k)), dtype=np.uint64) if result is not None else None for k in "abc")
+
+
 class InvalidData(G16Error):
     """ark_serialize::SerializationError::InvalidData"""
 
@@ -101,6 +113,11 @@ class PkInfoC(C.Structure):
         return d
 
 
+class CheckResultC(C.Structure):
+    """g16_check_result"""
+    _fields_ = [("n_unsatisfied", C.c_uint64), ("first_row", C.c_uint64), ("a", C.c_uint64 * 4), ("b", C.c_uint64 * 4), ("c", C.c_uint64 * 4)]
+
+
 class TimingsC(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "witness_map_ms", "msm_h_ms", "msm_l_ms", "msm_a_ms", "msm_b_g1_ms", "msm_b_g2_ms", "scalar_prep_ms", "finish_ms",
@@ -129,6 +146,7 @@ EXPORTS = [
     "g16_decompress_points", "g16_decompress_proofs", "g16_host_decompress_points", "g16_verify_aggregate_bytes",
     "g16_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed_gt",
     "g16_circuit_load_qap", "g16_circuit_qap", "g16_generate_parameters_qap", "g16_h_query_len", "g16_host_h_query_scalars",
+    "g16_circuit_attach_c", "g16_circuit_check", "g16_prove_checked", "g16_host_circuit_check",
 ]
 
 
@@ -263,10 +281,16 @@ class Lib:
                                                       C.c_void_p]
         c.g16_host_verify_aggregate_mixed_gt.argtypes = [C.c_int, C.POINTER(VkViewC), C.c_uint64, u32p, u64p, C.c_uint64, u64p, C.c_uint64, u64p,
                                                          u64p, u64p]
+        c.g16_circuit_attach_c.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CsrViewC)]
+        c.g16_circuit_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(CheckResultC)]
+        c.g16_prove_checked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, u64p, u64p, C.POINTER(ProofC),
+                                        C.POINTER(CheckResultC)]
+        c.g16_host_circuit_check.argtypes = [C.c_int, C.POINTER(CsrViewC), C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(CheckResultC)]
         c.g16_dev_fp30_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_fp30_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
 
-    def check(self, status: int):
+    def check(self, status: int, check_result: "Optional[CheckResultC]" = None):
+        """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable"""
         if status == 0:
             return
         msg = self.c.g16_strerror(status).decode()
@@ -281,6 +305,8 @@ class Lib:
             raise InvalidData(status, msg)
         if status == 11:
             raise MalformedVerifyingKey(status, msg)
+        if status == 12:
+            raise Unsatisfiable(status, msg, check_result)
         raise G16Error(status, msg)
 
     def version(self) -> str:

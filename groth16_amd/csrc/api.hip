@@ -237,6 +237,8 @@ void g16_ctx_destroy(g16_ctx* ctx) {
     (void)hipStreamDestroy(ctx->stream_h2d);
     (void)hipStreamDestroy(ctx->stream_wm);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    (void)hipFree(ctx->check_z);
+    (void)hipFree(ctx->check_rec);
     (void)hipStreamDestroy(ctx->stream);
     (void)hipStreamDestroy(ctx->stream2);
     (void)hipStreamDestroy(ctx->stream3);
@@ -700,6 +702,118 @@ int g16_prove(g16_ctx* ctx, const g16_pk* pk, const g16_circuit* circuit, const 
     return g16_prove_finalize(ctx, pk, &part, 1, r, s, out);
 }
 
+// ---- R1CS satisfaction (r1cs_check.hip): cs.is_satisfied() / which_is_unsatisfied() behind prover.rs:193 ------------------------
+int g16_circuit_attach_c(g16_ctx* ctx, g16_circuit* circuit, const g16_csr_view* c) {
+    if (!ctx || !circuit || !c || circuit->curve != ctx->curve) return G16_ERR_BAD_ARG;
+    if (circuit->qap != G16_QAP_CIRCOM) return G16_OK;   // a Libsnark circuit holds C since its load
+    if (!ctx->subs.empty() || !circuit->subs.empty() || !circuit->dc || !usable_on(circuit->ctx, ctx)) return G16_ERR_BAD_ARG;
+    auto attach = [&](auto* dc) -> int {
+        if (dc->row_ptr[2]) return G16_OK;   // a second call replaces nothing
+        const uint64_t nc = dc->num_constraints;
+        if (!c->row_ptr || c->row_ptr[0] != 0) { g_last_error = "g16_circuit_attach_c: row_ptr is NULL or does not start at 0"; return G16_ERR_BAD_ARG; }
+        for (uint64_t i = 0; i < nc; ++i)
+            if (c->row_ptr[i] > c->row_ptr[i + 1] || c->row_ptr[i + 1] - c->row_ptr[i] >= ((uint64_t)1 << 32)) {
+                g_last_error = "g16_circuit_attach_c: row_ptr decreases, or a row has 2^32 terms or more";
+                return G16_ERR_BAD_ARG;
+            }
+        const uint64_t nnz = c->row_ptr[nc];
+        if (nnz && (!c->col || !c->val)) { g_last_error = "g16_circuit_attach_c: col / val is NULL"; return G16_ERR_BAD_ARG; }
+        for (uint64_t k = 0; k < nnz; ++k)
+            if (c->col[k] >= dc->num_variables) { g_last_error = "g16_circuit_attach_c: a column index is >= num_variables"; return G16_ERR_BAD_ARG; }
+        G16_HIP_TRY(hipSetDevice(ctx->device));
+        return r1cs_attach_c_device(dc, c, ctx->stream);
+    };
+    try {
+        if (ctx->curve == G16_BLS12_381) return attach(static_cast<DeviceCircuit<Bls12_381>*>(circuit->dc));
+        return attach(static_cast<DeviceCircuit<Bn254>*>(circuit->dc));
+    } catch (const std::bad_alloc&) {
+        return G16_ERR_OOM;
+    }
+}
+
+// the check on `ctx` (single-device, or the first device of a multi-device context); *resident: the assignment as the check read it
+// on the device (the uploaded copy, or the caller's device pointer)
+static int circuit_check_impl(g16_ctx* ctx, const g16_circuit* circuit, const uint64_t* z, uint64_t n_assign, int on_device, g16_check_result* out,
+                              const uint64_t** resident) {
+    if (!ctx || !circuit || !z || !out || circuit->curve != ctx->curve) return G16_ERR_BAD_ARG;
+    g16_ctx* one = ctx;
+    const g16_circuit* ck = circuit;
+    if (!ctx->subs.empty()) {   // the circuit is replicated on every device: the first one checks
+        if (circuit->ctx != ctx || circuit->subs.empty()) return G16_ERR_BAD_ARG;
+        one = ctx->subs[0];
+        ck = circuit->subs[0];
+    } else if (!circuit->subs.empty() || !usable_on(circuit->ctx, ctx)) {
+        return G16_ERR_BAD_ARG;
+    }
+    if (!ck->dc) return G16_ERR_BAD_ARG;
+    auto run = [&](const auto* dc) -> int {
+        typedef typename std::remove_pointer_t<decltype(dc)>::Fr Fr;
+        if (n_assign != dc->num_variables) return G16_ERR_BAD_LENGTH;
+        if (dc->num_constraints && !dc->row_ptr[2]) {
+            g_last_error = "g16_circuit_check: a Circom circuit holds no C matrix until g16_circuit_attach_c brings one";
+            return G16_ERR_BAD_ARG;
+        }
+        if (dc->long_rows) { g_last_error = "g16_circuit_check: a row of the circuit has 2^32 terms or more"; return G16_ERR_BAD_ARG; }
+        G16_HIP_TRY(hipSetDevice(one->device));
+        if (!one->check_rec) G16_HIP_TRY(hipMalloc(&one->check_rec, R1CS_CHECK_SCRATCH));
+        const uint64_t* d_z = z;
+        if (!on_device) {
+            const size_t bytes = (size_t)n_assign * sizeof(Fr);
+            if (one->check_z_bytes < bytes) {
+                (void)hipFree(one->check_z);
+                one->check_z = nullptr;
+                one->check_z_bytes = 0;
+                G16_HIP_TRY(hipMalloc((void**)&one->check_z, bytes));
+                one->check_z_bytes = bytes;
+            }
+            // whole, in ONE copy: the piecewise upload of the witness maps follows need_col, which for a Circom circuit does not cover C
+            G16_HIP_TRY(hipMemcpyAsync(one->check_z, z, bytes, hipMemcpyHostToDevice, one->stream));
+            d_z = one->check_z;
+        }
+        const int rc = r1cs_check_device(dc, reinterpret_cast<const Fr*>(d_z), one->check_rec, one->stream, out);
+        if (rc) { (void)hipStreamSynchronize(one->stream); return rc; }   // (the upload may still be reading the caller's array)
+        if (resident) *resident = d_z;
+        return G16_OK;
+    };
+    try {
+        if (ctx->curve == G16_BLS12_381) return run(static_cast<const DeviceCircuit<Bls12_381>*>(ck->dc));
+        return run(static_cast<const DeviceCircuit<Bn254>*>(ck->dc));
+    } catch (const std::bad_alloc&) {
+        return G16_ERR_OOM;
+    }
+}
+
+int g16_circuit_check(g16_ctx* ctx, const g16_circuit* circuit, const uint64_t* full_assignment, uint64_t n_assign, int assignment_on_device,
+                      g16_check_result* out) {
+    return circuit_check_impl(ctx, circuit, full_assignment, n_assign, assignment_on_device, out, nullptr);
+}
+
+int g16_prove_checked(g16_ctx* ctx, const g16_pk* pk, const g16_circuit* circuit, const uint64_t* full_assignment, uint64_t n_assign,
+                      int assignment_on_device, const uint64_t r[4], const uint64_t s[4], g16_proof* out, g16_check_result* check_out) {
+    if (!ctx || !pk || !circuit || !full_assignment || !r || !s || !out) return G16_ERR_BAD_ARG;
+    g16_check_result res;
+    const uint64_t* resident = nullptr;
+    G16_TRY(circuit_check_impl(ctx, circuit, full_assignment, n_assign, assignment_on_device, &res, &resident));
+    if (check_out) *check_out = res;
+    if (res.n_unsatisfied) return G16_ERR_UNSATISFIED;   // debug_assert!(cs.is_satisfied().unwrap()), prover.rs:193: nothing is proved
+    // the copy the check uploaded lives on the first device only: a multi-device context proves from the caller's pointer, every
+    // device staging its own copy as g16_prove has it
+    if (ctx->subs.empty()) return g16_prove(ctx, pk, circuit, resident, n_assign, 1, r, s, out);
+    return g16_prove(ctx, pk, circuit, full_assignment, n_assign, assignment_on_device, r, s, out);
+}
+
+int g16_host_circuit_check(int curve, const g16_csr_view abc[3], uint64_t num_constraints, const uint64_t* full_assignment, uint64_t n_assign,
+                           g16_check_result* out) {
+    if (!abc || !out || (!full_assignment && n_assign)) return G16_ERR_BAD_ARG;
+    try {
+        if (curve == G16_BLS12_381) return r1cs_check_host<Bls12_381>(abc, num_constraints, full_assignment, n_assign, out);
+        if (curve == G16_BN254) return r1cs_check_host<Bn254>(abc, num_constraints, full_assignment, n_assign, out);
+    } catch (const std::bad_alloc&) {
+        return G16_ERR_OOM;
+    }
+    return G16_ERR_BAD_ARG;
+}
+
 int g16_prove_partial_prepare(g16_ctx* ctx, const g16_pk* pk, const g16_circuit* circuit, const uint64_t* full_assignment_dev, uint64_t n_assign) {
     if (!ctx || !pk || !circuit || !full_assignment_dev) return G16_ERR_BAD_ARG;
     if (pk->curve != ctx->curve || circuit->curve != ctx->curve) return G16_ERR_BAD_ARG;
@@ -953,6 +1067,7 @@ const char* g16_strerror(int status) {
         case G16_ERR_INVALID_DATA: return "invalid data: the bytes do not encode a point of the group";
         case G16_ERR_NO_PEER_ACCESS: return "two devices of a multi-device context have no peer access (G16_MULTI_REQUIRE_PEER)";
         case G16_ERR_MALFORMED_VK: return "malformed verifying key: public inputs + 1 != gamma_abc_g1";
+        case G16_ERR_UNSATISFIED: return "unsatisfied: the assignment does not satisfy the constraint system (g16_check_result names the first row)";
         default: return "unknown status";
     }
 }
@@ -969,6 +1084,7 @@ uint64_t g16_struct_size(int which) {
         case G16_STRUCT_PARTIAL: return sizeof(g16_partial);
         case G16_STRUCT_PK_VIEW: return sizeof(g16_pk_view);
         case G16_STRUCT_VK_VIEW: return sizeof(g16_vk_view);
+        case G16_STRUCT_CHECK_RESULT: return sizeof(g16_check_result);
         default: return 0;
     }
 }

@@ -148,6 +148,11 @@ struct g16_ctx {
     } finprep;
     void* pinned = nullptr;  // window sums land here (hipHostMalloc)
     size_t pinned_bytes = 0;
+    // g16_circuit_check / g16_prove_checked: a host assignment uploaded whole (it outlives the per-call arena: g16_prove_checked proves
+    // from it after the check), grown on demand and kept until the context goes; and the check's result record (R1CS_CHECK_SCRATCH)
+    uint64_t* check_z = nullptr;
+    size_t check_z_bytes = 0;
+    void* check_rec = nullptr;
     // g16_ctx_create_multi: a multi-device context owns one full context per device and no device state of its own
     std::vector<g16_ctx*> subs;
     std::vector<char> peer;   // [i * n + j]: device i reaches device j's memory directly (hipDeviceCanAccessPeer + enabled); see g16_ctx_peer_access

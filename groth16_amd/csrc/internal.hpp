@@ -142,6 +142,10 @@ struct DeviceCircuit {
     // generator of the 2n-point domain (rho^2 = w), takes s1_br's place between the inverse and the forward transform
     int qap = G16_QAP_LIBSNARK;
     Fr* circom_pre = nullptr;
+    // g16_circuit_attach_c: a Circom circuit's C matrix, uploaded after the load for the satisfaction check alone (r1cs_check.hip) --
+    // row_ptr[2] / col[2] / val[2] / nnz[2] are then set, need_col and the map still cover A and B only
+    // long_rows: some row of a Libsnark circuit has 2^32 terms or more (the check's row walk counts in 32 bits and refuses such a circuit)
+    bool long_rows = false;
 };
 // a host assignment on its way to the device: witness_map_device issues the copies itself (in DeviceCircuit::Z_CHUNKS pieces on
 // `copy_stream`, one event each) and interleaves them with the row blocks of the mat-vec that each piece unlocks
@@ -156,9 +160,24 @@ struct ZUpload {
 // transforms, all under ntt_timers[0])
 // after the CSR upload: flag the unit coefficients in the DEVICE column indices (bit 31), see witness_map.hip
 template <class C> int mark_unit_coefficients(DeviceCircuit<C>* ck, hipStream_t st);
+// the same for one matrix's device arrays (the caller has checked num_variables < 2^31)
+template <class C> int mark_unit_matrix(uint32_t* col, const typename C::Fr* val, uint64_t nnz, hipStream_t st);
 // up != nullptr: d_z is an empty device buffer and the assignment still lies in host memory (ZUpload)
 template <class C> int witness_map_device(const DeviceCircuit<C>* ck, const typename C::Fr* d_z, typename C::Fr* d_h, Arena& arena,
                                           hipStream_t st, EventTimer* ntt_timers = nullptr, ZUpload* up = nullptr);
+
+// ---- R1CS satisfaction check (r1cs_check.hip): cs.is_satisfied() / which_is_unsatisfied() behind prover.rs:193 ------------
+// One lane per constraint row < num_constraints: a bad row has <A_row, z> * <B_row, z> != <C_row, z>.  d_scratch: R1CS_CHECK_SCRATCH
+// bytes of device memory (the 16-byte result record and the three values of the first bad row).  Returns after one stream
+// synchronisation when every row holds, after a second one (the values of the first bad row) otherwise.  The circuit holds C.
+static constexpr size_t R1CS_CHECK_SCRATCH = 128;
+template <class C> int r1cs_check_device(const DeviceCircuit<C>* ck, const typename C::Fr* d_z, void* d_scratch, hipStream_t st,
+                                         g16_check_result* out);
+// upload a Circom circuit's C matrix (host view, already validated against the circuit) and mark its unit coefficients
+template <class C> int r1cs_attach_c_device(DeviceCircuit<C>* ck, const g16_csr_view* c, hipStream_t st);
+// the same check on the host over the caller's (unmarked) arrays; they are validated first (G16_ERR_BAD_LENGTH)
+template <class C> int r1cs_check_host(const g16_csr_view abc[3], uint64_t num_constraints, const uint64_t* z, uint64_t n_assign,
+                                       g16_check_result* out);
 
 // ---- distributed witness map (witness_map.hip): the same h over N ranks, one all-to-all per transform --------------------
 // n = N * M, blk = M / N (needs N^2 | n, N a power of two <= 16).  Two distributions of an n-vector over the ranks:

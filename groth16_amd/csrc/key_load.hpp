@@ -253,9 +253,13 @@ struct KeyLoader {
             if (abc[m].row_ptr[0] != 0) return fail(G16_ERR_BAD_LENGTH);
             for (uint64_t i = 0; i < num_constraints; ++i)
                 if (abc[m].row_ptr[i] > abc[m].row_ptr[i + 1]) return fail(G16_ERR_BAD_LENGTH);
-            if (qap == G16_QAP_CIRCOM)   // spmv_circom_kernel counts a row's terms in 32 bits
-                for (uint64_t i = 0; i < num_constraints; ++i)
-                    if (abc[m].row_ptr[i + 1] - abc[m].row_ptr[i] >= ((uint64_t)1 << 32)) return fail(G16_ERR_BAD_LENGTH);
+            // spmv_circom_kernel and r1cs_check_kernel count a row's terms in 32 bits: a Circom circuit with a longer row is refused,
+            // a Libsnark circuit (whose map does not mind) is marked and refused by the check alone
+            for (uint64_t i = 0; i < num_constraints; ++i)
+                if (abc[m].row_ptr[i + 1] - abc[m].row_ptr[i] >= ((uint64_t)1 << 32)) {
+                    if (qap == G16_QAP_CIRCOM) return fail(G16_ERR_BAD_LENGTH);
+                    dc->long_rows = true;
+                }
             const uint64_t nnz = abc[m].row_ptr[num_constraints];
             dc->nnz[m] = nnz;
             if (nnz && (!abc[m].col || !abc[m].val)) return fail(G16_ERR_BAD_ARG);

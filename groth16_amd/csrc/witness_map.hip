@@ -11,6 +11,7 @@
 //   h[k] = q[bitrev(k)] * n^-1 g^-k                           (coset ifft's tail, fused with the un-permute)
 // All kernels are HBM-streaming (32 B per element per sweep); the CSR mat-vec is gather-bound.
 #include "internal.hpp"
+#include "csr_row_dot.hpp"
 #include <algorithm>
 #include <new>
 
@@ -65,29 +66,7 @@ __global__ void quotient_kernel(Fr* __restrict__ a, const Fr* __restrict__ b, co
 }
 
 // ---- Circom reduction ---------------------------------------------------------------------------------------------------
-// <M_row, z> of one CSR row, with the unit-coefficient fast path of spmv3_kernel
-template <class Fr>
-__device__ __forceinline__ Fr csr_row_dot(const uint64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, const Fr* __restrict__ val,
-                                          const Fr* __restrict__ z, uint64_t row) {
-    Fr acc = Fr::zero();
-    const Fr one = Fr::one();
-    // (a row has fewer than 2^32 terms -- g16_circuit_load_qap checks -- so the walk counts in one register)
-    const uint64_t b = row_ptr[row];
-    const uint32_t len = (uint32_t)(row_ptr[row + 1] - b);
-    col += b;
-    val += b;
-    for (uint32_t k = 0; k < len; ++k) {
-        const uint32_t c = col[k];
-        if (c >> 31) {
-            acc = acc + z[c & 0x7fffffffu];
-        } else {
-            const Fr coeff = val[k];
-            const Fr v = z[c];
-            acc = acc + ((coeff == one) ? v : v * coeff);
-        }
-    }
-    return acc;
-}
+// (csr_row_dot.hpp: <M_row, z> of one CSR row, with the unit-coefficient fast path of spmv3_kernel)
 
 // rows [row0, row0 + rows) of the Circom map's first two steps, one lane per row, each stored at its own row index:
 //   a = <A_row, z> (rows < nc), z[row - nc] (the num_inputs rows after them), 0 above;  b = <B_row, z> or 0;  c = a * b.
@@ -454,16 +433,23 @@ __global__ void mark_unit_kernel(uint32_t* __restrict__ col, const Fr* __restric
     if (k < nnz && val[k] == Fr::one()) col[k] |= 0x80000000u;
 }
 template <class C>
+int mark_unit_matrix(uint32_t* col, const typename C::Fr* val, uint64_t nnz, hipStream_t st) {
+    if (!nnz) return G16_OK;
+    hipLaunchKernelGGL((mark_unit_kernel<typename C::Fr>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, col, val, nnz);
+    G16_LAUNCH_CHECK();
+    return G16_OK;
+}
+template <class C>
 int mark_unit_coefficients(DeviceCircuit<C>* ck, hipStream_t st) {
     if (ck->num_variables >= (1ull << 31)) return G16_OK;
     for (int m = 0; m < 3; ++m) {
-        if (!ck->nnz[m] || !ck->col[m]) continue;   // (a Circom circuit holds no C matrix)
-        hipLaunchKernelGGL((mark_unit_kernel<typename C::Fr>), dim3((unsigned)((ck->nnz[m] + 255) / 256)), dim3(256), 0, st, ck->col[m], ck->val[m],
-                           ck->nnz[m]);
-        G16_LAUNCH_CHECK();
+        if (!ck->nnz[m] || !ck->col[m]) continue;   // (a Circom circuit holds no C matrix until g16_circuit_attach_c brings one)
+        G16_TRY((mark_unit_matrix<C>(ck->col[m], ck->val[m], ck->nnz[m], st)));
     }
     return G16_OK;
 }
+template int mark_unit_matrix<Bls12_381>(uint32_t*, const Bls12_381::Fr*, uint64_t, hipStream_t);
+template int mark_unit_matrix<Bn254>(uint32_t*, const Bn254::Fr*, uint64_t, hipStream_t);
 template int mark_unit_coefficients<Bls12_381>(DeviceCircuit<Bls12_381>*, hipStream_t);
 template int mark_unit_coefficients<Bn254>(DeviceCircuit<Bn254>*, hipStream_t);
 

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CsrViewC, ParamsViewC, PartialC, PkInfoC, PkViewC, ProofC, QueryC, TimingsC, ToxicWasteC, lib,
+from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, PkInfoC, PkViewC, ProofC, QueryC, TimingsC, ToxicWasteC, lib,
                       ptr32, ptr64, u64p)
 
 _MODULUS_R = {
@@ -126,6 +126,43 @@ class Proof:
 
     def flat(self) -> np.ndarray:
         return np.concatenate([self.a, self.b, self.c])
+
+
+@dataclass
+class CheckResult:
+    """g16_check_result: what cs.is_satisfied() / cs.which_is_unsatisfied() say of (matrices, assignment).  `first_row` is the lowest
+    failing row, None when every row holds; a, b, c are that row's <A_row, z>, <B_row, z>, <C_row, z> as Montgomery limbs (zero when
+    nothing fails)"""
+
+    n_unsatisfied: int
+    first_row: Optional[int]
+    a: np.ndarray
+    b: np.ndarray
+    c: np.ndarray
+
+    @property
+    def satisfied(self) -> bool:
+        return self.n_unsatisfied == 0
+
+    @staticmethod
+    def from_c(res: CheckResultC) -> "CheckResult":
+        first = int(res.first_row)
+        return CheckResult(int(res.n_unsatisfied), None if first == 0xFFFFFFFFFFFFFFFF else first,
+                           *[np.array(list(getattr(res, k)), dtype=np.uint64) for k in "abc"])
+
+    def __eq__(self, o):
+        return (self.n_unsatisfied == o.n_unsatisfied and self.first_row == o.first_row and (self.a == o.a).all() and (self.b == o.b).all()
+                and (self.c == o.c).all())
+
+
+def host_check_assignment(curve: str, matrices: "ConstraintMatrices", full_assignment: np.ndarray) -> CheckResult:
+    """g16_host_circuit_check: the check of Groth16.check_assignment by the same row walk compiled for the host -- no GPU needed"""
+    views, keep = _csr_views(matrices)
+    z = _c(full_assignment)
+    res = CheckResultC()
+    lb = lib()
+    lb.check(lb.c.g16_host_circuit_check(CURVE_ID[curve], views, matrices.num_constraints, z.ctypes.data, z.shape[0], C.byref(res)))
+    return CheckResult.from_c(res)
 
 
 def shard_ranges(m: int, w: int, h_len: int, num_inputs: int, idx: int, cnt: int):
@@ -243,6 +280,7 @@ class _DeviceCircuit:
         self.ctx = ctx
         self.handle = C.c_void_p()
         self.num_variables = m.num_instance_variables + m.num_witness_variables
+        self._has_c = qap_id == QAP_LIBSNARK
         views, self._keep = _csr_views(m)
         if qap_id == QAP_LIBSNARK:
             ctx.lib.check(ctx.lib.c.g16_circuit_load(ctx.handle, views, m.num_instance_variables, m.num_constraints, self.num_variables,
@@ -250,6 +288,18 @@ class _DeviceCircuit:
         else:
             ctx.lib.check(ctx.lib.c.g16_circuit_load_qap(ctx.handle, views, m.num_instance_variables, m.num_constraints, self.num_variables,
                                                          qap_id, C.byref(self.handle)))
+
+    def attach_c(self, m: ConstraintMatrices):
+        """g16_circuit_attach_c: bring a Circom circuit's C matrix to the device, for the satisfaction check alone (once; nothing
+        happens on a Libsnark circuit, which holds C since its load)"""
+        if self._has_c:
+            return
+        rp, col, val = (np.ascontiguousarray(m.c[0], dtype=np.uint64), np.ascontiguousarray(m.c[1], dtype=np.uint32), _c(m.c[2]))
+        if len(rp) != m.num_constraints + 1:   # the C view carries no row count: the one place that can compare it
+            raise G16Error(3, f"bad argument | C has {len(rp) - 1} rows, the circuit {m.num_constraints}")
+        view = CsrViewC(ptr64(rp), ptr32(col), ptr64(val))
+        self.ctx.lib.check(self.ctx.lib.c.g16_circuit_attach_c(self.ctx.handle, self.handle, C.byref(view)))
+        self._has_c = True
 
     @property
     def qap(self) -> int:
@@ -360,12 +410,16 @@ class Groth16:
             self._pks[key] = (pk, _DevicePk(self._ctx, pk, num_inputs, shard, dist_h))
         return self._pks[key][1]
 
-    def _ck(self, m: ConstraintMatrices) -> _DeviceCircuit:
+    def _ck(self, m: ConstraintMatrices, for_check: bool = False) -> _DeviceCircuit:
+        """for_check: the circuit is about to be checked -- a Circom circuit, which is loaded without its C matrix, gets it now"""
         if self._owner is not None:
-            return self._owner._ck(m)
+            return self._owner._ck(m, for_check)
         if id(m) not in self._cks:
             self._cks[id(m)] = (m, _DeviceCircuit(self._ctx, m, self.qap.QAP_ID))
-        return self._cks[id(m)][1]
+        dck = self._cks[id(m)][1]
+        if for_check:
+            dck.attach_c(m)
+        return dck
 
     def evict_pk(self, pk: ProvingKey, shard=(0, 1)):
         """drop the device-resident copies of one key shard -- the contiguous cut and the block-order cut of the distributed
@@ -467,8 +521,8 @@ class Groth16:
     # -- prover.rs:173-217 ------------------------------------------------------------------------
     _MAX_CIRCUITS_BY_CONTENT = 64
 
-    def create_proof_with_reduction(self, circuit, pk: ProvingKey, r: np.ndarray, s: np.ndarray, circuit_id=None) -> Proof:
-        """Groth16::create_proof_with_reduction: host-side synthesis exactly as prover.rs:185-204 (fresh constraint system,
+    def create_proof_with_reduction(self, circuit, pk: ProvingKey, r: np.ndarray, s: np.ndarray, circuit_id=None, check: bool = False) -> Proof:
+        """(check: see create_proof_with_reduction_and_matrices.)  Groth16::create_proof_with_reduction: host-side synthesis exactly as prover.rs:185-204 (fresh constraint system,
         generate_constraints, matrices, full_assignment = instance ++ witness), then the pure-data call on the GPU.  The
         device copy of the matrices is cached, so proving the same circuit again uploads only the assignment: by
         `circuit_id` (any hashable the caller vouches for: same id = same constraint matrices; no hashing at all) or, without
@@ -510,15 +564,17 @@ class Groth16:
                     raise ValueError(f"circuit_id {circuit_id!r} was first used for a circuit of shape {shape(known)} (instance, witness, "
                                      f"constraints, nnz) and is now passed with one of shape {shape(m)}: one id must mean one circuit")
             m = known
-        return self.create_proof_with_reduction_and_matrices(pk, r, s, m, cs.num_instance_variables, cs.num_constraints, cs.full_assignment())
+        return self.create_proof_with_reduction_and_matrices(pk, r, s, m, cs.num_instance_variables, cs.num_constraints, cs.full_assignment(),
+                                                             check=check)
 
-    def prove(self, pk: ProvingKey, circuit, rng=None) -> Proof:
+    def prove(self, pk: ProvingKey, circuit, rng=None, check: bool = False) -> Proof:
         """SNARK::prove (lib.rs:76-82) = create_random_proof_with_reduction(circuit, pk, rng) (prover.rs:138-150)"""
-        return self.create_proof_with_reduction(circuit, pk, _rand_fr(self.curve, rng), _rand_fr(self.curve, rng))
+        return self.create_proof_with_reduction(circuit, pk, _rand_fr(self.curve, rng), _rand_fr(self.curve, rng), check=check)
 
-    def create_proof_no_zk(self, circuit, pk: ProvingKey) -> Proof:
+    def create_proof_no_zk(self, circuit, pk: ProvingKey, check: bool = False) -> Proof:
         """prover.rs:155-168 on a circuit: r = s = 0 (same as create_proof_with_reduction_no_zk(circuit, pk))"""
-        return self.create_proof_with_reduction_no_zk(circuit, pk)
+        zero = np.zeros(4, dtype=np.uint64)
+        return self.create_proof_with_reduction(circuit, pk, zero, zero, check=check)
 
     # -- verifier.rs:13-76, lib.rs:84-96 ----------------------------------------------------------
     def prepare_verifying_key(self, vk) -> "PreparedVerifyingKey":
@@ -679,17 +735,49 @@ class Groth16:
 
     # -- prover.rs:26-51 -------------------------------------------------------------------
     def create_proof_with_reduction_and_matrices(self, pk: ProvingKey, r: np.ndarray, s: np.ndarray, matrices: ConstraintMatrices,
-                                                 num_inputs: int, num_constraints: int, full_assignment: np.ndarray) -> Proof:
+                                                 num_inputs: int, num_constraints: int, full_assignment: np.ndarray, check: bool = False) -> Proof:
+        """check=False is the reference's release build: the assignment is proved as given, and one that does not satisfy the
+        constraints yields a well-formed proof no verifier accepts.  check=True keeps debug_assert!(cs.is_satisfied()) of
+        prover.rs:193 (g16_prove_checked): the assignment is checked on the GPU first and `Unsatisfiable` -- with the first failing
+        row and its values -- is raised instead of proving; a satisfied one gives the same proof bit for bit."""
         assert num_inputs == matrices.num_instance_variables and num_constraints == matrices.num_constraints
         L = FQ_LIMBS[self.curve]
-        dpk, dck = self._pk(pk, num_inputs), self._ck(matrices)
+        dpk, dck = self._pk(pk, num_inputs), self._ck(matrices, for_check=check)
         z = _c(full_assignment)
         out = ProofC()
         lb = self._ctx.lib
-        lb.check(lb.c.g16_prove(self._ctx.handle, dpk.handle, dck.handle, z.ctypes.data, z.shape[0], 0, ptr64(_c(r)), ptr64(_c(s)),
-                                C.byref(out)))
+        if check:
+            res = CheckResultC()
+            lb.check(lb.c.g16_prove_checked(self._ctx.handle, dpk.handle, dck.handle, z.ctypes.data, z.shape[0], 0, ptr64(_c(r)), ptr64(_c(s)),
+                                            C.byref(out), C.byref(res)), res)
+        else:
+            lb.check(lb.c.g16_prove(self._ctx.handle, dpk.handle, dck.handle, z.ctypes.data, z.shape[0], 0, ptr64(_c(r)), ptr64(_c(s)),
+                                    C.byref(out)))
         return Proof(np.array(out.a[: 2 * L], dtype=np.uint64), np.array(out.b[: 4 * L], dtype=np.uint64),
                      np.array(out.c[: 2 * L], dtype=np.uint64))
+
+    # -- prover.rs:193: cs.is_satisfied() / cs.which_is_unsatisfied() (ark-relations) on the GPU ------------------------------
+    def check_assignment(self, matrices: ConstraintMatrices, full_assignment: Optional[np.ndarray], z_dev_ptr: int = 0) -> CheckResult:
+        """g16_circuit_check: how many constraint rows `full_assignment` fails, the first of them and its three sums.  z_dev_ptr != 0:
+        the assignment is read from device memory in place (`full_assignment` is then not looked at).  With CircomReduction the C
+        matrix, which the map never reads, is uploaded on the first check of a circuit."""
+        dck = self._ck(matrices, for_check=True)
+        res = CheckResultC()
+        lb = self._ctx.lib
+        if z_dev_ptr:
+            lb.check(lb.c.g16_circuit_check(self._ctx.handle, dck.handle, C.c_void_p(z_dev_ptr), dck.num_variables, 1, C.byref(res)))
+        else:
+            z = _c(full_assignment)
+            lb.check(lb.c.g16_circuit_check(self._ctx.handle, dck.handle, z.ctypes.data, z.shape[0], 0, C.byref(res)))
+        return CheckResult.from_c(res)
+
+    def is_satisfied(self, matrices: ConstraintMatrices, z: np.ndarray) -> bool:
+        """cs.is_satisfied()"""
+        return self.check_assignment(matrices, z).satisfied
+
+    def which_is_unsatisfied(self, matrices: ConstraintMatrices, z: np.ndarray) -> Optional[int]:
+        """cs.which_is_unsatisfied(): the index of the first failing row (the reference names it by its trace), None if none"""
+        return self.check_assignment(matrices, z).first_row
 
     # -- prover.rs:155-168 -----------------------------------------------------------------
     def create_proof_with_reduction_no_zk(self, *args) -> Proof:
@@ -999,6 +1087,8 @@ class PipelinedProver:
         self._second = Groth16(curve, device, qap=qap)
         self._second.share_device_data_of(self._owner)
         self._lock = threading.Lock()           # key / circuit loads go through the owner's caches: one at a time
+        self._idle = threading.Condition()      # _busy: proofs in flight (a Circom circuit's C is attached only between proofs)
+        self._busy = 0
         self._jobs: "queue.Queue" = queue.Queue()
         self._threads = [threading.Thread(target=self._work, args=(p,), daemon=True) for p in (self._owner, self._second)]
         for t in self._threads:
@@ -1013,21 +1103,33 @@ class PipelinedProver:
             if not fut.set_running_or_notify_cancel():
                 continue
             try:
-                pk, r, s, matrices, num_inputs, num_constraints, z = args
+                pk, r, s, matrices, num_inputs, num_constraints, z, check = args
                 with self._lock:     # make sure the handles exist (first use loads them) before the unlocked, concurrent proof
                     prover._pk(pk, num_inputs)
-                    prover._ck(matrices)
-                fut.set_result(prover.create_proof_with_reduction_and_matrices(pk, r, s, matrices, num_inputs, num_constraints, z))
+                    if check and not prover._ck(matrices)._has_c:
+                        # attaching C changes the circuit both contexts read: not while the other worker is proving over it
+                        with self._idle:
+                            self._idle.wait_for(lambda: self._busy == 0)
+                            prover._ck(matrices, for_check=True)
+                    with self._idle:
+                        self._busy += 1
+                try:
+                    fut.set_result(prover.create_proof_with_reduction_and_matrices(pk, r, s, matrices, num_inputs, num_constraints, z, check=check))
+                finally:
+                    with self._idle:
+                        self._busy -= 1
+                        self._idle.notify_all()
             except BaseException as e:  # noqa: BLE001 -- delivered through the future
                 fut.set_exception(e)
 
     def submit(self, pk: ProvingKey, r: np.ndarray, s: np.ndarray, matrices: ConstraintMatrices, num_inputs: int, num_constraints: int,
-               full_assignment: np.ndarray):
-        """Groth16::create_proof_with_reduction_and_matrices (prover.rs:26-51), asynchronously"""
+               full_assignment: np.ndarray, check: bool = False):
+        """Groth16::create_proof_with_reduction_and_matrices (prover.rs:26-51), asynchronously; check as there (the future then
+        carries `Unsatisfiable` for a bad assignment)"""
         from concurrent.futures import Future
 
         fut: Future = Future()
-        self._jobs.put((fut, (pk, r, s, matrices, num_inputs, num_constraints, full_assignment)))
+        self._jobs.put((fut, (pk, r, s, matrices, num_inputs, num_constraints, full_assignment, check)))
         return fut
 
     def close(self):

@@ -164,6 +164,17 @@ class ConstraintSystem:
         ev = lambda row: sum(cf * z[col] for cf, col in row) % self.p  # noqa: E731
         return all(ev(a) * ev(b) % self.p == ev(c) for a, b, c in zip(*flat))
 
+    def which_is_unsatisfied(self) -> Optional[int]:
+        """cs.which_is_unsatisfied(): the index of the first constraint the assignment fails (the reference names it by its trace),
+        None when all hold.  A Python big-int loop like is_satisfied: for matrices of any size, Groth16.check_assignment"""
+        z = self.instance_assignment + self.witness_assignment
+        flat = [self._flat_rows(r) for r in self._rows]
+        ev = lambda row: sum(cf * z[col] for cf, col in row) % self.p  # noqa: E731
+        for i, (a, b, c) in enumerate(zip(*flat)):
+            if ev(a) * ev(b) % self.p != ev(c):
+                return i
+        return None
+
 
 def to_montgomery(vals: Sequence[int], p: int) -> np.ndarray:
     """integers mod p -> (n, 4) uint64 limbs of v * 2^256 mod p (the arkworks in-memory form of Fr)"""

@@ -12,6 +12,8 @@
  *   g16_pvk_load         <->  prepare_verifying_key / process_vk                    src/verifier.rs:13-20, src/lib.rs:84-86
  *   g16_verify_batch     <->  verify_proof (per proof)                             src/verifier.rs:25-76
  *   g16_verify_batch_prepared <-> verify_proof_with_prepared_inputs               src/verifier.rs:44-65
+ *   g16_circuit_check    <->  cs.is_satisfied() / cs.which_is_unsatisfied() (ark-relations) behind the debug_assert! of
+ *                             src/prover.rs:193; g16_prove_checked = that assertion kept in a release build, then g16_prove
  *   g16_prove_partial / g16_prove_finalize: the same proof with the MSM base set sharded
  *                             over several GPUs (one process per GPU; the host exchanges the
  *                             fixed-size g16_partial records, e.g. one RCCL all-gather).
@@ -57,7 +59,8 @@ typedef enum {
     G16_ERR_UNEXPECTED_IDENTITY = 8, /* SynthesisError::UnexpectedIdentity: gamma or delta is zero (generator.rs:110-111) */
     G16_ERR_INVALID_DATA = 9,        /* SerializationError::InvalidData: bytes that are not a point of the group        */
     G16_ERR_NO_PEER_ACCESS = 10,     /* g16_ctx_create_multi with G16_MULTI_REQUIRE_PEER=1: a device pair without peer access */
-    G16_ERR_MALFORMED_VK = 11        /* SynthesisError::MalformedVerifyingKey: public inputs + 1 != gamma_abc_g1 (verifier.rs:29-31) */
+    G16_ERR_MALFORMED_VK = 11,       /* SynthesisError::MalformedVerifyingKey: public inputs + 1 != gamma_abc_g1 (verifier.rs:29-31) */
+    G16_ERR_UNSATISFIED = 12         /* SynthesisError::Unsatisfiable (ark-relations): g16_prove_checked met a row with a*b != c       */
 } g16_status;
 
 typedef enum { G16_BLS12_381 = 0, G16_BN254 = 1 } g16_curve;
@@ -236,6 +239,48 @@ uint64_t g16_circuit_domain_size(const g16_circuit* c);
 /* full_assignment: n_assign Fr (host memory unless assignment_on_device != 0); r, s: one Fr each */
 int g16_prove(g16_ctx* ctx, const g16_pk* pk, const g16_circuit* circuit, const uint64_t* full_assignment,
               uint64_t n_assign, int assignment_on_device, const uint64_t r[4], const uint64_t s[4], g16_proof* out);
+
+/* ---- R1CS satisfaction on the GPU: debug_assert!(cs.is_satisfied().unwrap()), src/prover.rs:193 ----
+ * The reference checks the assignment in debug builds only; g16_prove, like a release build, proves whatever it is given, and for an
+ * assignment that does not satisfy the constraints returns G16_OK and a well-formed proof that no verifier accepts.  The calls below
+ * restate ark-relations' is_satisfied / which_is_unsatisfied over the matrices a g16_circuit already holds on the device: one more
+ * gather-bound walk of A, B and C.  Row i < num_constraints fails when <A_i, z> * <B_i, z> != <C_i, z>; the
+ * instance-copy rows the witness maps append are no constraints and are not looked at.
+ * g16_check_result: n_unsatisfied rows fail, first_row is the lowest of them (what which_is_unsatisfied names) and a, b, c are its three
+ * sums, Montgomery Fr like every scalar of this header; first_row = UINT64_MAX and a = b = c = 0 when no row fails. */
+typedef struct {
+    uint64_t n_unsatisfied;
+    uint64_t first_row;
+    uint64_t a[4], b[4], c[4];
+} g16_check_result;
+/* A Circom circuit holds A and B only (the map computes c = a .* b itself), so nothing on the device could notice that C z disagrees:
+ * this uploads C (host view over num_constraints rows; the view carries no row count of its own, row_ptr is read as
+ * num_constraints + 1 entries) and marks its unit coefficients like those of A and B.  The witness map still does not read C.  On a
+ * Libsnark circuit, and on a circuit that already has C, nothing happens: G16_OK.  Not while another call is using the circuit.
+ * G16_ERR_BAD_ARG: NULL, another curve or context, a row_ptr that does not start at 0, decreases or gives a row 2^32 terms, NULL col /
+ * val with entries present, a column >= num_variables (g16_last_error says which). */
+int g16_circuit_attach_c(g16_ctx* ctx, g16_circuit* circuit, const g16_csr_view* c);
+/* is_satisfied / which_is_unsatisfied of (circuit, full_assignment).  G16_OK means the check RAN; the answer is in *out
+ * (out->n_unsatisfied == 0: satisfied).  A host assignment is uploaded whole, in one copy, into a buffer the context keeps; a device
+ * assignment is read in place.  num_constraints == 0 gives {0, UINT64_MAX}.  A multi-device context checks on its first device (the
+ * circuit is replicated there; a device assignment must live on that device).
+ * G16_ERR_BAD_LENGTH: n_assign != num_variables.  G16_ERR_BAD_ARG: NULL, another curve, a circuit of another GPU, a Circom circuit
+ * without C (g16_circuit_attach_c first; g16_last_error says so), a Libsnark circuit with a row of 2^32 terms or more. */
+int g16_circuit_check(g16_ctx* ctx, const g16_circuit* circuit, const uint64_t* full_assignment, uint64_t n_assign,
+                      int assignment_on_device, g16_check_result* out);
+/* g16_prove with the assertion of prover.rs:193 kept: arguments as g16_prove, plus check_out (may be NULL).  A host assignment is
+ * uploaded once, checked, and proved from the resident copy through g16_prove(.., assignment_on_device = 1, ..) -- which gives up the
+ * overlap of g16_prove's piecewise upload with the first mat-vec rows; a device assignment is checked in place.  (A multi-device
+ * context checks on its first device and then proves from the caller's pointer as g16_prove does: every device stages its own copy.)
+ * Unsatisfied: G16_ERR_UNSATISFIED, *out untouched, *check_out filled, no MSM launched.  Satisfied: whatever g16_prove returns for the
+ * same inputs, the same proof bit for bit.  Errors of g16_circuit_check and of g16_prove as there. */
+int g16_prove_checked(g16_ctx* ctx, const g16_pk* pk, const g16_circuit* circuit, const uint64_t* full_assignment,
+                      uint64_t n_assign, int assignment_on_device, const uint64_t r[4], const uint64_t s[4], g16_proof* out,
+                      g16_check_result* check_out);
+/* CPU only: the same check by the same row walk compiled for the host, over the caller's own arrays (abc: A, B, C over num_constraints
+ * rows; n_assign Fr).  G16_ERR_BAD_LENGTH for a malformed row_ptr or a column >= n_assign, G16_ERR_BAD_ARG for NULL or an unknown curve. */
+int g16_host_circuit_check(int curve, const g16_csr_view abc[3], uint64_t num_constraints, const uint64_t* full_assignment,
+                           uint64_t n_assign, g16_check_result* out);
 
 /* sharded proof: every rank runs _partial on its pk shard, the host gathers the records, any rank
  * (all ranks, typically) runs _finalize over all of them */
@@ -575,7 +620,7 @@ const char* g16_version(void);
  * sizes (g16_struct_size), or uses the *_sized readers below, which copy min(size, library's size) bytes and never more. */
 #define G16_ABI_VERSION 2
 int g16_abi_version(void);
-enum { G16_STRUCT_TIMINGS = 0, G16_STRUCT_PK_INFO = 1, G16_STRUCT_DIAG = 2, G16_STRUCT_PROOF = 3, G16_STRUCT_PARTIAL = 4, G16_STRUCT_PK_VIEW = 5, G16_STRUCT_VK_VIEW = 6 };
+enum { G16_STRUCT_TIMINGS = 0, G16_STRUCT_PK_INFO = 1, G16_STRUCT_DIAG = 2, G16_STRUCT_PROOF = 3, G16_STRUCT_PARTIAL = 4, G16_STRUCT_PK_VIEW = 5, G16_STRUCT_VK_VIEW = 6, G16_STRUCT_CHECK_RESULT = 7 };
 /* sizeof the library's own idea of a struct of this header; 0 for an unknown `which` */
 uint64_t g16_struct_size(int which);
 /* g16_get_timings / g16_pk_get_info into a caller struct of `size` bytes (its sizeof at ITS compile time) */
