@@ -141,7 +141,7 @@ EXPORTS = [
     "g16_abi_version", "g16_struct_size", "g16_get_timings_sized", "g16_pk_get_info_sized",
     "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
-    "g16_dev_fp30_op", "g16_host_fp30_op",
+    "g16_dev_fp30_op", "g16_host_fp30_op", "g16_dev_msm_reduce_lab",
     "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
     "g16_decompress_points", "g16_decompress_proofs", "g16_host_decompress_points", "g16_verify_aggregate_bytes",
     "g16_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed_gt",
@@ -288,6 +288,7 @@ class Lib:
         c.g16_host_circuit_check.argtypes = [C.c_int, C.POINTER(CsrViewC), C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(CheckResultC)]
         c.g16_dev_fp30_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_fp30_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
+        c.g16_dev_msm_reduce_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u32p, u32p, C.c_uint64, u32p, u64p]
 
     def check(self, status: int, check_result: "Optional[CheckResultC]" = None):
         """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable"""
@@ -311,6 +312,22 @@ class Lib:
 
     def version(self) -> str:
         return self.c.g16_version().decode()
+
+
+def msm_reduce_lab(lb: "Lib", ctx, g2: bool, merged: bool, c: int, groups: int, G: int, nparts: np.ndarray, records: np.ndarray,
+                   affine_words: int):
+    """g16_dev_msm_reduce_lab (test hook): the prover's MSM reductions and host fold on caller-made partial sums.
+    nparts: uint32 [groups * 2^(c-1)] partial sums per bucket; records: uint32 [sum(nparts), record words] raw lazy limbs.
+    Returns (every bucket's first slot after the combine stages, uint32 [buckets, record words]; the folded affine point,
+    uint64 [affine_words])."""
+    nparts = np.ascontiguousarray(nparts, dtype=np.uint32)
+    records = np.ascontiguousarray(records, dtype=np.uint32)
+    assert nparts.shape == (groups << (c - 1),) and records.ndim == 2 and records.shape[0] == int(nparts.sum())
+    first = np.full((nparts.shape[0], records.shape[1]), 0xDEADBEEF, dtype=np.uint32)
+    out = np.zeros(affine_words, dtype=np.uint64)
+    lb.check(lb.c.g16_dev_msm_reduce_lab(ctx, int(g2), int(merged), c, groups, G, ptr32(nparts), ptr32(records), records.shape[0],
+                                         ptr32(first), ptr64(out)))
+    return first, out
 
 
 _LIB: Optional[Lib] = None

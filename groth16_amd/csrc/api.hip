@@ -936,6 +936,15 @@ int g16_msm_bucket_shard(g16_ctx* ctx, int g2, const uint64_t* bases, const uint
     G16_DISPATCH(ctx->curve, I::template msm_api<typename I::Fq2>(ctx, bases, scalars, n, out_affine, world, rank));
 }
 
+int g16_dev_msm_reduce_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, const uint32_t* nparts, const uint32_t* records,
+                           uint64_t n_records, uint32_t* first_slots, uint64_t* out_affine) {
+    if (!ctx || !nparts || !first_slots || !out_affine || (n_records && !records)) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty()) return g16_dev_msm_reduce_lab(ctx->subs[0], g2, merged, c, groups, G, nparts, records, n_records, first_slots, out_affine);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    if (!g2) G16_DISPATCH(ctx->curve, I::template msm_reduce_lab<typename I::Fq>(ctx, merged, c, groups, G, nparts, records, n_records, first_slots, out_affine));
+    G16_DISPATCH(ctx->curve, I::template msm_reduce_lab<typename I::Fq2>(ctx, merged, c, groups, G, nparts, records, n_records, first_slots, out_affine));
+}
+
 int g16_ntt(g16_ctx* ctx, uint64_t* data, int log_n, int inverse, int coset) {
     if (!ctx || !data) return G16_ERR_BAD_ARG;
     if (!ctx->subs.empty()) return g16_ntt(ctx->subs[0], data, log_n, inverse, coset);

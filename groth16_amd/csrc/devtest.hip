@@ -4,9 +4,14 @@
 // fips_asm_gen.hpp; the lane-pair forms run with one Fq2 value per adjacent lane pair and their DPP moves live.  The host has no
 // lanes: its lane-pair forms call the pair's pure per-lane routines once with hi = false and once with hi = true.
 // The accumulator forms put a lazy Acc30 through a chain of mixed additions (G1, G2 in one lane, G2 on the lane pair: device only).
+// The parked forms do the same with the bucket pass's own accumulator: AccParked over LdsAccStore in the kernel's LDS layout, signed
+// additions from packed y, gather() and to_packed as the flush does (G1; G2 on the lane pair: device only).  The host twin of the G1
+// form parks in ParkedArrayStore.
 // Kernel names start with devlab_: no resource budget applies to them.
 #include "internal.hpp"
 #include "fp30.hpp"
+#include "acc_store.hpp"
+#include <type_traits>
 #include <vector>
 
 using namespace g16;
@@ -42,6 +47,8 @@ constexpr bool lab_slots(int form, int* nin, int* nout) {
         case 63: case 64: case 65: i = 8; o = 2; break;
         case 70: i = 11; o = 5; break;
         case 71: case 72: i = 21; o = 9; break;
+        case 73: i = 11; o = 5; break;
+        case 74: i = 21; o = 9; break;
         default: return false;
     }
     *nin = i;
@@ -50,7 +57,9 @@ constexpr bool lab_slots(int form, int* nin, int* nout) {
 }
 constexpr int lab_nin(int form) { int i = 0, o = 0; lab_slots(form, &i, &o); return i; }
 constexpr int lab_nout(int form) { int i = 0, o = 0; lab_slots(form, &i, &o); return o; }
-constexpr bool lab_is_pair(int form) { return (form >= 60 && form < 70) || form == 72; }
+constexpr bool lab_is_pair(int form) { return (form >= 60 && form < 70) || form == 72 || form == 74; }
+constexpr bool lab_is_parked(int form) { return form == 73 || form == 74; }
+constexpr bool lab_device_only(int form) { return form == 72 || form == 74; }   // the lane pair's accumulators need their lanes
 // base fields have the fused-subtraction products, the Fq2 forms and the lane pair; scalar fields have sub_pow2
 template <class P>
 constexpr bool lab_has(int form) {
@@ -116,6 +125,45 @@ struct AccLab {
     }
 };
 
+// The bucket pass's accumulator (bucket_accumulate30_kernel): AccParked, coordinates behind a store, the sum's sign tracked in `neg`.
+// Same slots as AccLab, with the points as the window table holds them (canonical PACKED words, x and y) and more flags:
+//   in:  x y zz zzz (raw lazy limbs, the coordinates AS THEY LIE: the represented point is -(x, y, zz, zzz) when neg is set) |
+//        flag slot: word 0 the accumulator is the identity, word 1 the initial neg (kept as given beside an identity flag too: a
+//        flush or a cancellation leaves it behind), word 2 the number of points, word 3 + j point j is the identity (skipped, as
+//        the kernel skips it), word 6 + j point j is subtracted (`minus`, the signed digit's sign) | x y of three points
+//   out: gather() -- what a flush hands to the reductions -- through to_packed | word 0 of the last slot: the result is the identity
+template <class P, class F, class Store>
+struct ParkedLab {
+    typedef Fp30<P> B;
+    static constexpr int C = F::LANES_PER_TASK == 2 ? 2 : 1;
+    G16_HD static F ldf(const uint32_t* in, int slot, int hi) {
+        if constexpr (C == 2) return F{ld<P>(in, slot + hi)};
+        else return ld<P>(in, slot);
+    }
+    G16_HD static void stf(uint32_t* out, int slot, int hi, const F& v) {
+        if constexpr (C == 2) st_words<P>(out, slot + hi, v.c.to_packed());
+        else st_words<P>(out, slot, v.to_packed());
+    }
+    G16_HD static void run(const uint32_t* in, uint32_t* out, int hi, AccParked<F, Store>& a) {
+        const uint32_t* flags = in + 4 * C * B::NL;
+        a.inf = flags[0] != 0;
+        a.neg = flags[1] != 0;
+        if (!a.inf) {
+            a.s.st(a.CX, ldf(in, 0, hi)); a.s.st(a.CY, ldf(in, C, hi)); a.s.st(a.CZZ, ldf(in, 2 * C, hi)); a.s.st(a.CZZZ, ldf(in, 3 * C, hi));
+        }
+        const int n = flags[2] > 3u ? 3 : (int)flags[2];
+        for (int j = 0; j < n; ++j) {
+            if (flags[3 + j] != 0) continue;
+            const Fp<P> xw = ld_words<P>(in, 4 * C + 1 + 2 * j * C + hi), yw = ld_words<P>(in, 4 * C + 1 + (2 * j + 1) * C + hi);
+            a.add_affine_packed(F{B::unpack(xw.v)}, yw, flags[6 + j] != 0);
+        }
+        Acc30<F> g = a.gather();
+        if (g.inf) g.x = g.y = g.zz = g.zzz = F::zero();
+        stf(out, 0, hi, g.x); stf(out, C, hi, g.y); stf(out, 2 * C, hi, g.zz); stf(out, 3 * C, hi, g.zzz);
+        if (C == 1 || hi == 0) st_flag<P>(out, 4 * C, g.inf);
+    }
+};
+
 // one tuple of a one-lane form
 template <class P, int FORM>
 struct LabOp {
@@ -177,6 +225,10 @@ struct LabOp {
         }
         else if constexpr (FORM == 70) AccLab<P, Fp30<P>>::run(in, out, 0);
         else if constexpr (FORM == 71) AccLab<P, Fp2x30<P>>::run(in, out, 0);
+        else if constexpr (FORM == 73) {   // (the host twin: on the device devlab_op parks in LDS)
+            AccParked<B, ParkedArrayStore<B>> a;
+            ParkedLab<P, B, ParkedArrayStore<B>>::run(in, out, 0, a);
+        }
     }
 };
 
@@ -225,7 +277,21 @@ template <class P, int FORM>
 __global__ void __launch_bounds__(LAB_WG) devlab_op(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
     constexpr int NL = Fp30<P>::NL, NIN = lab_nin(FORM), NOUT = lab_nout(FORM);
     const uint32_t t = blockIdx.x * LAB_WG + threadIdx.x;
-    if constexpr (lab_is_pair(FORM)) {
+    if constexpr (lab_is_parked(FORM)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        // the bucket pass's LDS layout: 4 * NL * 64 words per 64-lane workgroup, every lane its own column (no barrier needed)
+        typedef typename std::conditional<lab_is_pair(FORM), Fp2p30<P>, Fp30<P>>::type F;
+        static_assert(LAB_WG == ACC_THREADS, "LdsAccStore is laid out for ACC_THREADS lanes");
+        __shared__ __attribute__((aligned(16))) uint32_t acc_lds[4 * F::PREFIX_LIMBS * ACC_THREADS];
+        constexpr uint32_t LPT = F::LANES_PER_TASK;
+        if (t >= LPT * n) return;   // both lanes of a pair leave together
+        const size_t i = t / LPT;
+        AccParked<F, LdsAccStore<F>> acc;
+        acc.s.quad = acc_lds + 4 * threadIdx.x;
+        acc.s.tail = acc_lds + 4 * LdsAccStore<F>::QUADS * ACC_THREADS + threadIdx.x;
+        ParkedLab<P, F, LdsAccStore<F>>::run(in + i * NIN * NL, out + i * NOUT * NL, LPT == 2 && (threadIdx.x & 1u) ? 1 : 0, acc);
+#endif
+    } else if constexpr (lab_is_pair(FORM)) {
         if (t >= 2 * n) return;   // both lanes of a pair leave together
         const size_t i = t >> 1;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -272,9 +338,9 @@ int lab_host(const uint32_t* operands, uint64_t n, uint32_t* out) {
 
 #define LAB_FORMS(X)                                                                                                              \
     X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(30) X(31) \
-    X(32) X(33) X(34) X(35) X(36) X(37) X(38) X(39) X(40) X(41) X(42) X(43) X(50) X(51) X(60) X(61) X(62) X(63) X(64) X(65) X(70) X(71) X(72)
+    X(32) X(33) X(34) X(35) X(36) X(37) X(38) X(39) X(40) X(41) X(42) X(43) X(50) X(51) X(60) X(61) X(62) X(63) X(64) X(65) X(70) X(71) X(72) X(73) X(74)
 
-// device: launch on st; otherwise the host twin (which has no lanes: the lane pair's accumulator, form 72, is a device form)
+// device: launch on st; otherwise the host twin (which has no lanes: the lane pair's accumulators, forms 72 and 74, are device forms)
 template <class P>
 int lab_dispatch(bool device, hipStream_t st, int form, const uint32_t* operands, uint64_t n, uint32_t* out) {
     switch (form) {
@@ -282,7 +348,7 @@ int lab_dispatch(bool device, hipStream_t st, int form, const uint32_t* operands
     case F:                                                                                    \
         if constexpr (lab_has<P>(F)) {                                                         \
             if (device) return lab_device<P, F>(st, operands, n, out);                         \
-            if constexpr (F == 72) return G16_ERR_BAD_ARG;                                     \
+            if constexpr (lab_device_only(F)) return G16_ERR_BAD_ARG;                                  \
             else return lab_host<P, F>(operands, n, out);                                      \
         } else return G16_ERR_BAD_ARG;
         LAB_FORMS(X)

@@ -598,17 +598,52 @@ struct SelfTest {
             pts.push_back(run.mul_bits(k, 32).to_affine());
             run.add_affine(gen);
         }
-        for (int round = 0; round < 4; ++round) {
+        // Rounds 4..8: SIGNED additions (`minus`: the digit's sign, as the bucket pass passes it) through both entries of the parked
+        // form, against ref.add_affine(-P).  Round 4 has random signs; in rounds 5..8 the third point is subtracted while the parked
+        // sum is negated (one hot addition behind it) and is chosen so that the signed addition meets the sum itself (5, 7: the
+        // doubling branch, which keeps neg) or its negative (6, 8: a cancellation, whose neg the next first point must reset).
+        for (int round = 0; round < 9; ++round) {
             std::vector<G1A> seq;
             for (int i = 0; i < 40; ++i) seq.push_back(pts[sm_next(st) % pts.size()]);
+            std::vector<bool> minus(seq.size(), false);
             if (round == 1) { seq[1] = seq[0]; }                          // P + P -> doubling branch
             if (round == 2) { seq[1] = seq[0].neg(); }                    // P - P -> identity, then keep adding
             if (round == 3) { seq[3] = seq[0]; seq[2] = seq[1]; seq[5] = seq[4].neg(); }
+            if (round >= 4) for (size_t i = 0; i < seq.size(); ++i) minus[i] = (sm_next(st) & 1) != 0;
+            if (round >= 5) {
+                if (seq[0].x == seq[1].x) seq[1] = pts[0].x == seq[0].x ? pts[1] : pts[0];   // the second addition is a plain one: neg is set after it
+                G1X two = G1X::identity();
+                two.add_affine(minus[0] ? seq[0].neg() : seq[0]);
+                two.add_affine(minus[1] ? seq[1].neg() : seq[1]);
+                const G1A sum = two.to_affine();
+                minus[2] = true;
+                seq[2] = (round & 1) ? sum.neg() : sum;   // minus: -(-sum) = sum, the doubling; -(sum), the cancellation
+            }
             Acc30<F30> acc = Acc30<F30>::identity();
             AccParked<F30, ParkedArrayStore<F30>> park;   // the bucket pass's form: coordinates outside the registers, re-ordered products
             park.set_identity();
             G1X ref = G1X::identity();
             for (size_t i = 0; i < seq.size(); ++i) {
+                if (round >= 4) {
+                    const G1A eff = minus[i] ? seq[i].neg() : seq[i];
+                    if (round >= 5 && i == 2) {   // the premises of the crafted step: the parked sum is negated, and the point meets it
+                        const G1A cur = ref.to_affine();
+                        if (!park.neg || park.inf) return 7900 + round;
+                        if (!((round & 1) ? eff == cur : eff == cur.neg())) return 7910 + round;
+                    }
+                    acc.add_affine(to30(eff.x), to30(eff.y));
+                    if ((i + (size_t)(round >> 1)) & 1) park.add_affine_packed(to30(seq[i].x), F30::std_to_r30(seq[i].y), minus[i]);
+                    else park.add_affine_signed(to30(seq[i].x), to30(seq[i].y), minus[i]);
+                    ref.add_affine(eff);
+                    const G1A want = ref.to_affine();
+                    if (round >= 5 && i == 2) {
+                        if ((round & 1) ? (park.inf || !park.neg) : !park.inf) return 7920 + round;   // doubled and still negated / cancelled
+                    }
+                    if (round >= 5 && (round & 1) == 0 && i == 3 && (park.inf || park.neg)) return 7930 + round;   // the first point after a cancellation resets neg
+                    if (!(acc.to_std().to_affine() == want)) return 8000 + round * 100 + (int)i;
+                    if (!(park.gather().to_std().to_affine() == want)) return 7000 + round * 100 + (int)i;
+                    continue;
+                }
                 {   // the packed conditional negation against the limb form's
                     const Fq yw = F30::std_to_r30(seq[i].y);
                     if (!F30::unpack_cond_neg(yw, true).same_limbs(F30::unpack(yw.v).neg2()) || !F30::unpack_cond_neg(yw, false).same_limbs(F30::unpack(yw.v)))
@@ -717,11 +752,43 @@ struct SelfTest {
                 pts2.push_back(run2.mul_bits(k, 32).to_affine());
                 run2.add_affine(gen2);
             }
-            for (int round = 0; round < 3; ++round) {
+            // rounds 3..5: signed additions as in the G1 loop (3: random signs; 4: a doubling, 5: a cancellation while the parked sum is
+            // negated); the one-lane Fq2 has the limb entry only (add_affine_signed)
+            for (int round = 0; round < 6; ++round) {
                 std::vector<G2A> seq;
                 for (int i = 0; i < 24; ++i) seq.push_back(pts2[sm_next(st) % pts2.size()]);
                 if (round == 1) { seq[1] = seq[0]; }
                 if (round == 2) { seq[1] = seq[0].neg(); seq[4] = seq[3]; }
+                if (round >= 3) {
+                    std::vector<bool> minus(seq.size(), false);
+                    for (size_t i = 0; i < seq.size(); ++i) minus[i] = (sm_next(st) & 1) != 0;
+                    if (round >= 4) {
+                        if (seq[0].x == seq[1].x) seq[1] = pts2[0].x == seq[0].x ? pts2[1] : pts2[0];
+                        G2X two = G2X::identity();
+                        two.add_affine(minus[0] ? seq[0].neg() : seq[0]);
+                        two.add_affine(minus[1] ? seq[1].neg() : seq[1]);
+                        minus[2] = true;
+                        seq[2] = round == 4 ? two.to_affine().neg() : two.to_affine();
+                    }
+                    AccParked<F230, ParkedArrayStore<F230>> ps;
+                    ps.set_identity();
+                    G2X ref = G2X::identity();
+                    for (size_t i = 0; i < seq.size(); ++i) {
+                        const G2A eff = minus[i] ? seq[i].neg() : seq[i];
+                        if (round >= 4 && i == 2) {
+                            const G2A cur = ref.to_affine();
+                            if (!ps.neg || ps.inf) return 7950 + round;
+                            if (!(round == 4 ? eff == cur : eff == cur.neg())) return 7960 + round;
+                        }
+                        const F230 px = {to30(seq[i].x.c0), to30(seq[i].x.c1)}, py = {to30(seq[i].y.c0), to30(seq[i].y.c1)};
+                        ps.add_affine_signed(px, py, minus[i]);
+                        ref.add_affine(eff);
+                        if (round >= 4 && i == 2 && (round == 4 ? (ps.inf || !ps.neg) : !ps.inf)) return 7970 + round;
+                        if (round == 5 && i == 3 && (ps.inf || ps.neg)) return 7980 + round;
+                        if (!(ps.gather().to_std().to_affine() == ref.to_affine())) return 7500 + round * 100 + (int)i;
+                    }
+                    continue;
+                }
                 Acc30<F230> acc = Acc30<F230>::identity();
                 AccParked<F230, ParkedArrayStore<F230>> park2;
                 park2.set_identity();

@@ -254,6 +254,11 @@ int msm_window_override();  // env G16_MSM_WINDOW (0 = auto)
 int merged_window_bits(uint64_t n, int scalar_bits, const uint32_t* modulus_words, int mod_nwords);
 int msm_plan_windows(int c, int scalar_bits, const uint32_t* modulus_words, int mod_nwords);
 
+// A bucket with more partial sums than this is combined cooperatively by a workgroup (heavy_reduce_kernel: FEW buckets with MANY partial
+// sums -- the top window's short digit range, repeated scalars); up to this many are added up by one lane (bucket_combine_kernel).
+// 8 until round 5: a bucket-space shard's top-window buckets hold ~2x the mean (224 entries = 8 - 9 segments of 32), thousands of them
+// just over the threshold, and the cooperative kernel -- a 128-lane tree per bucket -- took 0.5 - 0.9 ms per MSM in the tail of the proof.
+static constexpr uint32_t HEAVY_PARTS = 16;
 // digit extraction + bucket sort of one scalar array, shared by every MSM over those scalars
 struct ScalarSort {
     MsmPlan plan;

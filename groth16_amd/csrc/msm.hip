@@ -51,6 +51,7 @@
 #include "internal.hpp"
 #include "msm_common.hpp"
 #include "fp30.hpp"
+#include "acc_store.hpp"
 #include "batch_affine.hpp"
 #include "window_tables.hpp"
 #include <algorithm>
@@ -59,8 +60,6 @@
 namespace g16 {
 
 static constexpr int SORT_THREADS = 1024;
-static constexpr int ACC_THREADS = 64;   // one wave per workgroup: finer re-dispatch granularity.  Same box, full proof at 2^22 (round 3): 64 lanes
-                                         // 79.56 ms (G2 pass 25.87), 128 lanes 80.38 / 80.17 (26.53 / 26.44), 256 lanes 80.81 (26.76); G1 passes equal
 static constexpr int RED_THREADS = 64;
 static constexpr int WIN_THREADS = 256;  // lanes of the per-window reduction
 #ifndef G16_REDUCE_G
@@ -291,11 +290,6 @@ static __global__ __launch_bounds__(SORT_M_THREADS) void bucket_scatter_merged_k
 static constexpr int SCAN_THREADS = 256;
 static constexpr int SCAN_PER_THREAD = 8;
 static constexpr int SCAN_TILE = SCAN_THREADS * SCAN_PER_THREAD;
-// A bucket with more partial sums than this is combined cooperatively by a workgroup (heavy_reduce_kernel: FEW buckets with MANY partial
-// sums -- the top window's short digit range, repeated scalars); up to this many are added up by one lane (bucket_combine_kernel).
-// 8 until round 5: a bucket-space shard's top-window buckets hold ~2x the mean (224 entries = 8 - 9 segments of 32), thousands of them
-// just over the threshold, and the cooperative kernel -- a 128-lane tree per bucket -- took 0.5 - 0.9 ms per MSM in the tail of the proof.
-static constexpr uint32_t HEAVY_PARTS = 16;
 
 // exclusive scan of one value per thread across the workgroup; returns the workgroup total through *total
 __device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* sh, uint32_t* total) {
@@ -587,41 +581,6 @@ static __global__ __launch_bounds__(SORT_THREADS) void bucket_scatter_kernel(con
 // `bases` hold canonical x*R', y*R' packed in 32-bit words (convert_bases30_kernel).
 // DIRECT (batched-affine plan): the walk is over the level-R list itself -- slot e holds an affine point (or the identity),
 // bucket b owns slots [offsets[b] >> off_shift, offsets[b + 1] >> off_shift) -- instead of over sorted entry words.
-// The accumulator's coordinates in LDS (AccParked, fp30.hpp): value v, limb i of lane t.  Limbs are grouped in fours so that a
-// coordinate moves as ds_read_b128 / ds_write_b128 (each lane its own 16 bytes, consecutive lanes consecutive: conflict-free) plus
-// single words for the NL mod 4 tail rows.  4 * NL * 64 words per 64-lane workgroup: 13 KB (NL = 13), i.e. 104 of the CU's 160 KB at
-// two waves per SIMD (eight workgroups per CU).
-template <class F30>
-struct LdsAccStore {
-    static constexpr int NL = F30::PREFIX_LIMBS;
-    static constexpr int QUADS = NL / 4, TAIL = NL % 4;
-    static constexpr int WORDS_PER_VALUE = NL * ACC_THREADS;
-    uint32_t* quad;   // lds + 4 * lane
-    uint32_t* tail;   // lds + 4 * QUADS * ACC_THREADS + lane
-    __device__ __forceinline__ F30 ld(int v) const {
-        asm volatile("" ::: "memory");   // a FRESH read every time: the point of parking is that the value is not kept live
-        uint32_t w[NL];
-        const uint32_t* q = quad + v * WORDS_PER_VALUE;
-        G16_UNROLL for (int g = 0; g < QUADS; ++g) {
-            const uint4 t = *reinterpret_cast<const uint4*>(q + g * 4 * ACC_THREADS);
-            w[4 * g] = t.x; w[4 * g + 1] = t.y; w[4 * g + 2] = t.z; w[4 * g + 3] = t.w;
-        }
-        const uint32_t* r = tail + v * WORDS_PER_VALUE;
-        G16_UNROLL for (int i = 0; i < TAIL; ++i) w[4 * QUADS + i] = r[i * ACC_THREADS];
-        return F30::from_limbs(w);
-    }
-    __device__ __forceinline__ void st(int v, const F30& a) const {
-        uint32_t w[NL];
-        a.get_limbs(w);
-        uint32_t* q = quad + v * WORDS_PER_VALUE;
-        G16_UNROLL for (int g = 0; g < QUADS; ++g)
-            *reinterpret_cast<uint4*>(q + g * 4 * ACC_THREADS) = make_uint4(w[4 * g], w[4 * g + 1], w[4 * g + 2], w[4 * g + 3]);
-        uint32_t* r = tail + v * WORDS_PER_VALUE;
-        G16_UNROLL for (int i = 0; i < TAIL; ++i) r[i * ACC_THREADS] = w[4 * QUADS + i];
-        asm volatile("" ::: "memory");
-    }
-};
-
 // Stores for the reductions' streamed additions (acc_add_streamed, fp30.hpp).
 // An AccRaw record in LDS or global memory as the lane(s) of one task see it: coordinate k of a one-lane field is the k-th F30 of the
 // record; of the lane pair, component (lane parity) of the k-th Fq2.  Identity <=> zz is all-zero limbs (AccRaw).
@@ -882,12 +841,14 @@ __global__ __launch_bounds__(RED_THREADS, F30::LANES_PER_TASK == 1 ? G16_FIRST_S
     if (np < 2 || np > HEAVY_PARTS) return;   // (heavy buckets were combined into [t0] by heavy_reduce_kernel)
     const RawAccStore<F30> mine{&partials[t0]};
     bool inf = mine.inf();
-    const bool was = inf;
     for (uint32_t q = 1; q < np; ++q) {
         const RawAccStore<F30> src{&partials[t0 + q]};
         acc_add_streamed<F30>(mine, inf, src, src.inf());
     }
-    if (inf && !was) mine.set_inf();
+    // Several additions into one slot: an identity first partial may have been overwritten by a point that a later partial cancelled
+    // ([O, P, -P]), which leaves the flag set and P's zz in the record -- so the identity is written whenever the flag ends set, not
+    // only when the slot held a point at the start.  (The trees of heavy_reduce_kernel / window_reduce_kernel add once per step.)
+    if (inf) mine.set_inf();
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -119,6 +119,75 @@ struct UnitApi {
         return G16_OK;
     }
 
+    // The reductions alone on caller-made partial sums (test hook, g16_dev_msm_reduce_lab): a plan, a ScalarSort -- slot offsets and
+    // the heavy list by bucket_slots_kernel's rule for a segment length of 1: one partial per entry, more than HEAVY_PARTS is heavy --
+    // and the buffers are filled here; the kernels are launched by msm_reduce and the sums folded by fold_windows, as in a proof.
+    template <class F>
+    static int msm_reduce_lab(g16_ctx* ctx, int merged, int c, int groups, int G, const uint32_t* nparts, const uint32_t* records,
+                              uint64_t n_records, uint32_t* first_slots, uint64_t* out_affine) {
+        typedef Affine<F> A;
+        typedef XYZZ<F> X;
+        typedef Fp30<typename Fq::Params> B30;
+        typedef AccRaw<typename std::conditional<std::is_same<F, Fq>::value, B30, Fp2x30<typename Fq::Params>>::type> Raw;
+        constexpr size_t REC_WORDS = (std::is_same<F, Fq>::value ? 4 : 8) * B30::NL;
+        static_assert(sizeof(Raw) == REC_WORDS * sizeof(uint32_t), "a record is its limbs, nothing else");
+        if (c < 2 || c > 16 || groups < 1 || groups > 32 || (G != 8 && G != 16 && G != 32)) return G16_ERR_BAD_ARG;
+        ScalarSort ss;
+        MsmPlan& plan = ss.plan;
+        plan.c = c;
+        plan.W = groups;
+        plan.groups = groups;
+        plan.merged = merged != 0;
+        plan.B = 1u << (c - 1);
+        plan.G = (uint32_t)G;
+        plan.Lmax = 1;
+        plan.chunk = 1024;
+        for (int k = 0; k < 10; ++k) plan.K[k] = 0;
+        if (plan.outputs() > MSM_MAX_OUTPUTS) return G16_ERR_BAD_ARG;
+        const uint32_t M = plan.buckets();
+        std::vector<uint32_t> task_off((size_t)M + 1), heavy((size_t)M + 1, 0u);
+        uint64_t total = 0;
+        for (uint32_t b = 0; b < M; ++b) {
+            task_off[b] = (uint32_t)total;
+            total += nparts[b];
+            if (nparts[b] > HEAVY_PARTS) heavy[1 + heavy[0]++] = b;
+            if (total >= ((uint64_t)1 << 31)) return G16_ERR_BAD_LENGTH;
+        }
+        task_off[M] = (uint32_t)total;
+        if (total != n_records) return G16_ERR_BAD_LENGTH;
+        hipStream_t st = ctx->stream;
+        DrainOnError drain(ctx);
+        ctx->reset_arena();
+        Raw *d_partials = nullptr, *d_chunk = nullptr;
+        MsmBuffers<F> buf;
+        G16_TRY(ctx->arena.alloc_n((size_t)M + 1, &ss.task_off));
+        G16_TRY(ctx->arena.alloc_n((size_t)M + 1, &ss.heavy));
+        G16_TRY(ctx->arena.alloc_n(n_records ? (size_t)n_records : 1, &d_partials));
+        G16_TRY(ctx->arena.alloc_n((size_t)plan.chunks() * plan.groups * 2, &d_chunk));
+        G16_TRY(ctx->arena.alloc_n((size_t)plan.outputs(), &buf.window_sums));
+        buf.partials = d_partials;
+        buf.chunk_out = d_chunk;
+        ss.max_tasks = (uint32_t)total;
+        G16_HIP_TRY(hipMemcpyAsync(ss.task_off, task_off.data(), ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        G16_HIP_TRY(hipMemcpyAsync(ss.heavy, heavy.data(), ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (n_records) G16_HIP_TRY(hipMemcpyAsync(d_partials, records, (size_t)n_records * sizeof(Raw), hipMemcpyHostToDevice, st));
+        G16_TRY((msm_reduce<F>(buf, ss, st)));
+        std::vector<X> hws(plan.outputs());
+        std::vector<uint32_t> after((size_t)n_records * REC_WORDS);
+        G16_HIP_TRY(hipMemcpyAsync(hws.data(), buf.window_sums, sizeof(X) * plan.outputs(), hipMemcpyDeviceToHost, st));
+        if (n_records) G16_HIP_TRY(hipMemcpyAsync(after.data(), d_partials, (size_t)n_records * sizeof(Raw), hipMemcpyDeviceToHost, st));
+        G16_HIP_TRY(hipStreamSynchronize(st));
+        drain.dismiss();
+        for (uint32_t b = 0; b < M; ++b) {
+            uint32_t* o = first_slots + (size_t)b * REC_WORDS;
+            if (nparts[b]) memcpy(o, after.data() + (size_t)task_off[b] * REC_WORDS, sizeof(Raw));
+            else memset(o, 0, sizeof(Raw));
+        }
+        const A res = fold_windows<F>(hws.data(), plan).to_affine();
+        memcpy(out_affine, &res, sizeof(A));
+        return G16_OK;
+    }
+
     static int ntt_api(g16_ctx* ctx, uint64_t* data, int log_n, int inverse, int coset) {
         if (log_n < 0 || log_n > 30) return G16_ERR_DEGREE_TOO_LARGE;
         hipStream_t st = ctx->stream;

@@ -478,9 +478,28 @@ int g16_host_selftest(int curve, uint64_t seed, int iters);
  *   72 G2 lane pair (21 -> 9; device only).  A field element takes C slots (1 for Fq, 2 for Fq2).  in: x y zz zzz raw lazy limbs |
  *   a flag slot: word 0 the accumulator is the identity, word 1 the number of points, word 2 + j point j is the identity | x y of
  *   three affine points (limbs, below 2 p).  out: x y zz zzz canonical in the packed form's words | word 0: the result is the identity
+ *   parked accumulator (Fq only): the bucket pass's own form -- AccParked, coordinates parked in LDS in the kernel's layout, signed
+ *   additions from packed y, the flush's gather().  73 parked_chain_g1 (11 -> 5 slots; the host twin parks in plain memory),
+ *   74 parked_chain_g2_pair (lane pair, 21 -> 9; device only).  in: x y zz zzz raw lazy limbs AS PARKED (the sum is their negative
+ *   when neg is set) | a flag slot: word 0 the accumulator is the identity, word 1 the initial neg, word 2 the number of points,
+ *   word 3 + j point j is the identity, word 6 + j point j is subtracted | x y of three affine points (canonical, the packed form's
+ *   words).  out: as 70..72
  * G16_ERR_BAD_ARG for an unknown form or one the field does not have, n == 0 or n > 2^22. */
 int g16_dev_fp30_op(g16_ctx* ctx, int field, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
 int g16_host_fp30_op(int curve, int field, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
+
+/* ---- the reduction lab (test hook): the MSM reductions alone, on caller-made partial sums ----
+ * Fills a plan (merged: 0 per-window fold, 1 merged fold; `groups` groups of 2^(c-1) buckets, 2 <= c <= 16; G = 8, 16 or 32 buckets
+ * per lane of the bucket reduction), the partial-sum slot offsets and the heavy-bucket list from nparts[groups * 2^(c-1)] (partial sums
+ * per bucket), uploads `records` -- n_records = sum of nparts records in bucket order, each x y zz zzz as raw lazy 30-bit limbs (NL words
+ * per Fq component: 4 NL words for G1, x.c0 x.c1 y.c0 ... 8 NL words for G2; the identity is an all-zero zz) -- and runs the prover's
+ * reduction (heavy combine, bucket combine, bucket reduction, window reduction) and the host fold.  Preconditions are those the bucket
+ * pass guarantees (x < 7.5 p, y < 4 p, zz, zzz < 1.8 p per component); nothing is checked.  The suite runs c = 6 with two groups
+ * and every G; other window sizes are accepted as make_msm_plan accepts them and are not exercised by a test.
+ * first_slots: groups * 2^(c-1) records, every bucket's first slot after the combine stages (zeros for a bucket without partial sums);
+ * out_affine: the folded sum  sum_w 2^(c w) sum_b (b + 1) S_(w,b)  (per-window)  or  sum_k (k + 1) S_k over the bucket key k (merged). */
+int g16_dev_msm_reduce_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, const uint32_t* nparts, const uint32_t* records,
+                           uint64_t n_records, uint32_t* first_slots, uint64_t* out_affine);
 
 /* ---- verifier (src/verifier.rs:13-76, src/lib.rs:84-96) ------------------------------------------------------------
  * GT values cross as 12 Fq in arkworks' order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1 (Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - xi)),

@@ -205,9 +205,10 @@ LAB = {
     "pair_mul_v": (60, 4, 2), "pair_sqr_v": (61, 2, 2), "pair_sqr_sub_x3_v": (62, 6, 2), "pair_mul_add_fused": (63, 8, 2),
     "pair_mul_sub": (64, 8, 2), "pair_mul_add_fused_v": (65, 8, 2),
     "acc_chain_g1": (70, 11, 5), "acc_chain_g2": (71, 21, 9), "acc_chain_g2_pair": (72, 21, 9),
+    "parked_chain_g1": (73, 11, 5), "parked_chain_g2_pair": (74, 21, 9),
 }
-FQ_ONLY = ("fp2x_", "pair_", "acc_")
-DEVICE_ONLY = ("acc_chain_g2_pair",)   # the lane pair's accumulator needs its lanes: the host twin does not have it
+FQ_ONLY = ("fp2x_", "pair_", "acc_", "parked_")
+DEVICE_ONLY = ("acc_chain_g2_pair", "parked_chain_g2_pair")   # the lane pair's accumulators need their lanes: the host twin does not have them
 
 
 def lab_forms(f, host=False):
@@ -409,6 +410,8 @@ def lab_cases(f, form, seed=1):
         return out
     if form.startswith("acc_chain"):
         return acc_cases(f, form, rng)
+    if form.startswith("parked_chain"):
+        return parked_cases(f, form, rng)
     raise KeyError(form)
 
 
@@ -498,4 +501,153 @@ def acc_cases(f, form, rng):
         A = pts[1 + rng.randrange(40)]
         chain = [pts[rng.randrange(41)] for _ in range(1 + n % 3)]
         out.append(case(A, scale(), ks[rng.randrange(len(ks))], kys[rng.randrange(len(kys))], chain, n % 2, "%s random chain %d" % (form, n)))
+    return out
+
+
+# ---- the bucket pass's own accumulator: parked coordinates, signed additions, a sign that gather() resolves ------------------------
+def parked_cases(f, form, rng):
+    """AccParked (fp30.hpp) as bucket_accumulate30_kernel runs it.  The parked coordinates are lazy like Acc30's (x < 7.5 p, y < 3.5 p,
+    zz and zzz < 1.8 p) and may be those of -A (`neg`): a hot-path addition leaves the negated sum, so the next point enters with its
+    sign flipped -- together with the signed digit's own sign (`minus`) -- and gather() negates y once, at the flush.  The cold
+    branches (first point, doubling) keep the sign they find, a cancellation leaves `neg` behind beside the identity flag and the
+    first point after it must reset it.  Points come as the window table holds them: canonical, x and y packed in words.
+
+    A case is written down by the point the accumulator REPRESENTS (A), the initial neg, and the chain [(Q, minus)]; the tuple holds
+    the coordinates as parked, i.e. those of -A when neg is set.  Expected: pymodel's group law, A + sum +-Q, compared as a canonical
+    affine point.  Every step a case names a doubling or a cancellation is asserted to be one with the model alone."""
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import pymodel
+    cp = pymodel.CURVES[f.curve]
+    g2 = form != "parked_chain_g1"
+    G = pymodel.groups(cp)[1 if g2 else 0]
+    F, p, NL = G.F, f.p, f.NL
+    C = 2 if g2 else 1
+    comps = (lambda e: list(e)) if g2 else (lambda e: [e])
+    elem = (lambda c: (c[0], c[1])) if g2 else (lambda c: c[0])
+    gen = cp.g2 if g2 else cp.g1
+    pts = [None, gen]
+    for _ in range(40):
+        pts.append(G.add(pts[-1], gen))
+    rinv = pow(f.R, -1, p)
+
+    def lazy(e, ks):       # Montgomery form, component c as the representative r + ks[c] p
+        return [f.limbs(c * f.R % p + k * p) for c, k in zip(comps(e), ks)]
+
+    def packed(e):         # Montgomery form, canonical, in the packed form's words
+        return [f.words(c * f.R % p) for c in comps(e)]
+
+    def scale():
+        return elem([rng.randrange(1, p) for _ in range(C)])
+
+    def signed(Q, minus):
+        return G.neg(Q) if (minus and Q is not None) else Q
+
+    def case(A, neg, kx, ky, chain, what, steps=(), kz=0):
+        """chain: [(Q or None, minus)]; steps: what each step must be by the model -- "dbl", "cancel", "first" or None;
+        kz = 1: zz and zzz as r + p, with a scale whose residues leave that below 1.8 p"""
+        if A is None:
+            acc, inf = [[0] * NL] * (4 * C), 1
+        else:
+            Ap = G.neg(A) if neg else A
+            while True:
+                z = scale()
+                zz = F.sqr(z)
+                zzz = F.mul(zz, z)
+                if not kz or all(5 * (c * f.R % p + p) < 9 * p for e in (zz, zzz) for c in comps(e)):
+                    break
+            acc, inf = lazy(F.mul(Ap[0], zz), kx) + lazy(F.mul(Ap[1], zzz), ky) + lazy(zz, [kz] * C) + lazy(zzz, [kz] * C), 0
+        flags = [inf, int(neg), len(chain)] + [1 if j < len(chain) and chain[j][0] is None else 0 for j in range(3)]
+        flags += [int(chain[j][1]) if j < len(chain) else 0 for j in range(3)]
+        slots = acc + [(flags + [0] * NL)[:NL]]
+        want = A
+        for j in range(3):
+            Q, minus = chain[j] if j < len(chain) else (None, 0)
+            if Q is None:
+                slots += [[0] * NL] * (2 * C)
+                assert j >= len(steps) or steps[j] is None, what
+                continue
+            slots += packed(Q[0]) + packed(Q[1])
+            sQ = signed(Q, minus)
+            if j < len(steps) and steps[j] is not None:   # the collision the case is named after really happens, by the model alone
+                if steps[j] == "dbl":
+                    assert want is not None and sQ == want, "%s: step %d is no doubling" % (what, j)
+                elif steps[j] == "cancel":
+                    assert want is not None and sQ == G.neg(want) and G.add(want, sQ) is None, "%s: step %d is no cancellation" % (what, j)
+                elif steps[j] == "first":
+                    assert want is None, "%s: step %d does not meet the identity" % (what, j)
+                else:
+                    assert steps[j] == "hot" and want is not None and sQ[0] != want[0], "%s: step %d is no plain addition" % (what, j)
+            want = G.add(want, sQ)
+
+        def check(out, want=want, what=what):
+            got_inf = int(out[4 * C][0])
+            if want is None:
+                assert got_inf == 1, "%s: expected the identity, got a point" % what
+                return
+            assert got_inf == 0, "%s: got the identity, expected %s" % (what, want)
+            v = [[f.from_words(out[e * C + c]) for c in range(C)] for e in range(4)]
+            assert all(x < p for e in v for x in e), "%s: a coordinate is not canonical" % what
+            x, y, zz, zzz = [elem([c * rinv % p for c in e]) for e in v]
+            got = (F.mul(x, F.inv(zz)), F.mul(y, F.inv(zzz)))
+            assert got == want, "%s: got %s want %s" % (what, got, want)
+        return LabCase(slots, check, form)
+
+    out = []
+    ks = [[k] * C for k in range(7)] + ([[0, 6], [5, 1]] if g2 else [])
+    kys = [[k] * C for k in range(3)] + ([[0, 2]] if g2 else [])
+    k0, y0 = ks[0], kys[0]
+    i = 0
+    # P + P and P - P for every admissible representative, from either parked sign and with either digit sign: the point is chosen
+    # so that the SIGNED addition meets +-(the represented point)
+    for kx in ks:
+        for ky in kys:
+            for neg in (0, 1):
+                for minus in (0, 1):
+                    A = pts[1 + i % 20]
+                    i += 1
+                    tail = "neg = %d, minus = %d, x + %s p, y + %s p" % (neg, minus, kx, ky)
+                    out.append(case(A, neg, kx, ky, [(signed(A, minus), minus)], "%s A + A (doubling), %s" % (form, tail), ["dbl"]))
+                    out.append(case(A, neg, kx, ky, [(signed(G.neg(A), minus), minus)], "%s A - A (cancellation), %s" % (form, tail), ["cancel"]))
+    P, Q, S, T = pts[3], pts[7], pts[11], pts[13]
+    for neg in (0, 1):   # (an identity accumulator keeps the neg a flush or a cancellation left behind)
+        for minus in (0, 1):
+            t = "neg = %d, minus = %d" % (neg, minus)
+            out.append(case(None, neg, None, None, [(P, minus)], "%s first point into the identity, %s" % (form, t), ["first"]))
+            out.append(case(None, neg, None, None, [(P, minus), (Q, 1 - minus)], "%s first point then a hot addition, %s" % (form, t), ["first", "hot"]))
+            # the cold branch keeps neg: the addition after a doubling must still take the parked sign
+            out.append(case(P, neg, ks[2], kys[1], [(signed(P, minus), minus), (Q, minus)],
+                            "%s doubling then an addition, %s" % (form, t), ["dbl", "hot"]))
+            out.append(case(P, neg, ks[5], kys[2], [(signed(P, minus), minus), (Q, 1 - minus), (S, minus)],
+                            "%s doubling then two additions, %s" % (form, t), ["dbl", "hot", "hot"]))
+            # a cancellation leaves neg behind: the first point after it must reset it
+            out.append(case(P, neg, ks[1], kys[0], [(signed(G.neg(P), minus), minus), (Q, minus)],
+                            "%s cancellation then an addition, %s" % (form, t), ["cancel", "first"]))
+            out.append(case(P, neg, ks[4], kys[1], [(signed(G.neg(P), minus), minus), (Q, 1 - minus), (S, minus)],
+                            "%s cancellation then two additions, %s" % (form, t), ["cancel", "first", "hot"]))
+            # a doubling / a cancellation reached after one hot addition (neg has toggled once)
+            PQ = G.add(P, signed(Q, minus))
+            out.append(case(P, neg, ks[3], kys[2], [(Q, minus), (signed(PQ, minus), minus)],
+                            "%s hot addition then a doubling, %s" % (form, t), ["hot", "dbl"]))
+            out.append(case(P, neg, ks[6], kys[0], [(Q, minus), (signed(G.neg(PQ), 1 - minus), 1 - minus), (T, minus)],
+                            "%s hot addition, a cancellation, then a first point, %s" % (form, t), ["hot", "cancel", "first"]))
+            # gather() after an odd and an even number of hot additions
+            for n in (1, 2, 3):
+                chain = [((Q, S, T)[j], (minus + j) % 2) for j in range(n)]
+                out.append(case(P, neg, ks[n], kys[n - 1], chain, "%s %d hot additions, %s" % (form, n, t), ["hot"] * n))
+            # identity points inside the chain are skipped and do not toggle anything
+            out.append(case(P, neg, k0, y0, [(None, minus), (Q, minus), (None, 1 - minus)], "%s O, Q, O, %s" % (form, t)))
+            out.append(case(P, neg, k0, y0, [(Q, minus), (None, 1), (S, 1 - minus)], "%s Q, O, S, %s" % (form, t)))
+            out.append(case(P, neg, k0, y0, [(None, 1), (None, 0), (None, 1)], "%s O, O, O, %s" % (form, t)))
+            out.append(case(None, neg, None, None, [(None, minus), (None, minus), (Q, minus)], "%s identity + O + O + Q, %s" % (form, t), [None, None, "first"]))
+            # zz, zzz in the upper part of their range (r + p < 1.8 p): U2 - x and S2 - y from the largest admissible operands
+            tz = "zz + p, zzz + p, " + t
+            out.append(case(P, neg, ks[6], kys[2], [(signed(P, minus), minus)], "%s A + A (doubling), %s" % (form, tz), ["dbl"], kz=1))
+            out.append(case(P, neg, ks[6], kys[2], [(signed(G.neg(P), minus), minus)], "%s A - A (cancellation), %s" % (form, tz), ["cancel"], kz=1))
+            out.append(case(P, neg, ks[6], kys[2], [(Q, minus), (S, 1 - minus)], "%s two hot additions, %s" % (form, tz), ["hot", "hot"], kz=1))
+    out.append(case(None, 0, None, None, [], form + " identity, empty chain"))
+    out.append(case(P, 1, ks[6], kys[2], [], form + " empty chain, neg = 1: gather() alone"))
+    for n in range(32):
+        A = pts[1 + rng.randrange(40)]
+        chain = [(pts[rng.randrange(41)], rng.randrange(2)) for _ in range(1 + n % 3)]
+        out.append(case(A, rng.randrange(2), ks[rng.randrange(len(ks))], kys[rng.randrange(len(kys))], chain, "%s random chain %d" % (form, n)))
     return out

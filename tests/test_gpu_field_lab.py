@@ -4,7 +4,8 @@ their DPP moves live -- the CPU tier (test_fips_asm_emulated.py) can only emulat
 
 Product forms, the carry / subtraction helpers and the canonicalisers are compared limb for limb, the zero tests as flags, the Fq2
 forms as residues with the promised bound per component, the accumulator forms (a lazy XYZZ accumulator through a chain of mixed
-additions: G1, G2 in one lane and G2 on the lane pair) as canonical affine points against pymodel's group law.  Every form is
+additions: G1, G2 in one lane and G2 on the lane pair; and the bucket pass's own parked, sign-tracking accumulator in its LDS layout
+through signed additions and the flush's gather(): G1 and G2 on the lane pair) as canonical affine points against pymodel's group law.  Every form is
 launched with n = 1, 63, 64, 65 tuples (first and last lane, a partial and a full wavefront, a second workgroup) and once with
 every case, cycled to more than two thousand tuples."""
 import ctypes as C
@@ -47,7 +48,7 @@ def run_batch(lib, ctx, f, form, cases):
         try:
             c.check(o)
         except AssertionError as e:
-            lanes = (2 * i, 2 * i + 1) if form.startswith("pair_") else (i,)
+            lanes = (2 * i, 2 * i + 1) if form.startswith("pair_") or form.endswith("_pair") else (i,)
             raise AssertionError("%s %s, n = %d, tuple %d (lanes %s): %s" % (f.name, form, len(cases), i, lanes, e)) from None
 
 
