@@ -401,9 +401,16 @@ struct Pairing {
         }
         return true;
     }
+    // Straight-line, all six Fq2 comparisons evaluated.  Not a loop `eq = eq && a.coef(k) == b.coef(k)`: left rolled on the device,
+    // that loop (a per-lane flag carried round it beside the early exits of the zero tests) answered true for values that differ in
+    // c0 only, where the host build of the same text answered false -- the tower lab's `equal` form found it.
     G16_HD static bool equal(const F12& a, const F12& b) {
-        bool eq = true;
-        for (int k = 0; k < 6; ++k) eq = eq && a.coef(k) == b.coef(k);
+        bool eq = a.c0.c0 == b.c0.c0;
+        eq &= a.c0.c1 == b.c0.c1;
+        eq &= a.c0.c2 == b.c0.c2;
+        eq &= a.c1.c0 == b.c1.c0;
+        eq &= a.c1.c1 == b.c1.c1;
+        eq &= a.c1.c2 == b.c1.c2;
         return eq;
     }
     // GT value -> 12 Fq in arkworks' order and Montgomery form (Fq::N / 2 64-bit limbs each)

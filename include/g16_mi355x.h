@@ -488,6 +488,32 @@ int g16_host_selftest(int curve, uint64_t seed, int iters);
 int g16_dev_fp30_op(g16_ctx* ctx, int field, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
 int g16_host_fp30_op(int curve, int field, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
 
+/* ---- the tower lab (test hooks): ONE operation of the pairing tower (csrc/pairing.hpp) on raw limbs ----
+ * g16_dev_pairing_op runs one tuple per lane on the ctx's (first) GPU and its curve, g16_host_pairing_op the same code compiled for
+ * the host.  A slot is NL 32-bit words of the curve's Fq (13 for BLS12-381, 9 for BN254).  An Fq operand is RAW 30-bit limbs in the
+ * R' Montgomery radix, ANY representative below 2 p (loaded straight into Q30::a); an Fq result is the raw limbs the operation left,
+ * not canonicalised.  Fq2 is 2 slots (c0 c1), Fq6 is 6, Fq12 is 12, in arkworks' order c0.c0.c0 ... c1.c2.c1.  A flag, a small
+ * integer or an exponent sits in the low words of a slot; "words" is the standard (arkworks) Montgomery form's 32-bit words padded
+ * with zeros.  operands: n tuples of `in` slots; out: n tuples of `out` slots.  form (in -> out slots):
+ *   Q30   0 a + b (2->1)  1 a - b  2 neg (1)  3 dbl (1)  4 a * b (2)  5 sqr (1)  6 is_zero (1 -> flag)  7 a == b (2 -> flag)
+ *         8 inverse (1; of a zero residue: 0)  9 from_std then to_std (words -> words)
+ *   T2    10 a + b (4->2)  11 a - b  12 neg (2->2)  13 conj  14 dbl  15 scale(a, k) (3->2)  16 mul_outlined (4->2)
+ *         17 sqr_outlined (2)  18 inverse (2; of zero: zero)  19 mul_by_xi (2)  20 a == b (4 -> flag)
+ *   T6    30 a + b (12->6)  31 a - b  32 neg (6->6)  33 mul_outlined (12->6)  34 mul_by_v (6)  35 inverse (6; of zero: zero)
+ *   T12   40 mul_outlined (24->12)  41 sqr_outlined (12->12)  42 cyc_sqr_outlined  43 conj  44 inverse (of zero: zero)
+ *         45 is_zero (12 -> flag)
+ *   Pairing   50 frob(a, j): a | j = 1, 2, 3 in word 0 (13->12)  51 equal(a, b) (24 -> flag)  52 store_gt (12 -> 12 words)
+ *         53 load_gt then store_gt (12 words -> 12 words)  54 ell(f, coeffs, P): f | c0 c1 c2 (Fq2 each) | P.x P.y (20->12)
+ *         55 Proj::dbl_step: T = x y z (6 -> T' and c0 c1 c2: 12)  56 Proj::add_step: T | the affine addend x y (10->12)
+ *         57 frob_twist(q, k): q.x q.y | k = 1, 2 in word 0 (5->4)  58 cyc_pow: a | the exponent's low and high word, > 0 (13->12)
+ *         59 cyc_pow_bits: a | words 0..7 the exponent, word 8 the bit count <= 256 (13->12)  60 exp_by_x (12->12)
+ *         61 final_exp (12 -> 12 and a flag slot: the returned bool; the value is zero where it is false)
+ *         62 g1_on_curve: x y words (2 -> flag)  63 g2_on_curve: x.c0 x.c1 y.c0 y.c1 words (4 -> flag)
+ * Preconditions are those of pairing.hpp (42, 58..60: a in the cyclotomic subgroup); nothing is checked.
+ * G16_ERR_BAD_ARG for an unknown form, a null pointer, n == 0 or n > 2^22. */
+int g16_dev_pairing_op(g16_ctx* ctx, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
+int g16_host_pairing_op(int curve, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
+
 /* ---- the reduction lab (test hook): the MSM reductions alone, on caller-made partial sums ----
  * Fills a plan (merged: 0 per-window fold, 1 merged fold; `groups` groups of 2^(c-1) buckets, 2 <= c <= 16; G = 8, 16 or 32 buckets
  * per lane of the bucket reduction), the partial-sum slot offsets and the heavy-bucket list from nparts[groups * 2^(c-1)] (partial sums

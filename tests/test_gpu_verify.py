@@ -6,7 +6,7 @@ import pytest
 import pairing_model as pmod
 import pymodel as pm
 from helpers import g1_to_arr, g2_to_arr, mont_to_ints, ints_to_mont, oracle
-from verify_cases import oracle_case, tamperings, wrong_input
+from verify_cases import identity_ic_case, nonsubgroup_pairs_with_model, oracle_case, tamperings, torsion_pair, wrong_input
 
 import groth16_amd as g
 from groth16_amd.serialize import proof_from_bytes, proof_to_bytes
@@ -39,6 +39,80 @@ def test_gpu_pairing_equals_host_and_model(setup):
     got = prover.pairing(g1s, g2s)
     assert (got == g.host_pairing(name, g1s, g2s)).all()
     assert (got == pmod.to_ark_limbs(name, pmod.pairing_product(name, pairs))).all()
+
+
+def test_gpu_pairing_outside_the_subgroups_equals_host_and_model(setup):
+    """the plain verifier accepts any on-curve B, so its Miller loop runs on S + T_l (T_l of prime order l in the cofactor), and on
+    BLS12-381 on a G1 point outside its subgroup: GPU == host == the big-int model, which never divides by zero there"""
+    name, prover, pvk, vk, proofs, x, cp = setup
+    for label, pairs, want in nonsubgroup_pairs_with_model(name):
+        g1s, g2s = g1_to_arr([p for p, _ in pairs], cp), g2_to_arr([q for _, q in pairs], cp)
+        got = prover.pairing(g1s, g2s)
+        assert (got == g.host_pairing(name, g1s, g2s)).all(), label
+        assert (got == want).all(), label
+
+
+def pairing_outcome(call):
+    """the GT limbs, or the exception's type where the entry point reports a status"""
+    try:
+        return list(call())
+    except g.G16Error as e:
+        return type(e)
+
+
+def test_gpu_pairing_of_a_pure_torsion_point_equals_host(setup):
+    """Q = T_l alone (l = 13 on BLS12-381, 10069 on BN254).  On BLS12-381 the loop's chain of multiples reaches a multiple of l: the
+    projective T passes through z = 0 and the loop value becomes 0, reported as an unexpected identity.  The big-int model works on
+    affine points and defines no value there, so the GPU is held to the host build of the same templates, bit for bit."""
+    name, prover, pvk, vk, proofs, x, cp = setup
+    l, P, T, hits = torsion_pair(name)
+    g1s, g2s = g1_to_arr([P], cp), g2_to_arr([T], cp)
+    got = pairing_outcome(lambda: prover.pairing(g1s, g2s))
+    assert got == pairing_outcome(lambda: g.host_pairing(name, g1s, g2s))
+    if hits:
+        assert got is g.UnexpectedIdentity
+
+
+def test_gpu_cancelling_pairs_and_the_empty_product_give_the_unit(setup):
+    name, prover, pvk, vk, proofs, x, cp = setup
+    G1, G2 = pm.groups(cp)
+    one = pmod.to_ark_limbs(name, pm.Fq12(cp).one)
+    P, Q = G1.mul(cp.g1, 0x5EED), G2.mul(cp.g2, 0xF00D)
+    for ps, qs in (([P, G1.neg(P)], [Q, Q]), ([P, P], [Q, G2.neg(Q)])):
+        g1s, g2s = g1_to_arr(ps, cp), g2_to_arr(qs, cp)
+        assert (prover.pairing(g1s, g2s) == one).all()
+        assert (g.host_pairing(name, g1s, g2s) == one).all()
+    L = cp.fq_limbs64
+    assert (prover.pairing(np.zeros((0, 2 * L), np.uint64), np.zeros((0, 4 * L), np.uint64)) == one).all()   # n_pairs = 0
+
+
+def test_identity_ic(setup):
+    """gamma_abc_g1 = [-k G, G] with the public input k: the prepared input is the identity (ic_id in verify_batch_kernel, an
+    identity S_IC in the aggregate's tail) and its pair contributes nothing; with k + 1 it is G and the equation fails"""
+    name, prover, _, _, _, _, cp = setup
+    vk, proofs, x_good, x_bad, cp = identity_ic_case(name)
+    n = len(proofs)
+    flat = np.stack(proofs)
+    pvk = prover.prepare_verifying_key(vk)
+    try:
+        assert list(prover.verify_verdicts(pvk, flat, [x_good] * n)) == [1] * n
+        assert list(prover.verify_verdicts(pvk, flat, [x_bad] * n)) == [0] * n
+        assert list(prover.verify_verdicts(pvk, flat, [x_good, x_bad] + [x_good] * (n - 2))) == [1, 0] + [1] * (n - 2)
+        for p in proofs:
+            assert host_verdict(name, vk, p, x_good) == 1 and host_verdict(name, vk, p, x_bad) == 0
+        assert prover.verify_aggregate_verdict(pvk, flat, [x_good] * n) == 1
+        assert prover.verify_aggregate_verdict(pvk, flat, [x_bad] * n) == 0
+        assert prover.verify_aggregate_verdict(pvk, flat[:1], [x_good]) == 1
+        assert prover.verify_aggregate_verdict(pvk, flat[:1], [x_bad]) == 0
+        # the same through prepared inputs: an all-zero point is the identity, G is what k + 1 prepares
+        L = cp.fq_limbs64
+        zero, gen = np.zeros(2 * L, np.uint64), g1_to_arr([cp.g1], cp)[0]
+        assert (prover.prepare_inputs(pvk, x_good).reshape(-1) == zero).all() and (prover.prepare_inputs(pvk, x_bad).reshape(-1) == gen).all()
+        from groth16_amd.verifier import verify_batch_prepared
+        assert list(verify_batch_prepared(prover._ctx, pvk, flat, np.stack([zero] * n))) == [1] * n
+        assert list(verify_batch_prepared(prover._ctx, pvk, flat, np.stack([zero, gen] + [zero] * (n - 2)))) == [1, 0] + [1] * (n - 2)
+    finally:
+        pvk.close()
 
 
 def test_alpha_beta_equals_model(setup):

@@ -10,7 +10,7 @@ import pytest
 import pairing_model as pmod
 import pymodel as pm
 from helpers import g1_to_arr, g2_to_arr
-from verify_cases import oracle_case, pm_proof, pm_vk, pymodel_case, tamperings
+from verify_cases import identity_ic_case, nonsubgroup_pairs_with_model, oracle_case, pm_proof, pm_vk, pymodel_case, tamperings, torsion_pair
 
 import groth16_amd as g
 
@@ -57,6 +57,60 @@ def test_host_pairing_of_nothing_is_one(name):
     cp = pm.CURVES[name]
     got = g.host_pairing(name, np.zeros((0, 2 * cp.fq_limbs64), np.uint64), np.zeros((0, 4 * cp.fq_limbs64), np.uint64))
     assert (got == pmod.to_ark_limbs(name, pm.Fq12(cp).one)).all()
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_host_pairing_outside_the_subgroups_equals_model(name):
+    """the plain verifier accepts any on-curve B: the Miller loop on S + T_l (and on BLS12-381 a G1 point outside its subgroup)"""
+    cp = pm.CURVES[name]
+    for label, pairs, want in nonsubgroup_pairs_with_model(name):
+        got = g.host_pairing(name, g1_to_arr([p for p, _ in pairs], cp), g2_to_arr([q for _, q in pairs], cp))
+        assert (got == want).all(), label
+
+
+def pairing_outcome(call):
+    """the GT limbs, or the exception's type where the entry point reports a status"""
+    try:
+        return list(call())
+    except g.G16Error as e:
+        return type(e)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_host_pairing_of_a_pure_torsion_point_is_deterministic(name):
+    """Q = T_l alone: on BLS12-381 (l = 13) the chain of multiples reaches [13 k] Q, the projective T passes through z = 0 and the
+    loop value becomes 0, which the entry point reports as an unexpected identity.  The big-int model works on affine points and
+    defines no value there, so this pins the outcome only: the same on every call (tests/test_gpu_verify.py: and on the GPU)."""
+    cp = pm.CURVES[name]
+    l, P, T, hits = torsion_pair(name)
+    assert hits == (name == "bls12_381")
+    a, b = g1_to_arr([P], cp), g2_to_arr([T], cp)
+    first = pairing_outcome(lambda: g.host_pairing(name, a, b))
+    assert first == pairing_outcome(lambda: g.host_pairing(name, a, b))
+    if hits:
+        assert first is g.UnexpectedIdentity
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_host_cancelling_pairs_give_the_unit(name):
+    cp = pm.CURVES[name]
+    G1, G2 = pm.groups(cp)
+    P, Q = G1.mul(cp.g1, 0x5EED), G2.mul(cp.g2, 0xF00D)
+    got = g.host_pairing(name, g1_to_arr([P, G1.neg(P)], cp), g2_to_arr([Q, Q], cp))
+    assert (got == pmod.to_ark_limbs(name, pm.Fq12(cp).one)).all()
+    got = g.host_pairing(name, g1_to_arr([P, P], cp), g2_to_arr([Q, G2.neg(Q)], cp))
+    assert (got == pmod.to_ark_limbs(name, pm.Fq12(cp).one)).all()
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_host_verify_with_identity_ic(name):
+    """gamma_abc_g1 = [-k G, G] and the input k: the prepared input is the identity and its pair contributes nothing"""
+    vk, proofs, x_good, x_bad, cp = identity_ic_case(name)
+    for p in proofs:
+        assert g.verifier.host_verdict(name, vk, p, x_good) == 1
+        assert g.verifier.host_verdict(name, vk, p, x_bad) == 0
+    assert g.verifier.host_aggregate_verdict(name, vk, proofs, [x_good] * len(proofs)) == 1
+    assert g.verifier.host_aggregate_verdict(name, vk, proofs, [x_good, x_bad] + [x_good] * (len(proofs) - 2)) == 0
 
 
 @pytest.mark.parametrize("make", [oracle_case, pymodel_case], ids=["oracle_syn", "pymodel_mimc"])
