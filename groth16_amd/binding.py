@@ -141,7 +141,7 @@ EXPORTS = [
     "g16_abi_version", "g16_struct_size", "g16_get_timings_sized", "g16_pk_get_info_sized",
     "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
-    "g16_dev_fp30_op", "g16_host_fp30_op", "g16_dev_msm_reduce_lab", "g16_dev_pairing_op", "g16_host_pairing_op",
+    "g16_dev_fp30_op", "g16_host_fp30_op", "g16_dev_msm_reduce_lab", "g16_dev_window_table_lab", "g16_dev_pairing_op", "g16_host_pairing_op",
     "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
     "g16_decompress_points", "g16_decompress_proofs", "g16_host_decompress_points", "g16_verify_aggregate_bytes",
     "g16_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed_gt",
@@ -291,6 +291,7 @@ class Lib:
         c.g16_dev_pairing_op.argtypes = [C.c_void_p, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_pairing_op.argtypes = [C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_dev_msm_reduce_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u32p, u32p, C.c_uint64, u32p, u64p]
+        c.g16_dev_window_table_lab.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, C.c_int, C.c_int, u64p]
 
     def check(self, status: int, check_result: "Optional[CheckResultC]" = None):
         """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable"""
@@ -330,6 +331,18 @@ def msm_reduce_lab(lb: "Lib", ctx, g2: bool, merged: bool, c: int, groups: int, 
     lb.check(lb.c.g16_dev_msm_reduce_lab(ctx, int(g2), int(merged), c, groups, G, ptr32(nparts), ptr32(records), records.shape[0],
                                          ptr32(first), ptr64(out)))
     return first, out
+
+
+def window_table_lab(lb: "Lib", ctx, g2: bool, points: np.ndarray, c: int, W: int, fill: int = 0xDEADBEEFDEADBEEF):
+    """g16_dev_window_table_lab (test hook): the key loader's window-table builder on caller-made points.
+    points: uint64 [n, affine words] in the ABI's form.  Returns (status, uint64 [W, n, affine words]: row j of point i is
+    2^(c j) P_i, canonical x R' and y R' in the packed form's words, an identity row all zero).  The buffer is pre-filled with
+    `fill`, so what the call did not write shows."""
+    points = np.ascontiguousarray(points, dtype=np.uint64)
+    assert points.ndim == 2
+    out = np.full((max(W, 0), points.shape[0], points.shape[1]), fill, dtype=np.uint64)
+    status = lb.c.g16_dev_window_table_lab(ctx, int(g2), ptr64(points), points.shape[0], c, W, ptr64(out))
+    return status, out
 
 
 _LIB: Optional[Lib] = None

@@ -945,6 +945,14 @@ int g16_dev_msm_reduce_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, 
     G16_DISPATCH(ctx->curve, I::template msm_reduce_lab<typename I::Fq2>(ctx, merged, c, groups, G, nparts, records, n_records, first_slots, out_affine));
 }
 
+int g16_dev_window_table_lab(g16_ctx* ctx, int g2, const uint64_t* points, uint64_t n, int c, int W, uint64_t* table_out) {
+    if (!ctx || (n && (!points || !table_out))) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty()) return g16_dev_window_table_lab(ctx->subs[0], g2, points, n, c, W, table_out);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    if (!g2) G16_DISPATCH(ctx->curve, I::template window_table_lab<typename I::Fq>(ctx, points, n, c, W, table_out));
+    G16_DISPATCH(ctx->curve, I::template window_table_lab<typename I::Fq2>(ctx, points, n, c, W, table_out));
+}
+
 int g16_ntt(g16_ctx* ctx, uint64_t* data, int log_n, int inverse, int coset) {
     if (!ctx || !data) return G16_ERR_BAD_ARG;
     if (!ctx->subs.empty()) return g16_ntt(ctx->subs[0], data, log_n, inverse, coset);

@@ -93,8 +93,10 @@ struct ModInv30 {
         G16_UNROLL for (int i = 0; i < NL; ++i) r.v[i] += (int32_t)P::p30(i) & add2;
         carry(r);
     }
-    // x^-1 mod p as a plain integer in [0, p); x: normalised limbs of any value below 2^(30 NL - 3) that p does not divide
-    // (x = 0 mod p returns 0).  The loop ends when g = 0 (then f = +-1 and d = +-x^-1): ~2.3 steps per bit of p at worst.
+    // x^-1 mod p as a plain integer in [0, p); x: normalised limbs of any value below 2^(30 NL - 3); x = 0 mod p returns 0.
+    // The loop ends when g = 0: then f = +-gcd(x, p), i.e. f = +-1 and d = +-x^-1 -- or, when p divides x, f = +-p and d is whatever
+    // the steps made of it (x = 0 never enters the loop, but x = k p does: it used to return that d), so d is masked by f = +-1.
+    // ~2.3 steps per bit of p at worst.
     G16_HD static Fp30<P> inverse_plain(const Fp30<P>& x) {
         S30 d, e, f, g;
         G16_UNROLL for (int i = 0; i < NL; ++i) { d.v[i] = 0; e.v[i] = 0; f.v[i] = (int32_t)P::p30(i); g.v[i] = (int32_t)x.l[i]; }
@@ -110,8 +112,14 @@ struct ModInv30 {
             update_fg(f, g, t);
         }
         normalize(d, f.v[NL - 1]);
+        // f = 1: limbs 1, 0, .., 0; f = -1: 2^30 - 1, .., 2^30 - 1, -1
+        const int32_t fs = f.v[NL - 1] >> 31;
+        int32_t off = f.v[0] ^ ((fs & (M30 ^ 1)) ^ 1);
+        G16_UNROLL for (int i = 1; i + 1 < NL; ++i) off |= f.v[i] ^ (fs & M30);
+        off |= f.v[NL - 1] ^ fs;
+        const uint32_t keep = off == 0 ? ~0u : 0u;
         Fp30<P> r;
-        G16_UNROLL for (int i = 0; i < NL; ++i) r.l[i] = (uint32_t)d.v[i];
+        G16_UNROLL for (int i = 0; i < NL; ++i) r.l[i] = (uint32_t)d.v[i] & keep;
         return r;
     }
     // Montgomery form in, Montgomery form out: (a R')^-1 = a^-1 R'^-1, times R'^3 / R' = a^-1 R'   (output < 1.5p)
@@ -126,12 +134,18 @@ struct ModInv30 {
 template <class P>
 G16_HD Fp30<P> batch_inverse(const Fp30<P>& a) { return ModInv30<P>::inverse(a); }
 // Fq2 lane pair: (a0 + a1 u)^-1 = (a0 - a1 u) / (a0^2 + a1^2).  `m` is this lane's component, `o` the partner's; both lanes
-// invert the same norm (a pure function of (hi, m, o): host-testable without a wave)
+// invert the same norm (a pure function of (hi, m, o): host-testable without a wave).
+// Operands: both callers (window_table_task's `run`, AffineLevel::run's `pre`) hand it one() or the output of Fp2p30::mul, a
+// two-sweep product of a value below 1.5p with one below 3p: a0 b0 + a1 (16p - b1) < 28.5 p^2, so each component is below
+// (1 + 28.5 p / R') p < 1.06p, inside the 1.5p every product promises.  The steps themselves take any m, o < 16p (a pair's own
+// denominator, < 3p, is fine: the field lab inverts those).
+// Output < 1.5p per component, a zero component stays a multiple of p below that (lane 1 negates its operand, not the product:
+// 2p - t turned t = 0 into 2p itself); (a0 + a1 u) * out = R'^2 as residues, the zero element gives zero.
 template <class P>
 G16_HD Fp30<P> pair_inverse(bool hi, const Fp30<P>& m, const Fp30<P>& o) {
     const Fp30<P> n = m.sqr().add(o.sqr());                       // < 3p
-    const Fp30<P> t = m.mul(ModInv30<P>::inverse(n));             // lane 0: a0 / n     lane 1: a1 / n
-    return hi ? Fp30<P>::zero().template sub<2>(t) : t;           // lane 1: -a1 / n  (< 2p)
+    const Fp30<P> s = hi ? m.neg16() : m;                         // lane 0: a0     lane 1: -a1  (<= 16p)
+    return s.mul(ModInv30<P>::inverse(n));                        // lane 0: a0 / n     lane 1: -a1 / n
 }
 template <class P>
 G16_HD Fp2p30<P> batch_inverse(const Fp2p30<P>& a) { return {pair_inverse<P>(Fp2p30<P>::lane_hi(), a.c, Fp2p30<P>::swap(a.c))}; }

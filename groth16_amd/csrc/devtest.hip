@@ -7,10 +7,15 @@
 // The parked forms do the same with the bucket pass's own accumulator: AccParked over LdsAccStore in the kernel's LDS layout, signed
 // additions from packed y, gather() and to_packed as the flush does (G1; G2 on the lane pair: device only).  The host twin of the G1
 // form parks in ParkedArrayStore.
+// The inversion forms run the division-step inverse (ModInv30, batch_inverse, and pair_inverse on the lane pair with its DPP swap live),
+// the doubling forms jac30_double of the window-table builder, the affine forms one pair of the batched-affine tree (classify, the
+// inverse of its denominator, finish); the lane-pair doubling and affine forms are device only.
 // Kernel names start with devlab_: no resource budget applies to them.
 #include "internal.hpp"
 #include "fp30.hpp"
 #include "acc_store.hpp"
+#include "batch_affine.hpp"
+#include "window_tables.hpp"
 #include <type_traits>
 #include <vector>
 
@@ -49,6 +54,12 @@ constexpr bool lab_slots(int form, int* nin, int* nout) {
         case 71: case 72: i = 21; o = 9; break;
         case 73: i = 11; o = 5; break;
         case 74: i = 21; o = 9; break;
+        case 80: case 81: i = 1; break;
+        case 82: i = 2; o = 2; break;
+        case 83: i = 4; o = 3; break;
+        case 84: i = 7; o = 6; break;
+        case 85: i = 5; o = 3; break;
+        case 86: i = 9; o = 5; break;
         default: return false;
     }
     *nin = i;
@@ -57,9 +68,10 @@ constexpr bool lab_slots(int form, int* nin, int* nout) {
 }
 constexpr int lab_nin(int form) { int i = 0, o = 0; lab_slots(form, &i, &o); return i; }
 constexpr int lab_nout(int form) { int i = 0, o = 0; lab_slots(form, &i, &o); return o; }
-constexpr bool lab_is_pair(int form) { return (form >= 60 && form < 70) || form == 72 || form == 74; }
+constexpr bool lab_is_pair(int form) { return (form >= 60 && form < 70) || form == 72 || form == 74 || form == 82 || form == 84 || form == 86; }
 constexpr bool lab_is_parked(int form) { return form == 73 || form == 74; }
-constexpr bool lab_device_only(int form) { return form == 72 || form == 74; }   // the lane pair's accumulators need their lanes
+// the lane pair's accumulators, doublings and affine pairs need their lanes
+constexpr bool lab_device_only(int form) { return form == 72 || form == 74 || form == 84 || form == 86; }
 // base fields have the fused-subtraction products, the Fq2 forms and the lane pair; scalar fields have sub_pow2
 template <class P>
 constexpr bool lab_has(int form) {
@@ -164,6 +176,45 @@ struct ParkedLab {
     }
 };
 
+// d times jac30_double (window_tables.hpp).  A field element occupies C slots (the lane pair reads and writes the slot of its own
+// component `hi`):  in: X Y Z raw lazy limbs | word 0 of the last slot: d, clamped to 1 .. 32   out: X Y Z as the doublings left them
+template <class P, class F>
+struct JacLab {
+    static constexpr int C = F::LANES_PER_TASK;
+    G16_HD static F ldf(const uint32_t* in, int slot, int hi) { return TableLane<F>::wrap(ld<P>(in, slot + hi)); }
+    G16_HD static void run(const uint32_t* in, uint32_t* out, int hi) {
+        F X = ldf(in, 0, hi), Y = ldf(in, C, hi), Z = ldf(in, 2 * C, hi);
+        const uint32_t dw = in[3 * C * Fp30<P>::NL];
+        const int d = dw < 1u ? 1 : dw > 32u ? 32 : (int)dw;
+        for (int k = 0; k < d; ++k) jac30_double(X, Y, Z);
+        st<P>(out, hi, TableLane<F>::comp(X)); st<P>(out, C + hi, TableLane<F>::comp(Y)); st<P>(out, 2 * C + hi, TableLane<F>::comp(Z));
+    }
+};
+
+// One pair of the batched-affine tree: classify, the inverse of the pair's own denominator, finish.  Stricter than AffineLevel::run,
+// which inverts the running prefix product (an output of mul, below 1.06p): here batch_inverse gets the raw d, up to 3p per component.
+//   in:  a flag slot (word 0: P is the identity, word 1: Q is) | px py qx qy canonical limbs
+//   out: rx ry | word 0 of the last slot: the sum is the identity, word 1: the kind
+template <class P, class F>
+struct AffLab {
+    static constexpr int C = F::LANES_PER_TASK;
+    G16_HD static F ldf(const uint32_t* in, int slot, int hi) { return TableLane<F>::wrap(ld<P>(in, slot + hi)); }
+    G16_HD static void run(const uint32_t* in, uint32_t* out, int hi) {
+        const bool pz = in[0] != 0, qz = in[1] != 0;
+        const F px = ldf(in, 1, hi), py = ldf(in, 1 + C, hi), qx = ldf(in, 1 + 2 * C, hi), qy = ldf(in, 1 + 3 * C, hi);
+        F d, rx, ry;
+        bool rz;
+        const int kind = AffineBatch<F>::classify(pz, qz, px, py, qx, qy, d);
+        const F inv_d = batch_inverse(d);
+        AffineBatch<F>::finish(kind, px, py, qx, qy, inv_d, rx, ry, rz);
+        st<P>(out, hi, TableLane<F>::comp(rx)); st<P>(out, C + hi, TableLane<F>::comp(ry));
+        if (hi == 0) {
+            uint32_t* fl = out + 2 * C * Fp30<P>::NL;
+            G16_UNROLL for (int i = 0; i < Fp30<P>::NL; ++i) fl[i] = i == 0 ? (rz ? 1u : 0u) : i == 1 ? (uint32_t)kind : 0u;
+        }
+    }
+};
+
 // one tuple of a one-lane form
 template <class P, int FORM>
 struct LabOp {
@@ -229,6 +280,10 @@ struct LabOp {
             AccParked<B, ParkedArrayStore<B>> a;
             ParkedLab<P, B, ParkedArrayStore<B>>::run(in, out, 0, a);
         }
+        else if constexpr (FORM == 80) st<P>(out, 0, ModInv30<P>::inverse_plain(L(0)));
+        else if constexpr (FORM == 81) st<P>(out, 0, batch_inverse(L(0)));
+        else if constexpr (FORM == 83) JacLab<P, B>::run(in, out, 0);
+        else if constexpr (FORM == 85) AffLab<P, B>::run(in, out, 0);
     }
 };
 
@@ -241,6 +296,8 @@ struct LabPair {
     static __device__ __forceinline__ void run(const uint32_t* in, uint32_t* out) {
         const int hi = F::lane_hi() ? 1 : 0;
         if constexpr (FORM == 72) { AccLab<P, F>::run(in, out, hi); return; }
+        if constexpr (FORM == 84) { JacLab<P, F>::run(in, out, hi); return; }
+        if constexpr (FORM == 86) { AffLab<P, F>::run(in, out, hi); return; }
         auto L = [&](int k) { return F{ld<P>(in, 2 * k + hi)}; };
         F r = F::zero();
         if constexpr (FORM == 60) r = F::mul_v(F::lhs(L(0)), F::rhs(L(1)));
@@ -249,6 +306,7 @@ struct LabPair {
         else if constexpr (FORM == 63) r = F::mul_add_fused(L(0), L(1), L(2), L(3));
         else if constexpr (FORM == 64) r = F::mul_sub_fused(L(0), L(1), L(2), L(3));
         else if constexpr (FORM == 65) r = F::mul_add_fused_v(F::lhs(L(0)), F::rhs(L(1)), F::lhs(L(2)), F::rhs(L(3)));
+        else if constexpr (FORM == 82) r = batch_inverse(L(0));
         st<P>(out, hi, r.c);
     }
 #endif
@@ -266,6 +324,7 @@ struct LabPair {
             // (mul_add_fused_v has no pure per-lane routine: this line restates it, so on the host form 65 checks the restatement and
             //  the four-sweep product only; the device tier runs the project's own lhs / rhs / mul_add_fused_v)
             else if constexpr (FORM == 65) r = B::template mul4_cols<uint64_t>(C(0, 0), C(1, h), C(0, 1), y2(1), C(2, 0), C(3, h), C(2, 1), y2(3));
+            else if constexpr (FORM == 82) r = pair_inverse<P>(hi, C(0, h), C(0, 1 - h));
             st<P>(out, h, r);
         }
     }
@@ -338,9 +397,11 @@ int lab_host(const uint32_t* operands, uint64_t n, uint32_t* out) {
 
 #define LAB_FORMS(X)                                                                                                              \
     X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(30) X(31) \
-    X(32) X(33) X(34) X(35) X(36) X(37) X(38) X(39) X(40) X(41) X(42) X(43) X(50) X(51) X(60) X(61) X(62) X(63) X(64) X(65) X(70) X(71) X(72) X(73) X(74)
+    X(32) X(33) X(34) X(35) X(36) X(37) X(38) X(39) X(40) X(41) X(42) X(43) X(50) X(51) X(60) X(61) X(62) X(63) X(64) X(65) X(70) X(71) X(72) X(73) X(74) \
+    X(80) X(81) X(82) X(83) X(84) X(85) X(86)
 
-// device: launch on st; otherwise the host twin (which has no lanes: the lane pair's accumulators, forms 72 and 74, are device forms)
+// device: launch on st; otherwise the host twin (which has no lanes: the lane pair's accumulators, doublings and affine pairs, forms
+// 72, 74, 84 and 86, are device forms)
 template <class P>
 int lab_dispatch(bool device, hipStream_t st, int form, const uint32_t* operands, uint64_t n, uint32_t* out) {
     switch (form) {

@@ -9,7 +9,7 @@ end of a column's sum), and every way of pinning the order from C++ costs more t
 DEFINES the running sum draws a wait state (s_nop 0) before its reader from the hazard recognizer (2 200 per mixed
 addition: measured 3.6 % slower than the operand-scanning forms), one that only READS it lets the scheduler stretch the
 live ranges (G1 pass 137 -> 248 registers, the lane-pair kernel spills).  Written out, the chain is exactly
-2 NL^2 (+ 2 per extra accumulator) v_mad_u64_u32 and 5 NL - 1 other vector instructions per product, ~45 live registers.
+2 NL^2 (+ 2 per extra accumulator) v_mad_u64_u32 and 5 NL - 2 other vector instructions per product, ~45 live registers.
 
 Register use inside a block: operands are compiler-allocated (%n); the accumulators are the PHYSICAL pairs v[2:3], v[4:5],
 v[6:7] (declared as clobbers) because their halves must be named (v_mul_lo_u32 reads the low word, the accumulator merge

@@ -394,10 +394,13 @@ struct SelfTest {
         const int cases[4][2] = {{3, 1}, {5, 4}, {20, 13}, {19, 14}};   // (c, W)
         for (int cs = 0; cs < 4; ++cs) {
             const int c = cases[cs][0], W = cases[cs][1];
-            for (int it = 0; it < 3; ++it) {
+            // it = 2: the identity; it = 3: (x, 0), a two-torsion point of some curve y^2 = x^3 + b' (the doublings never read b): Z is
+            // zero after the first doubling, so row 0 is finite, every later row the identity -- the task's `live` exit
+            for (int it = 0; it < 4; ++it) {
                 uint32_t k[2] = {(uint32_t)sm_next(st) | 1u, (uint32_t)sm_next(st)};
                 {   // G1
-                    const G1A p = it == 2 ? G1A::identity() : G1X::from_affine(C::g1_generator()).mul_bits(k, 64).to_affine();
+                    G1A p = it == 2 ? G1A::identity() : G1X::from_affine(C::g1_generator()).mul_bits(k, 64).to_affine();
+                    if (it == 3) p.y = Fq::zero();
                     TableHostIO<F30> io;
                     io.ident = p.is_identity();
                     io.x0 = to30(p.x); io.y0 = to30(p.y);
@@ -411,10 +414,12 @@ struct SelfTest {
                         if (io.rid[j] < 0) return 700;
                         if (a.is_identity() != (io.rid[j] == 1)) return 701;
                         if (!a.is_identity() && (!same30(io.rx[j], a.x) || !same30(io.ry[j], a.y))) return 702;
+                        if (it == 3 && a.is_identity() != (j > 0)) return 703;
                     }
                 }
                 {   // G2, lane-pair emulation
-                    const G2A p = it == 2 ? G2A::identity() : G2X::from_affine(C::g2_generator()).mul_bits(k, 64).to_affine();
+                    G2A p = it == 2 ? G2A::identity() : G2X::from_affine(C::g2_generator()).mul_bits(k, 64).to_affine();
+                    if (it == 3) p.y = Fq2::zero();
                     TableHostIO<E2> io;
                     io.ident = p.is_identity();
                     io.x0 = E2{to30(p.x.c0), to30(p.x.c1)}; io.y0 = E2{to30(p.y.c0), to30(p.y.c1)};
@@ -431,6 +436,7 @@ struct SelfTest {
                         if (!a.is_identity() && (!same30(io.rx[j].c0, a.x.c0) || !same30(io.rx[j].c1, a.x.c1) || !same30(io.ry[j].c0, a.y.c0) ||
                                                  !same30(io.ry[j].c1, a.y.c1)))
                             return 712;
+                        if (it == 3 && a.is_identity() != (j > 0)) return 713;
                     }
                 }
             }

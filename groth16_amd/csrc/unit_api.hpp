@@ -188,6 +188,28 @@ struct UnitApi {
         return G16_OK;
     }
 
+    // The window-table builder in place (test hook, g16_dev_window_table_lab): the points go up as they are, build_window_tables is
+    // called as the key loader and msm_api call it -- it runs its own chunk loop, allocates its own parking buffer and picks its own
+    // launch shape; park = nullptr makes it return with the table finished -- and the W * n records come back.  W is NOT checked
+    // against the builder's limit here: refusing W = 33 is the builder's to do.
+    template <class F>
+    static int window_table_lab(g16_ctx* ctx, const uint64_t* points, uint64_t n, int c, int W, uint64_t* table_out) {
+        typedef Affine<F> A;
+        if (c < 1 || c > 32 || W < 1 || W > 64 || n > ((uint64_t)1 << 18) + 4096) return G16_ERR_BAD_ARG;
+        hipStream_t st = ctx->stream;
+        DrainOnError drain(ctx);
+        ctx->reset_arena();
+        A *d_p = nullptr, *d_t = nullptr;
+        G16_TRY(ctx->arena.alloc_n(n ? (size_t)n : 1, &d_p));
+        G16_TRY(ctx->arena.alloc_n(n ? (size_t)n * W : 1, &d_t));
+        if (n) G16_HIP_TRY(hipMemcpyAsync(d_p, points, (size_t)n * sizeof(A), hipMemcpyHostToDevice, st));
+        G16_TRY((build_window_tables<F>(d_p, n, c, W, d_t, st)));
+        if (n) G16_HIP_TRY(hipMemcpyAsync(table_out, d_t, (size_t)n * W * sizeof(A), hipMemcpyDeviceToHost, st));
+        G16_HIP_TRY(hipStreamSynchronize(st));
+        drain.dismiss();
+        return G16_OK;
+    }
+
     static int ntt_api(g16_ctx* ctx, uint64_t* data, int log_n, int inverse, int coset) {
         if (log_n < 0 || log_n > 30) return G16_ERR_DEGREE_TOO_LARGE;
         hipStream_t st = ctx->stream;

@@ -484,9 +484,30 @@ int g16_host_selftest(int curve, uint64_t seed, int iters);
  *   when neg is set) | a flag slot: word 0 the accumulator is the identity, word 1 the initial neg, word 2 the number of points,
  *   word 3 + j point j is the identity, word 6 + j point j is subtracted | x y of three affine points (canonical, the packed form's
  *   words).  out: as 70..72
+ *   inversion and the window-table / batched-affine arithmetic (Fq only; batch_affine.hpp, window_tables.hpp):
+ *   80 inv_plain = ModInv30::inverse_plain (1->1): normalised limbs of any value below 2^(30 NL - 3) -> canonical limbs of x^-1 mod p
+ *      as a plain integer, 0 when p divides x  81 inv = batch_inverse(Fp30) (1->1): same operands, residue x^-1 R'^2, below 1.5 p
+ *   82 pair_inv = batch_inverse(Fp2p30) on the lane pair (c0 c1 -> c0 c1; the host twin calls pair_inverse with hi = false and true):
+ *      components below 16 p in (the callers stay below 1.5 p; a pair's own denominator reaches 3 p), below 1.5 p out,
+ *      (c0 + c1 u) * out = R'^2, zero gives zero
+ *   83 jac_dbl_g1 (4->3), 84 jac_dbl_g2_pair (lane pair, 7->6; device only): X Y Z raw lazy limbs (X < 5.8 p, Y < 5.5 p, Z < 3 p per
+ *      component) | word 0 of the last slot: d, 1 <= d <= 32 (clamped) -> X Y Z after d times jac30_double
+ *   85 aff_pair_g1 (5->3), 86 aff_pair_g2_pair (lane pair, 9->5; device only): one pair of the batched-affine tree --
+ *      AffineBatch::classify, batch_inverse of its denominator, AffineBatch::finish.  in: a flag slot (word 0: P is the identity,
+ *      word 1: Q is) | px py qx qy canonical limbs.  out: rx ry canonical limbs | word 0: the sum is the identity, word 1: the kind
+ *      (0 ADD, 1 DBL, 2 TAKE_P, 3 TAKE_Q, 4 ZERO)
  * G16_ERR_BAD_ARG for an unknown form or one the field does not have, n == 0 or n > 2^22. */
 int g16_dev_fp30_op(g16_ctx* ctx, int field, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
 int g16_host_fp30_op(int curve, int field, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
+
+/* ---- the table lab (test hook): the window-table builder in place ----
+ * Uploads n affine points (the ABI's form: Montgomery limbs, all-zero = the identity; G2 when g2 != 0), calls the key loader's
+ * build_window_tables for window size c and W rows -- its chunk loop, the parking buffer it allocates, its launch shape -- and
+ * downloads the W * n records: table_out[j * n + i] = 2^(c j) P_i as the bucket pass reads it, x then y (G2: x.c0 x.c1 y.c0 y.c1),
+ * each the canonical value times R' = 2^(30 NL) mod p in the packed form's words; an identity row is all zero.  The points are not
+ * checked (not even for being on the curve: the doubling formulas never read b).  1 <= c <= 32, 1 <= W <= 64, n <= 2^18 + 4096 (just
+ * past the builder's chunk of 2^18 points; W * n records of device memory, 3.3 GB at the limits for G2 on BLS12-381), else G16_ERR_BAD_ARG; W > 32 is the builder's own refusal, G16_ERR_INTERNAL; n == 0 returns G16_OK and writes nothing. */
+int g16_dev_window_table_lab(g16_ctx* ctx, int g2, const uint64_t* points, uint64_t n, int c, int W, uint64_t* table_out);
 
 /* ---- the tower lab (test hooks): ONE operation of the pairing tower (csrc/pairing.hpp) on raw limbs ----
  * g16_dev_pairing_op runs one tuple per lane on the ctx's (first) GPU and its curve, g16_host_pairing_op the same code compiled for

@@ -206,9 +206,13 @@ LAB = {
     "pair_mul_sub": (64, 8, 2), "pair_mul_add_fused_v": (65, 8, 2),
     "acc_chain_g1": (70, 11, 5), "acc_chain_g2": (71, 21, 9), "acc_chain_g2_pair": (72, 21, 9),
     "parked_chain_g1": (73, 11, 5), "parked_chain_g2_pair": (74, 21, 9),
+    "inv_plain": (80, 1, 1), "inv": (81, 1, 1), "pair_inv": (82, 2, 2), "jac_dbl_g1": (83, 4, 3), "jac_dbl_g2_pair": (84, 7, 6),
+    "aff_pair_g1": (85, 5, 3), "aff_pair_g2_pair": (86, 9, 5),
 }
-FQ_ONLY = ("fp2x_", "pair_", "acc_", "parked_")
-DEVICE_ONLY = ("acc_chain_g2_pair", "parked_chain_g2_pair")   # the lane pair's accumulators need their lanes: the host twin does not have them
+FQ_ONLY = ("fp2x_", "pair_", "acc_", "parked_", "inv", "jac_dbl_", "aff_pair_")
+# the lane pair's accumulators, doublings and affine pairs need their lanes: the host twin does not have them
+DEVICE_ONLY = ("acc_chain_g2_pair", "parked_chain_g2_pair", "jac_dbl_g2_pair", "aff_pair_g2_pair")
+TABLE_FORMS = ("inv_plain", "inv", "pair_inv", "jac_dbl_g1", "jac_dbl_g2_pair", "aff_pair_g1", "aff_pair_g2_pair")   # cases: tests/table_cases.py
 
 
 def lab_forms(f, host=False):
@@ -412,6 +416,9 @@ def lab_cases(f, form, seed=1):
         return acc_cases(f, form, rng)
     if form.startswith("parked_chain"):
         return parked_cases(f, form, rng)
+    if form in TABLE_FORMS:
+        import table_cases
+        return table_cases.lab_cases(f, form)
     raise KeyError(form)
 
 

@@ -16,7 +16,7 @@ def test_fips_asm_header_is_current(tmp_path):
 
 
 def test_fips_asm_block_shape():
-    """every block is a straight multiply-add chain: 2 NL^2 (+ 2 per extra accumulator) v_mad_u64_u32 and 5 NL - 1 other vector
+    """every block is a straight multiply-add chain: 2 NL^2 (+ 2 per extra accumulator) v_mad_u64_u32 and 5 NL - 2 other vector
     instructions for a plain product -- the counts the header's trailer records and DESIGN.md 4.1 quotes"""
     txt = open(os.path.join(CSRC, "fips_asm_gen.hpp")).read()
     rows = {}
