@@ -118,6 +118,19 @@ class CheckResultC(C.Structure):
     _fields_ = [("n_unsatisfied", C.c_uint64), ("first_row", C.c_uint64), ("a", C.c_uint64 * 4), ("b", C.c_uint64 * 4), ("c", C.c_uint64 * 4)]
 
 
+class PassLabJobC(C.Structure):
+    """g16_pass_lab_job"""
+    _fields_ = [("table", u64p), ("base_count", C.c_uint64), ("shift", C.c_int64), ("counts", u32p), ("sorted", u32p), ("n_sorted", C.c_uint64),
+                ("record_cap", C.c_uint64), ("records", u32p), ("n_records", C.c_uint64), ("offsets", u32p), ("task_off", u32p), ("heavy", u32p),
+                ("out_affine", u64p)]
+
+
+class SortLabInfoC(C.Structure):
+    """g16_sort_lab_info"""
+    _fields_ = [("c", C.c_int32), ("W", C.c_int32), ("groups", C.c_int32), ("merged", C.c_int32), ("B", C.c_uint32), ("Lmax", C.c_uint32),
+                ("max_tasks", C.c_uint32), ("max_segments", C.c_uint32), ("K", C.c_uint32 * 10), ("n_sorted", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class TimingsC(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "witness_map_ms", "msm_h_ms", "msm_l_ms", "msm_a_ms", "msm_b_g1_ms", "msm_b_g2_ms", "scalar_prep_ms", "finish_ms",
@@ -142,6 +155,7 @@ EXPORTS = [
     "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
     "g16_dev_fp30_op", "g16_host_fp30_op", "g16_dev_msm_reduce_lab", "g16_dev_window_table_lab", "g16_dev_pairing_op", "g16_host_pairing_op",
+    "g16_dev_msm_pass_lab", "g16_dev_msm_sort_lab",
     "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
     "g16_decompress_points", "g16_decompress_proofs", "g16_host_decompress_points", "g16_verify_aggregate_bytes",
     "g16_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed_gt",
@@ -292,6 +306,10 @@ class Lib:
         c.g16_host_pairing_op.argtypes = [C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_dev_msm_reduce_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u32p, u32p, C.c_uint64, u32p, u64p]
         c.g16_dev_window_table_lab.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, C.c_int, C.c_int, u64p]
+        c.g16_dev_msm_pass_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PassLabJobC),
+                                           C.c_int]
+        c.g16_dev_msm_sort_lab.argtypes = [C.c_void_p, u64p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(SortLabInfoC), u32p, u32p, u32p,
+                                           C.c_uint64, u32p, C.c_uint64]
 
     def check(self, status: int, check_result: "Optional[CheckResultC]" = None):
         """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable"""
@@ -331,6 +349,63 @@ def msm_reduce_lab(lb: "Lib", ctx, g2: bool, merged: bool, c: int, groups: int, 
     lb.check(lb.c.g16_dev_msm_reduce_lab(ctx, int(g2), int(merged), c, groups, G, ptr32(nparts), ptr32(records), records.shape[0],
                                          ptr32(first), ptr64(out)))
     return first, out
+
+
+PASS_LAB_GUARDS = 8
+
+
+def msm_pass_lab(lb: "Lib", ctx, g2: bool, merged: bool, c: int, groups: int, G: int, lseg: int, rows: int, jobs, record_words: int,
+                 affine_words: int):
+    """g16_dev_msm_pass_lab (test hook): the bucket pass's walk on caller-made sorted lists, all jobs in one launch.
+    jobs: a list of dicts with table (uint64 [rows * base_count, affine words]), base_count, shift, counts (uint32 [M]) and sorted
+    (uint32 [S]).  Returns (status, results); results is None unless status == 0, else per job a dict: records (uint32
+    [task_off[M] + 8, record words], the last 8 the guards), offsets, task_off, heavy (uint32 [M + 1] each) and out (uint64
+    [affine_words], the folded sum).  Nothing is checked here: refusing is the library's to do."""
+    M = groups << (c - 1)
+    arr = (PassLabJobC * max(len(jobs), 1))()
+    keep, outs = [], []
+    for k, job in enumerate(jobs):
+        table = np.ascontiguousarray(job["table"], dtype=np.uint64)
+        counts = np.ascontiguousarray(job["counts"], dtype=np.uint32)
+        srt = np.ascontiguousarray(job["sorted"], dtype=np.uint32)
+        cap = job.get("record_cap", (len(srt) + max(lseg, 1) - 1) // max(lseg, 1) + M + PASS_LAB_GUARDS)
+        o = {"records": np.zeros((max(cap, 1), record_words), dtype=np.uint32), "offsets": np.zeros(M + 1, dtype=np.uint32),
+             "task_off": np.zeros(M + 1, dtype=np.uint32), "heavy": np.zeros(M + 1, dtype=np.uint32), "out": np.zeros(affine_words, dtype=np.uint64)}
+        keep.append((table, counts, srt))
+        outs.append(o)
+        j = arr[k]
+        j.table, j.base_count, j.shift = ptr64(table.reshape(-1)), int(job["base_count"]), int(job["shift"])
+        j.counts, j.sorted, j.n_sorted, j.record_cap = ptr32(counts), ptr32(srt), int(job.get("n_sorted", len(srt))), cap
+        j.records, j.offsets, j.task_off, j.heavy, j.out_affine = (ptr32(o["records"].reshape(-1)), ptr32(o["offsets"]), ptr32(o["task_off"]),
+                                                                   ptr32(o["heavy"]), ptr64(o["out"]))
+    status = lb.c.g16_dev_msm_pass_lab(ctx, int(g2), int(merged), c, groups, G, lseg, rows, arr, len(jobs))
+    if status != 0:
+        return status, None
+    for k, o in enumerate(outs):
+        o["records"] = o["records"][:arr[k].n_records + PASS_LAB_GUARDS]
+    return status, outs
+
+
+def msm_sort_lab(lb: "Lib", ctx, scalars: np.ndarray, merged_c: int = 0, shard_n: int = 1, shard_r: int = 0):
+    """g16_dev_msm_sort_lab (test hook): sort_scalars on caller-made scalars (uint64 [n, 4], Montgomery limbs).
+    Returns (status, result); result is None unless status == 0, else a dict: the g16_sort_lab_info fields, M, offsets, task_off,
+    heavy (uint32 [M + 1] each) and sorted (uint32 [offsets[M]])."""
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    n = scalars.shape[0]
+    bucket_cap = (1 << 20) + 1                  # 2^19 buckets at the largest plans (merged c = 20; per-window c = 16 has 17 x 2^15)
+    sorted_cap = max(n, 1) * 128                # W <= 86 windows (c = 3)
+    info = SortLabInfoC()
+    offsets, task_off, heavy = (np.zeros(bucket_cap, dtype=np.uint32) for _ in range(3))
+    srt = np.zeros(sorted_cap, dtype=np.uint32)
+    status = lb.c.g16_dev_msm_sort_lab(ctx, ptr64(scalars.reshape(-1)), n, merged_c, shard_n, shard_r, C.byref(info), ptr32(offsets),
+                                       ptr32(task_off), ptr32(heavy), bucket_cap, ptr32(srt), sorted_cap)
+    if status != 0:
+        return status, None
+    M = info.groups * info.B
+    res = {k: getattr(info, k) for k in ("c", "W", "groups", "merged", "B", "Lmax", "max_tasks", "max_segments", "n_sorted")}
+    res.update(M=M, K=sum(int(w) << (32 * i) for i, w in enumerate(info.K)), offsets=offsets[:M + 1].copy(), task_off=task_off[:M + 1].copy(),
+               heavy=heavy[:M + 1].copy(), sorted=srt[:info.n_sorted].copy())
+    return status, res
 
 
 def window_table_lab(lb: "Lib", ctx, g2: bool, points: np.ndarray, c: int, W: int, fill: int = 0xDEADBEEFDEADBEEF):

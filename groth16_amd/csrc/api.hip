@@ -945,6 +945,23 @@ int g16_dev_msm_reduce_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, 
     G16_DISPATCH(ctx->curve, I::template msm_reduce_lab<typename I::Fq2>(ctx, merged, c, groups, G, nparts, records, n_records, first_slots, out_affine));
 }
 
+int g16_dev_msm_pass_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, int lseg, int rows, g16_pass_lab_job* jobs, int n_jobs) {
+    if (!ctx || !jobs) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty()) return g16_dev_msm_pass_lab(ctx->subs[0], g2, merged, c, groups, G, lseg, rows, jobs, n_jobs);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    if (!g2) G16_DISPATCH(ctx->curve, I::template msm_pass_lab<typename I::Fq>(ctx, merged, c, groups, G, lseg, rows, jobs, n_jobs));
+    G16_DISPATCH(ctx->curve, I::template msm_pass_lab<typename I::Fq2>(ctx, merged, c, groups, G, lseg, rows, jobs, n_jobs));
+}
+
+int g16_dev_msm_sort_lab(g16_ctx* ctx, const uint64_t* scalars, uint64_t n, int merged_c, int shard_n, int shard_r, g16_sort_lab_info* info,
+                         uint32_t* offsets, uint32_t* task_off, uint32_t* heavy, uint64_t bucket_cap, uint32_t* sorted, uint64_t sorted_cap) {
+    if (!ctx || !info || !offsets || !task_off || !heavy || !sorted || (n && !scalars)) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty())
+        return g16_dev_msm_sort_lab(ctx->subs[0], scalars, n, merged_c, shard_n, shard_r, info, offsets, task_off, heavy, bucket_cap, sorted, sorted_cap);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    G16_DISPATCH(ctx->curve, I::msm_sort_lab(ctx, scalars, n, merged_c, shard_n, shard_r, info, offsets, task_off, heavy, bucket_cap, sorted, sorted_cap));
+}
+
 int g16_dev_window_table_lab(g16_ctx* ctx, int g2, const uint64_t* points, uint64_t n, int c, int W, uint64_t* table_out) {
     if (!ctx || (n && (!points || !table_out))) return G16_ERR_BAD_ARG;
     if (!ctx->subs.empty()) return g16_dev_window_table_lab(ctx->subs[0], g2, points, n, c, W, table_out);
@@ -1102,6 +1119,8 @@ uint64_t g16_struct_size(int which) {
         case G16_STRUCT_PK_VIEW: return sizeof(g16_pk_view);
         case G16_STRUCT_VK_VIEW: return sizeof(g16_vk_view);
         case G16_STRUCT_CHECK_RESULT: return sizeof(g16_check_result);
+        case G16_STRUCT_PASS_LAB_JOB: return sizeof(g16_pass_lab_job);
+        case G16_STRUCT_SORT_LAB_INFO: return sizeof(g16_sort_lab_info);
         default: return 0;
     }
 }

@@ -273,6 +273,12 @@ struct ScalarSort {
 };
 template <class C> int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Arena& arena, hipStream_t st, ScalarSort* out,
                                     int shard_n = 1, int shard_r = 0);
+// The tail of sort_scalars on its own (the pass lab runs it on caller-made counts): counts[M] -> offsets[M + 1] (every count rounded up
+// to a multiple of 2^R), nparts[M] = segments of length lseg each bucket touches, task_off[M + 1] = their exclusive prefix, and the heavy
+// list (heavy[0], zeroed by the caller, counts the buckets with more than HEAVY_PARTS partial sums; their ids follow in any order).
+// All device pointers; block_sums: M / 2048 + 1 words of scratch.
+int msm_slot_layout(const uint32_t* counts, uint32_t M, int R, uint32_t lseg, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off,
+                    uint32_t* heavy, uint32_t* block_sums, hipStream_t st);
 
 // Pippenger over one base array using a ScalarSort, in two stream-separable halves:
 //   msm_bucket_pass  the throughput-bound bucket accumulation.  Sorted index p addresses bases[p + shift] when

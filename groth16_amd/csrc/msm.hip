@@ -1112,6 +1112,31 @@ int make_msm_plan(uint64_t n, int scalar_bits, const uint32_t* modulus_words, in
 
 static int ilog2(uint32_t v) { int l = 0; while ((1u << l) < v) ++l; return l; }
 
+// exclusive prefix sum of `count` values (3. above); block_sums: scratch of ceil(count / SCAN_TILE) words
+static int prefix_scan_u32(const uint32_t* vals, uint32_t* prefix, uint32_t count, uint32_t padmask, uint32_t* block_sums, hipStream_t st) {
+    const uint32_t nblocks = (count + SCAN_TILE - 1) / SCAN_TILE;
+    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, st, vals, count, padmask, block_sums);
+    G16_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_block_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, block_sums, nblocks, count, prefix);
+    G16_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_write_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, st, vals, count, padmask, block_sums, prefix);
+    G16_LAUNCH_CHECK();
+    return G16_OK;
+}
+
+#if G16_MSM_PART == 0
+// The tail of sort_scalars, which the pass lab (unit_api.hpp) runs on caller-made counts: bucket counts -> offsets (every count
+// rounded up to a multiple of 2^R), offsets -> partial-sum slots per bucket and the heavy list, slots -> task_off.
+int msm_slot_layout(const uint32_t* counts, uint32_t M, int R, uint32_t lseg, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off,
+                    uint32_t* heavy, uint32_t* block_sums, hipStream_t st) {
+    G16_TRY(prefix_scan_u32(counts, offsets, M, (1u << R) - 1u, block_sums, st));
+    hipLaunchKernelGGL(bucket_slots_kernel, dim3((M + 255) / 256), dim3(256), 0, st, offsets, M, (uint32_t)R, lseg, nparts, heavy);
+    G16_LAUNCH_CHECK();
+    G16_TRY(prefix_scan_u32(nparts, task_off, M, 0u, block_sums, st));
+    return G16_OK;
+}
+#endif
+
 template <class C>
 int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Arena& arena, hipStream_t st, ScalarSort* out, int shard_n,
                  int shard_r) {
@@ -1207,15 +1232,8 @@ int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Aren
     const uint32_t sub_cells = two_level ? Q * S * gx2 : 0u;
     const uint32_t max_scan = std::max(std::max(M, plan.merged ? Q * nb : 0u), sub_cells);
     G16_TRY(arena.alloc_n((size_t)(max_scan + SCAN_TILE - 1) / SCAN_TILE, &block_sums));
-    auto prefix_scan = [&](const uint32_t* vals, uint32_t* prefix, uint32_t count, uint32_t padmask = 0) -> int {
-        const uint32_t nblocks = (count + SCAN_TILE - 1) / SCAN_TILE;
-        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, st, vals, count, padmask, block_sums);
-        G16_LAUNCH_CHECK();
-        hipLaunchKernelGGL(scan_block_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, block_sums, nblocks, count, prefix);
-        G16_LAUNCH_CHECK();
-        hipLaunchKernelGGL(scan_write_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, st, vals, count, padmask, block_sums, prefix);
-        G16_LAUNCH_CHECK();
-        return G16_OK;
+    auto prefix_scan = [&](const uint32_t* vals, uint32_t* prefix, uint32_t count) -> int {
+        return prefix_scan_u32(vals, prefix, count, 0u, block_sums, st);
     };
     // merged plan: ~4096 workgroups of 256 lanes over the class regions (a class region may hold anything between nothing and all
     // entries), at most 256 per class: every workgroup zeroes, stores and re-reads a histogram row whatever it counts
@@ -1266,11 +1284,7 @@ int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Aren
         }
         G16_LAUNCH_CHECK();
     }
-    G16_TRY(prefix_scan(counts, out->offsets, M, pad));
-    hipLaunchKernelGGL(bucket_slots_kernel, dim3((M + 255) / 256), dim3(256), 0, st, out->offsets, M, (uint32_t)R, plan.Lmax, nparts,
-                       out->heavy);
-    G16_LAUNCH_CHECK();
-    G16_TRY(prefix_scan(nparts, out->task_off, M));
+    G16_TRY(msm_slot_layout(counts, M, R, plan.Lmax, out->offsets, nparts, out->task_off, out->heavy, block_sums, st));
     if (n && !two_level) {
         if (plan.merged)
             hipLaunchKernelGGL(bucket_scatter_merged_kernel, dim3(gx, Q), dim3(SORT_M_THREADS), lds, st, planes, ent_tag, class_off, nb, Bs,

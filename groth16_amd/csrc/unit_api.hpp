@@ -188,6 +188,176 @@ struct UnitApi {
         return G16_OK;
     }
 
+    // The bucket pass's walk in place (test hook, g16_dev_msm_pass_lab): a plan filled by hand as above; per job a table, a bucket
+    // histogram and a sorted list the caller made.  offsets, task_off and the heavy list come from msm_slot_layout (the tail of
+    // sort_scalars), the passes of all jobs go as ONE launch of msm_bucket_pass_batch, then msm_reduce and fold_windows per job.
+    // msm_bucket_pass_batch allocates the partial-sum slots itself, from the arena and unzeroed.  The lab makes the same allocations
+    // first, fills them with 0xA5, and rewinds the arena, so that the batch call's own allocations land on the filled memory; that they
+    // did is checked afterwards (G16_ERR_INTERNAL).  ss.max_tasks = task_off[M] + 8: the 8 records behind the last slot are the guards.
+    // Refused (G16_ERR_BAD_ARG): whatever would let the kernel read outside what was uploaded.  A point index outside [0, base_count)
+    // after `shift` is NOT refused: skipping it is the kernel's to do.
+    template <class F>
+    static int msm_pass_lab(g16_ctx* ctx, int merged, int c, int groups, int G, int lseg, int rows, g16_pass_lab_job* jobs, int n_jobs) {
+        typedef Affine<F> A;
+        typedef XYZZ<F> X;
+        typedef Fp30<typename Fq::Params> B30;
+        typedef AccRaw<typename std::conditional<std::is_same<F, Fq>::value, B30, Fp2x30<typename Fq::Params>>::type> Raw;
+        constexpr size_t REC_WORDS = (std::is_same<F, Fq>::value ? 4 : 8) * B30::NL;
+        constexpr uint32_t GUARDS = 8;
+        constexpr int MAX_JOBS = 4;
+        if (n_jobs < 1 || n_jobs > MAX_JOBS || !jobs) return G16_ERR_BAD_ARG;
+        if (c < 2 || c > 16 || groups < 1 || groups > 32 || (G != 8 && G != 16 && G != 32) || lseg < 8 || lseg > 4096) return G16_ERR_BAD_ARG;
+        if (rows < 1 || rows > 32 || (!merged && rows != 1)) return G16_ERR_BAD_ARG;
+        ScalarSort ss[MAX_JOBS];
+        for (int j = 0; j < n_jobs; ++j) {
+            MsmPlan& plan = ss[j].plan;
+            plan.c = c;
+            plan.W = groups;
+            plan.groups = groups;
+            plan.merged = merged != 0;
+            plan.B = 1u << (c - 1);
+            plan.G = (uint32_t)G;
+            plan.Lmax = (uint32_t)lseg;
+            plan.chunk = 1024;
+            for (int k = 0; k < 10; ++k) plan.K[k] = 0;
+        }
+        const MsmPlan& plan = ss[0].plan;
+        if (plan.outputs() > MSM_MAX_OUTPUTS) return G16_ERR_BAD_ARG;
+        const uint32_t M = plan.buckets();
+        if (M > (1u << 12)) return G16_ERR_BAD_ARG;
+        for (int j = 0; j < n_jobs; ++j) {
+            const g16_pass_lab_job& job = jobs[j];
+            if (!job.counts || !job.records || !job.offsets || !job.task_off || !job.heavy || !job.out_affine) return G16_ERR_BAD_ARG;
+            if (job.n_sorted > ((uint64_t)1 << 16) || (job.n_sorted && !job.sorted)) return G16_ERR_BAD_ARG;
+            if (job.base_count > ((uint64_t)1 << 16) || (job.base_count && !job.table)) return G16_ERR_BAD_ARG;
+            if (job.shift > ((int64_t)1 << 40) || job.shift < -((int64_t)1 << 40)) return G16_ERR_BAD_ARG;
+            uint64_t total = 0;
+            for (uint32_t b = 0; b < M; ++b) total += job.counts[b];
+            if (total != job.n_sorted) return G16_ERR_BAD_ARG;
+            if (merged)
+                for (uint64_t e = 0; e < job.n_sorted; ++e)
+                    if (((job.sorted[e] >> 26) & 31u) >= (uint32_t)rows) return G16_ERR_BAD_ARG;
+            // a bucket gets one slot per segment it touches: <= segments + buckets in total
+            if (job.record_cap < (job.n_sorted + (uint64_t)lseg - 1) / (uint64_t)lseg + M + GUARDS) return G16_ERR_BAD_LENGTH;
+        }
+        hipStream_t st = ctx->stream;
+        DrainOnError drain(ctx);
+        ctx->reset_arena();
+        A* d_table[MAX_JOBS] = {};
+        uint32_t *d_counts[MAX_JOBS] = {}, *d_nparts = nullptr, *d_block = nullptr;
+        std::vector<uint32_t> h_task((size_t)MAX_JOBS * (M + 1));
+        for (int j = 0; j < n_jobs; ++j) {
+            const g16_pass_lab_job& job = jobs[j];
+            const size_t npts = (size_t)rows * job.base_count;
+            G16_TRY(ctx->arena.alloc_n(npts ? npts : 1, &d_table[j]));
+            G16_TRY(ctx->arena.alloc_n((size_t)M, &d_counts[j]));
+            G16_TRY(ctx->arena.alloc_n(job.n_sorted ? (size_t)job.n_sorted : 1, &ss[j].sorted));
+            G16_TRY(ctx->arena.alloc_n((size_t)M + 1, &ss[j].offsets));
+            G16_TRY(ctx->arena.alloc_n((size_t)M + 1, &ss[j].task_off));
+            G16_TRY(ctx->arena.alloc_n((size_t)M + 1, &ss[j].heavy));
+            if (!d_nparts) {
+                G16_TRY(ctx->arena.alloc_n((size_t)M, &d_nparts));
+                G16_TRY(ctx->arena.alloc_n((size_t)M / 2048 + 1, &d_block));
+            }
+            if (npts) {
+                G16_HIP_TRY(hipMemcpyAsync(d_table[j], job.table, npts * sizeof(A), hipMemcpyHostToDevice, st));
+                G16_TRY((convert_bases<F>(d_table[j], npts, st)));
+            }
+            G16_HIP_TRY(hipMemcpyAsync(d_counts[j], job.counts, (size_t)M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            if (job.n_sorted)
+                G16_HIP_TRY(hipMemcpyAsync(ss[j].sorted, job.sorted, (size_t)job.n_sorted * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            G16_HIP_TRY(hipMemsetAsync(ss[j].heavy, 0, ((size_t)M + 1) * sizeof(uint32_t), st));
+            G16_TRY(msm_slot_layout(d_counts[j], M, 0, plan.Lmax, ss[j].offsets, d_nparts, ss[j].task_off, ss[j].heavy, d_block, st));
+            G16_HIP_TRY(hipMemcpyAsync(h_task.data() + (size_t)j * (M + 1), ss[j].task_off, ((size_t)M + 1) * sizeof(uint32_t),
+                                       hipMemcpyDeviceToHost, st));
+        }
+        G16_HIP_TRY(hipStreamSynchronize(st));
+        for (int j = 0; j < n_jobs; ++j) {
+            const uint32_t tasks = h_task[(size_t)j * (M + 1) + M];
+            if ((uint64_t)tasks + GUARDS > jobs[j].record_cap) return G16_ERR_INTERNAL;   // more slots than segments + buckets
+            ss[j].n = jobs[j].n_sorted;
+            ss[j].max_sorted = jobs[j].n_sorted;
+            ss[j].max_tasks = tasks + GUARDS;
+            // one task past the last segment: real plans size the grid by an upper bound too, and that task must return at once
+            ss[j].max_segments = jobs[j].n_sorted ? (uint32_t)((jobs[j].n_sorted + plan.Lmax - 1) / plan.Lmax) + 1u : 0u;
+            jobs[j].n_records = tasks;
+        }
+        // the allocations msm_bucket_pass_batch is about to make (alloc_msm_buffers, job by job), filled, then handed back
+        std::vector<size_t> used;
+        for (const Arena::Chunk& ch : ctx->arena.chunks) used.push_back(ch.used);
+        Raw* expect[MAX_JOBS] = {};
+        for (int j = 0; j < n_jobs; ++j) {
+            Raw* chunk_out = nullptr;
+            X* sums = nullptr;
+            G16_TRY(ctx->arena.alloc_n((size_t)ss[j].max_tasks, &expect[j]));
+            G16_TRY(ctx->arena.alloc_n((size_t)plan.chunks() * plan.groups * 2, &chunk_out));
+            G16_TRY(ctx->arena.alloc_n((size_t)plan.outputs(), &sums));
+            G16_HIP_TRY(hipMemsetAsync(expect[j], 0xA5, (size_t)ss[j].max_tasks * sizeof(Raw), st));
+        }
+        for (size_t k = 0; k < ctx->arena.chunks.size(); ++k) ctx->arena.chunks[k].used = k < used.size() ? used[k] : 0;
+        MsmBuffers<F> buf[MAX_JOBS];
+        PassJob<F> pj[MAX_JOBS];
+        for (int j = 0; j < n_jobs; ++j) pj[j] = PassJob<F>{d_table[j], jobs[j].shift, jobs[j].base_count, &ss[j], &buf[j]};
+        G16_TRY((msm_bucket_pass_batch<F>(pj, n_jobs, ctx->arena, st, nullptr)));
+        for (int j = 0; j < n_jobs; ++j)
+            if (buf[j].partials != (void*)expect[j]) return G16_ERR_INTERNAL;
+        // the records as the pass left them, before the reductions combine them in place
+        for (int j = 0; j < n_jobs; ++j) {
+            G16_HIP_TRY(hipMemcpyAsync(jobs[j].records, buf[j].partials, (size_t)ss[j].max_tasks * sizeof(Raw), hipMemcpyDeviceToHost, st));
+            G16_HIP_TRY(hipMemcpyAsync(jobs[j].offsets, ss[j].offsets, ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            G16_HIP_TRY(hipMemcpyAsync(jobs[j].heavy, ss[j].heavy, ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            memcpy(jobs[j].task_off, h_task.data() + (size_t)j * (M + 1), ((size_t)M + 1) * sizeof(uint32_t));
+        }
+        std::vector<X> hws((size_t)MAX_JOBS * plan.outputs());
+        for (int j = 0; j < n_jobs; ++j) {
+            G16_TRY((msm_reduce<F>(buf[j], ss[j], st)));
+            G16_HIP_TRY(hipMemcpyAsync(hws.data() + (size_t)j * plan.outputs(), buf[j].window_sums, sizeof(X) * plan.outputs(),
+                                       hipMemcpyDeviceToHost, st));
+        }
+        G16_HIP_TRY(hipStreamSynchronize(st));
+        drain.dismiss();
+        for (int j = 0; j < n_jobs; ++j) {
+            const A res = fold_windows<F>(hws.data() + (size_t)j * plan.outputs(), plan).to_affine();
+            memcpy(jobs[j].out_affine, &res, sizeof(A));
+        }
+        return G16_OK;
+    }
+
+    // Digits and sort layout in place (test hook, g16_dev_msm_sort_lab): the scalars go up, sort_scalars runs as msm_api and the prover
+    // call it (the environment knobs apply), and the plan, the layout and the sorted list come back.
+    static int msm_sort_lab(g16_ctx* ctx, const uint64_t* scalars, uint64_t n, int merged_c, int shard_n, int shard_r, g16_sort_lab_info* info,
+                            uint32_t* offsets, uint32_t* task_off, uint32_t* heavy, uint64_t bucket_cap, uint32_t* sorted, uint64_t sorted_cap) {
+        if (n > ((uint64_t)1 << 16) || shard_n < 1 || shard_n > 64 || shard_r < 0 || shard_r >= shard_n || (shard_n > 1 && merged_c <= 0))
+            return G16_ERR_BAD_ARG;
+        if (merged_c && (merged_c < MSM_MERGED_MIN_C || merged_c > MSM_MERGED_MAX_C)) return G16_ERR_BAD_ARG;
+        hipStream_t st = ctx->stream;
+        DrainOnError drain(ctx);
+        ctx->reset_arena();
+        Fr* d_s = nullptr;
+        G16_TRY(ctx->arena.alloc_n(n ? (size_t)n : 1, &d_s));
+        if (n) G16_HIP_TRY(hipMemcpyAsync(d_s, scalars, (size_t)n * sizeof(Fr), hipMemcpyHostToDevice, st));
+        ScalarSort ss;
+        G16_TRY((sort_scalars<C>(d_s, n, merged_c, ctx->arena, st, &ss, shard_n, shard_r)));
+        const MsmPlan& plan = ss.plan;
+        const uint32_t M = plan.buckets();
+        memset(info, 0, sizeof(*info));
+        info->c = plan.c; info->W = plan.W; info->groups = plan.groups; info->merged = plan.merged ? 1 : 0;
+        info->B = plan.B; info->Lmax = plan.Lmax; info->max_tasks = ss.max_tasks; info->max_segments = ss.max_segments;
+        for (int k = 0; k < 10; ++k) info->K[k] = plan.K[k];
+        if (plan.affine_levels) return G16_ERR_BAD_ARG;   // padded bucket regions: `sorted` has holes, not this lab's subject
+        if ((uint64_t)M + 1 > bucket_cap) return G16_ERR_BAD_LENGTH;
+        G16_HIP_TRY(hipMemcpyAsync(offsets, ss.offsets, ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        G16_HIP_TRY(hipMemcpyAsync(task_off, ss.task_off, ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        G16_HIP_TRY(hipMemcpyAsync(heavy, ss.heavy, ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        G16_HIP_TRY(hipStreamSynchronize(st));
+        info->n_sorted = offsets[M];
+        if ((uint64_t)offsets[M] > ss.max_sorted) return G16_ERR_INTERNAL;   // more entries than the list was allocated for
+        if ((uint64_t)offsets[M] > sorted_cap) return G16_ERR_BAD_LENGTH;
+        if (offsets[M]) G16_HIP_TRY(hipMemcpy(sorted, ss.sorted, (size_t)offsets[M] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        drain.dismiss();
+        return G16_OK;
+    }
+
     // The window-table builder in place (test hook, g16_dev_window_table_lab): the points go up as they are, build_window_tables is
     // called as the key loader and msm_api call it -- it runs its own chunk loop, allocates its own parking buffer and picks its own
     // launch shape; park = nullptr makes it return with the table finished -- and the W * n records come back.  W is NOT checked

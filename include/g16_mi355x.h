@@ -548,6 +548,54 @@ int g16_host_pairing_op(int curve, int form, const uint32_t* operands, uint64_t 
 int g16_dev_msm_reduce_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, const uint32_t* nparts, const uint32_t* records,
                            uint64_t n_records, uint32_t* first_slots, uint64_t* out_affine);
 
+/* ---- the pass lab (test hook): the bucket pass's walk in place, on a caller-made sorted list ----
+ * A plan as in the reduction lab (merged, 2 <= c <= 16, `groups` groups of 2^(c-1) buckets, M = groups * 2^(c-1) <= 2^12 buckets, G = 8,
+ * 16 or 32) with segment length lseg (8 .. 4096), and 1 to 4 jobs that share it.  A job is a table of rows * base_count affine points in
+ * the ABI's form (rows = 1 for a per-window plan; row j of a merged plan's table is what window tag j addresses), uploaded as given and
+ * converted to the bucket pass's radix; `shift` and `base_count` as msm_bucket_pass takes them; counts[M], the entries per bucket; and
+ * `sorted`, the n_sorted = sum of counts entry words in bucket order, point | sign << 31 (merged: point | window << 26 | sign << 31).
+ * offsets, task_off and the heavy list are derived by the library's own layout code (the tail of sort_scalars); the partial-sum slots --
+ * task_off[M] records and 8 guard records behind them -- are filled with the byte 0xA5; the passes of all jobs run as ONE launch; the
+ * reductions and the fold then run per job.  Written per job: n_records = task_off[M]; records[0 .. n_records + 8) as the pass left them
+ * (the layout of the reduction lab's records; record_cap >= ceil(n_sorted / lseg) + M + 8, else G16_ERR_BAD_LENGTH); offsets, task_off and
+ * heavy, M + 1 words each (heavy[0] = count, then bucket ids in any order); out_affine, the folded sum as in the reduction lab.
+ * G16_ERR_BAD_ARG for what would let the kernel read outside what was uploaded: sum of counts != n_sorted, a merged entry whose window
+ * tag is >= rows, lseg outside 8 .. 4096, n_sorted > 2^16, M > 2^12, base_count > 2^16, |shift| > 2^40, n_jobs outside 1 .. 4, a null
+ * pointer.  A point index outside [0, base_count) after `shift` is NOT refused: the kernel skips such an entry. */
+typedef struct {
+    const uint64_t* table;
+    uint64_t base_count;
+    int64_t shift;
+    const uint32_t* counts;
+    const uint32_t* sorted;
+    uint64_t n_sorted;
+    uint64_t record_cap;
+    uint32_t* records;      /* out */
+    uint64_t n_records;     /* out */
+    uint32_t* offsets;      /* out */
+    uint32_t* task_off;     /* out */
+    uint32_t* heavy;        /* out */
+    uint64_t* out_affine;   /* out */
+} g16_pass_lab_job;
+int g16_dev_msm_pass_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, int lseg, int rows, g16_pass_lab_job* jobs, int n_jobs);
+
+/* ---- the sort lab (test hook): signed digits and the sort layout in place ----
+ * Uploads n <= 2^16 scalars (Fr, Montgomery limbs) and calls sort_scalars as the prover does: merged_c = 0 for a per-window plan (window
+ * size from the cost model or G16_MSM_WINDOW), 9 .. 20 for a merged plan, shard_n > 1 for rank shard_r's bucket-space share of a merged
+ * plan; G16_MSM_SEGMENT and the other environment knobs apply.  Returns the plan, the bounds the buffers were sized by, and the layout:
+ * offsets, task_off and heavy (M + 1 words each, M = groups * B; bucket_cap words available, else G16_ERR_BAD_LENGTH) and the first
+ * n_sorted = offsets[M] words of the sorted list (sorted_cap words available).  G16_MSM_AFFINE_LEVELS > 0 (padded bucket regions) is
+ * refused with G16_ERR_BAD_ARG. */
+typedef struct {
+    int32_t c, W, groups, merged;
+    uint32_t B, Lmax, max_tasks, max_segments;
+    uint32_t K[10];          /* the signed-digit bias, little-endian words */
+    uint32_t n_sorted;
+    uint32_t reserved;
+} g16_sort_lab_info;
+int g16_dev_msm_sort_lab(g16_ctx* ctx, const uint64_t* scalars, uint64_t n, int merged_c, int shard_n, int shard_r, g16_sort_lab_info* info,
+                         uint32_t* offsets, uint32_t* task_off, uint32_t* heavy, uint64_t bucket_cap, uint32_t* sorted, uint64_t sorted_cap);
+
 /* ---- verifier (src/verifier.rs:13-76, src/lib.rs:84-96) ------------------------------------------------------------
  * GT values cross as 12 Fq in arkworks' order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1 (Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - xi)),
  * Montgomery limbs as every other field element: byte-equal to PairingOutput.0.  Pairings are optimal ate with the exact final
@@ -686,7 +734,8 @@ const char* g16_version(void);
  * sizes (g16_struct_size), or uses the *_sized readers below, which copy min(size, library's size) bytes and never more. */
 #define G16_ABI_VERSION 2
 int g16_abi_version(void);
-enum { G16_STRUCT_TIMINGS = 0, G16_STRUCT_PK_INFO = 1, G16_STRUCT_DIAG = 2, G16_STRUCT_PROOF = 3, G16_STRUCT_PARTIAL = 4, G16_STRUCT_PK_VIEW = 5, G16_STRUCT_VK_VIEW = 6, G16_STRUCT_CHECK_RESULT = 7 };
+enum { G16_STRUCT_TIMINGS = 0, G16_STRUCT_PK_INFO = 1, G16_STRUCT_DIAG = 2, G16_STRUCT_PROOF = 3, G16_STRUCT_PARTIAL = 4, G16_STRUCT_PK_VIEW = 5, G16_STRUCT_VK_VIEW = 6, G16_STRUCT_CHECK_RESULT = 7,
+       G16_STRUCT_PASS_LAB_JOB = 8, G16_STRUCT_SORT_LAB_INFO = 9 };
 /* sizeof the library's own idea of a struct of this header; 0 for an unknown `which` */
 uint64_t g16_struct_size(int which);
 /* g16_get_timings / g16_pk_get_info into a caller struct of `size` bytes (its sizeof at ITS compile time) */

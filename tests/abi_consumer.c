@@ -56,6 +56,17 @@ static void layouts(void) {
     FIELD(g16_params_view, a_query); FIELD(g16_params_view, b_g1_query); FIELD(g16_params_view, b_g2_query);
     FIELD(g16_params_view, h_query); FIELD(g16_params_view, l_query); FIELD(g16_params_view, flags);
     END(g16_params_view);
+    BEGIN(g16_pass_lab_job);
+    FIELD(g16_pass_lab_job, table); FIELD(g16_pass_lab_job, base_count); FIELD(g16_pass_lab_job, shift); FIELD(g16_pass_lab_job, counts);
+    FIELD(g16_pass_lab_job, sorted); FIELD(g16_pass_lab_job, n_sorted); FIELD(g16_pass_lab_job, record_cap); FIELD(g16_pass_lab_job, records);
+    FIELD(g16_pass_lab_job, n_records); FIELD(g16_pass_lab_job, offsets); FIELD(g16_pass_lab_job, task_off); FIELD(g16_pass_lab_job, heavy);
+    FIELD(g16_pass_lab_job, out_affine);
+    END(g16_pass_lab_job);
+    BEGIN(g16_sort_lab_info);
+    FIELD(g16_sort_lab_info, c); FIELD(g16_sort_lab_info, W); FIELD(g16_sort_lab_info, groups); FIELD(g16_sort_lab_info, merged);
+    FIELD(g16_sort_lab_info, B); FIELD(g16_sort_lab_info, Lmax); FIELD(g16_sort_lab_info, max_tasks); FIELD(g16_sort_lab_info, max_segments);
+    FIELD(g16_sort_lab_info, K); FIELD(g16_sort_lab_info, n_sorted); FIELD(g16_sort_lab_info, reserved);
+    END(g16_sort_lab_info);
 }
 
 int main(int argc, char** argv) {
@@ -97,6 +108,7 @@ int main(int argc, char** argv) {
     if (g16_struct_size(G16_STRUCT_TIMINGS) != sizeof(g16_timings) || g16_struct_size(G16_STRUCT_PK_INFO) != sizeof(g16_pk_info) ||
         g16_struct_size(G16_STRUCT_DIAG) != sizeof(g16_diag) || g16_struct_size(G16_STRUCT_PROOF) != sizeof(g16_proof) ||
         g16_struct_size(G16_STRUCT_PARTIAL) != sizeof(g16_partial) || g16_struct_size(G16_STRUCT_PK_VIEW) != sizeof(g16_pk_view) ||
+        g16_struct_size(G16_STRUCT_PASS_LAB_JOB) != sizeof(g16_pass_lab_job) || g16_struct_size(G16_STRUCT_SORT_LAB_INFO) != sizeof(g16_sort_lab_info) ||
         g16_struct_size(99) != 0)
         ++failures;
     if (g16_get_timings_sized(NULL, a, sizeof a) == G16_OK || g16_pk_get_info_sized(NULL, a, 8) == G16_OK) ++failures;

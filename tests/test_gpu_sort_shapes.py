@@ -12,11 +12,15 @@ with the CPU oracle's MSM.  The sizes are the smallest at which each part of the
                          half zero (entries dropped at the first level)
   bucket-space shard     keys filtered by residue and re-indexed before the class split; the eight shares add up to the MSM
   padded regions         G16_MSM_AFFINE_LEVELS=1 keeps the histogram-matrix scatter (bucket regions padded, pre-filled with holes)
+  digit edges            the scalars of the sort lab (tests/pass_cases.py::digit_edge_scalars, for all four window sizes at once): every
+                         digit 2^(c-1) - 1, a digit of exactly -2^(c-1) at every window, one non-zero digit at every position; the
+                         sort lab checks where their entries land, this pins the sum end to end
 
 The oracle's result is computed once per (curve, scalar set) and shared by the window sizes."""
 import numpy as np
 import pytest
 
+import pass_cases as pc
 import pymodel as pm
 from helpers import ints_to_mont
 
@@ -28,6 +32,17 @@ WINDOWS = ["9", "13", "16", "20"]
 SIZES = [1, 255, 257, (1 << 13) + 1, 1 << 16]
 SKEWS = ["all_equal", "two_values", "zero_one_minus_one", "half_zero"]
 N_SKEW = 1 << 16
+
+
+def digit_edges(curve):
+    """the sort lab's edge scalars for every window size of this module, each once"""
+    r = CP[curve].r
+    out = []
+    for c in (int(w) for w in WINDOWS):
+        for s in pc.digit_edge_scalars(r, c, (r.bit_length() + c) // c):
+            if s not in out:
+                out.append(s)
+    return out
 
 
 @pytest.fixture(scope="module")
@@ -56,6 +71,8 @@ def cases(orc):
         cp = CP[curve]
         if kind == "uniform":
             return orc.rand_fr(curve, 900 + n, n)
+        if kind == "digit_edges":
+            return ints_to_mont(digit_edges(curve), cp.r, 4)
         if kind == "all_equal":
             return np.repeat(orc.rand_fr(curve, 901, 1), n, axis=0)
         if kind == "two_values":
@@ -108,6 +125,14 @@ def test_sort_skewed_scalars(env, cases, merged, kind, window):
     curve, prover = env
     merged(window)
     bases, sc, want = cases(curve, kind, N_SKEW)
+    assert (prover.msm(bases, sc) == want).all()
+
+
+@pytest.mark.parametrize("window", WINDOWS)
+def test_sort_digit_edge_scalars(env, cases, merged, window):
+    curve, prover = env
+    merged(window)
+    bases, sc, want = cases(curve, "digit_edges", len(digit_edges(curve)))
     assert (prover.msm(bases, sc) == want).all()
 
 
