@@ -26,16 +26,16 @@ Reference interface mirrored (paths relative to /root/reference):
       is_satisfied / which_is_unsatisfied, SynthesisError::Unsatisfiable) -- kept in "release": the check runs on the GPU
 """
 from .binding import (G16Error, Lib, PolynomialDegreeTooLarge, SynthesisError, UnexpectedIdentity, lib, FQ_LIMBS, CURVE_ID)  # noqa: F401
-from .groth16 import (CheckResult, CircomReduction, ConstraintMatrices, Groth16, LibsnarkReduction, PipelinedProver, Proof, ProvingKey, ShardedProver, finalize_host,  # noqa: F401
+from .groth16 import (CheckResult, CircomReduction, ConstraintMatrices, DeviceProvingKey, Groth16, LibsnarkReduction, PipelinedProver, Proof, ProvingKey, ShardedProver, finalize_host,  # noqa: F401
                       host_check_assignment, rerandomize_proof, shard_ranges)
-from .binding import MalformedVerifyingKey, Unsatisfiable  # noqa: F401
+from .binding import InvalidData, MalformedVerifyingKey, Unsatisfiable  # noqa: F401
 from .verifier import (PreparedVerifyingKey, VerifyingKey, check_subgroups_host, decompress_points_host, host_pairing, verify_proof_host,  # noqa: F401
-                       verify_proofs_aggregate_host, verify_proofs_aggregate_mixed_host)
+                       verify_proofs_aggregate_host, verify_proofs_aggregate_mixed_host, decode_points_host)
 from .r1cs import AssignmentMissing, ConstraintSynthesizer, ConstraintSystem, LinearCombination, Variable, lc  # noqa: F401
 
 __all__ = [
     "Groth16", "LibsnarkReduction", "CircomReduction", "ConstraintMatrices", "ProvingKey", "Proof", "ShardedProver", "PipelinedProver", "G16Error", "SynthesisError",
     "PolynomialDegreeTooLarge", "UnexpectedIdentity", "lib", "ConstraintSystem", "ConstraintSynthesizer", "Variable", "LinearCombination",
     "lc", "AssignmentMissing", "VerifyingKey", "PreparedVerifyingKey", "MalformedVerifyingKey", "verify_proof_host", "verify_proofs_aggregate_host", "verify_proofs_aggregate_mixed_host", "check_subgroups_host", "host_pairing",
-    "decompress_points_host", "CheckResult", "Unsatisfiable", "host_check_assignment",
+    "decompress_points_host", "CheckResult", "Unsatisfiable", "host_check_assignment", "DeviceProvingKey", "InvalidData", "decode_points_host",
 ]

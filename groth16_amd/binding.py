@@ -52,8 +52,22 @@ class Unsatisfiable(SynthesisError):
         self.a, self.b, self.c = (np.array(list(getattr(result, k)), dtype=np.uint64) if result is not None else None for k in "abc")
 
 
+PK_BYTES_SECTIONS = ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1", "beta_g1", "delta_g1", "a_query", "b_g1_query",
+                     "b_g2_query", "h_query", "l_query")   # a serialized ProvingKey in file order (g16_pk_bytes_info)
+
+
 class InvalidData(G16Error):
-    """ark_serialize::SerializationError::InvalidData"""
+    """ark_serialize::SerializationError::InvalidData.  From g16_pk_load_bytes it names the first failing point of the key in file
+    order: `.section` (a name of PK_BYTES_SECTIONS), `.index` within that section, `.reason` (0 the bytes do not decode, 2 off the
+    curve, 3 outside the prime-order subgroup) and `.n_bad`, the failing points of the whole key; None from every other call"""
+
+    def __init__(self, status: int, msg: str, info: "Optional[PkBytesInfoC]" = None):
+        super().__init__(status, msg)
+        named = info is not None and info.bad_section >= 0
+        self.section = PK_BYTES_SECTIONS[info.bad_section] if named else None
+        self.index = int(info.bad_index) if named else None
+        self.reason = int(info.bad_reason) if named else None
+        self.n_bad = int(info.n_bad) if named else None
 
 
 class QueryC(C.Structure):
@@ -118,6 +132,15 @@ class CheckResultC(C.Structure):
     _fields_ = [("n_unsatisfied", C.c_uint64), ("first_row", C.c_uint64), ("a", C.c_uint64 * 4), ("b", C.c_uint64 * 4), ("c", C.c_uint64 * 4)]
 
 
+class PkBytesInfoC(C.Structure):
+    """g16_pk_bytes_info"""
+    _fields_ = [("consumed", C.c_uint64), ("count", C.c_uint64 * 12), ("bad_section", C.c_int32), ("bad_reason", C.c_int32),
+                ("bad_index", C.c_uint64), ("n_bad", C.c_uint64)]
+
+    def counts(self) -> dict:
+        return {name: int(self.count[k]) for k, name in enumerate(PK_BYTES_SECTIONS)}
+
+
 class PassLabJobC(C.Structure):
     """g16_pass_lab_job"""
     _fields_ = [("table", u64p), ("base_count", C.c_uint64), ("shift", C.c_int64), ("counts", u32p), ("sorted", u32p), ("n_sorted", C.c_uint64),
@@ -161,6 +184,7 @@ EXPORTS = [
     "g16_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed_gt",
     "g16_circuit_load_qap", "g16_circuit_qap", "g16_generate_parameters_qap", "g16_h_query_len", "g16_host_h_query_scalars",
     "g16_circuit_attach_c", "g16_circuit_check", "g16_prove_checked", "g16_host_circuit_check",
+    "g16_decode_points", "g16_host_decode_points", "g16_host_pk_bytes_layout", "g16_pk_load_bytes", "g16_pk_load_bytes_timings",
 ]
 
 
@@ -300,6 +324,11 @@ class Lib:
         c.g16_prove_checked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, u64p, u64p, C.POINTER(ProofC),
                                         C.POINTER(CheckResultC)]
         c.g16_host_circuit_check.argtypes = [C.c_int, C.POINTER(CsrViewC), C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(CheckResultC)]
+        c.g16_decode_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, u64p, C.c_void_p]
+        c.g16_host_decode_points.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, u64p, C.c_void_p]
+        c.g16_host_pk_bytes_layout.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64]
+        c.g16_pk_load_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64]
+        c.g16_pk_load_bytes_timings.argtypes = [C.POINTER(C.c_double), C.c_int]
         c.g16_dev_fp30_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_fp30_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_dev_pairing_op.argtypes = [C.c_void_p, C.c_int, u32p, C.c_uint64, u32p]
@@ -311,8 +340,9 @@ class Lib:
         c.g16_dev_msm_sort_lab.argtypes = [C.c_void_p, u64p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(SortLabInfoC), u32p, u32p, u32p,
                                            C.c_uint64, u32p, C.c_uint64]
 
-    def check(self, status: int, check_result: "Optional[CheckResultC]" = None):
-        """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable"""
+    def check(self, status: int, check_result: "Optional[CheckResultC]" = None, pk_bytes_info: "Optional[PkBytesInfoC]" = None):
+        """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable; pk_bytes_info: the g16_pk_bytes_info
+        g16_pk_load_bytes filled, carried by InvalidData"""
         if status == 0:
             return
         msg = self.c.g16_strerror(status).decode()
@@ -324,7 +354,7 @@ class Lib:
         if status == 8:
             raise UnexpectedIdentity(status, msg)
         if status == 9:
-            raise InvalidData(status, msg)
+            raise InvalidData(status, msg, pk_bytes_info)
         if status == 11:
             raise MalformedVerifyingKey(status, msg)
         if status == 12:

@@ -367,6 +367,17 @@ int g16_pk_load(g16_ctx* ctx, const g16_pk_view* view, g16_pk** out) {
 // Bucket-space shard (round 5): the rank holds the WHOLE key as window tables and owns the buckets b mod world == rank of all five
 // MSMs; its g16_prove_partial[_h] then yields the partial sums over those buckets, and the ranks' records add up to the MSM sums in
 // g16_prove_finalize exactly like base-range shards' do.
+int g16_pk_load_bytes(g16_ctx* ctx, const uint8_t* bytes, uint64_t len, int compressed, int validate, g16_pk** out, void* info,
+                      uint64_t info_size) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || (!bytes && len) || (compressed != 0 && compressed != 1) || validate < 0 || validate > 2) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty()) {
+        g_last_error = "g16_pk_load_bytes: the bytes of a key are loaded whole, on one GPU (a multi-device context takes g16_pk_load)";
+        return G16_ERR_BAD_ARG;
+    }
+    return g16::pk_load_bytes(ctx, ctx->curve, ctx->device, ctx->stream, bytes, len, compressed, validate, out, info, info_size);
+}
+
 int g16_pk_load_bucket_shard(g16_ctx* ctx, const g16_pk_view* view, int rank, int world, g16_pk** out) {
     if (!ctx || !view || !out || world < 1 || world > 64 || rank < 0 || rank >= world) return G16_ERR_BAD_ARG;
     if (!ctx->subs.empty()) return G16_ERR_BAD_ARG;   // per-device form only (one process per GPU)

@@ -142,7 +142,57 @@ struct Decompress {
         *out = {x, ys};
         return 1;
     }
+
+    // ---- the uncompressed forms: x | y, by the rules of PointIo::read(compressed = false, ...) in serialize.hip -------------------
+    //   BLS12-381   flags in the first byte of x (x.c1): 0x80 must be clear, 0x20 (a sign has no place here) must be clear, 0x40 infinity
+    //   BN254       flags in the last byte of y (y.c1): 0x40 infinity, 0x80 the sign of y -- refused together with infinity, and NOT held
+    //               against y on a finite point (the host reader does not look at it either)
+    // Status 0: those flag rules, a coordinate >= p, infinity with x != 0 or y != 0.  Status 2 (only when check_curve is set, the
+    // reader's validate >= 1): a finite point that does not satisfy the curve equation; x = y = 0 without the infinity flag is such a
+    // point, although it has the identity's limbs.  Without check_curve whatever decodes is status 1, as on the host.
+    struct RawFlags { bool ok, inf; };
+    // top: the byte that carries the flags
+    G16_HD static RawFlags raw_flags(uint8_t top) {
+        if constexpr (ZCASH) return {(top & 0x80) == 0 && (top & 0x20) == 0, (top & 0x40) != 0};
+        else return {!((top & 0x40) && (top & 0x80)), (top & 0x40) != 0};
+    }
+    G16_HD static uint8_t g1_raw(const uint8_t* in, bool check_curve, typename C::G1A* out) {
+        *out = C::G1A::identity();
+        const RawFlags fl = raw_flags(in[ZCASH ? 0 : 2 * G1_BYTES - 1]);
+        typename C::G1A p;
+        if (!fl.ok || !read_fq(in, ZCASH, &p.x) || !read_fq(in + FQ_BYTES, !ZCASH, &p.y)) return 0;
+        if (fl.inf) return p.is_identity() ? 1 : 0;
+        if (check_curve && (p.is_identity() || !PP::g1_on_curve(p))) return 2;
+        *out = p;
+        return 1;
+    }
+    // (out may be the point's place in device memory, 16-byte aligned: the four coordinates are stored BEFORE the curve equation is
+    // evaluated and taken back if it fails, so that they need not stay in registers beside its Fq2 products)
+    G16_HD static uint8_t g2_raw(const uint8_t* in, bool check_curve, typename C::G2A* out) {
+        *out = C::G2A::identity();
+        const RawFlags fl = raw_flags(in[ZCASH ? 0 : 2 * G2_BYTES - 1]);
+        typename C::G2A p;
+        if (!fl.ok) return 0;
+        if (!read_fq(in, ZCASH, ZCASH ? &p.x.c1 : &p.x.c0) || !read_fq(in + FQ_BYTES, false, ZCASH ? &p.x.c0 : &p.x.c1)) return 0;
+        if (!read_fq(in + 2 * FQ_BYTES, false, ZCASH ? &p.y.c1 : &p.y.c0) || !read_fq(in + 3 * FQ_BYTES, !ZCASH, ZCASH ? &p.y.c0 : &p.y.c1))
+            return 0;
+        if (fl.inf) return p.is_identity() ? 1 : 0;
+        *out = p;
+        if (check_curve && (p.is_identity() || !PP::g2_on_curve(p))) {
+            *out = C::G2A::identity();
+            return 2;
+        }
+        return 1;
+    }
 };
+
+// What a point's status byte becomes once its membership flag (subgroup.hpp: 1 member, 0 on the curve but outside the subgroup, 2 off
+// the curve) is known -- the status codes of g16_decode_points: 1 passed, 0 the bytes do not decode, 2 off the curve, 3 outside the
+// subgroup.  A point that did not decode keeps its status (it was stored as the identity, which every membership test passes).
+G16_HD uint8_t decode_status_with_flag(uint8_t status, uint8_t flag) {
+    if (status != 1 || flag == 1) return status;
+    return flag == 2 ? 2 : 3;
+}
 
 // a proof decodes iff its three points do
 G16_HD uint8_t decompress_proof_status(uint8_t a, uint8_t b, uint8_t c) { return (a == 1 && b == 1 && c == 1) ? 1 : 0; }

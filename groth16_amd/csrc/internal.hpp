@@ -340,6 +340,12 @@ int serialize_points(int curve, int g2, int compressed, const uint64_t* points, 
 int deserialize_points(int curve, int g2, int compressed, const uint8_t* in, uint64_t n, int validate, uint64_t* points_out);
 uint64_t serialized_point_size(int curve, int g2, int compressed);
 
+// ---- a serialized proving key onto the GPU (key_bytes.hip) ------------------------------------------------
+// g16_pk_load_bytes on a single-device context (api.hip looks at the context and passes its curve, device and stream); the device
+// arrays it decodes go to g16_pk_load
+int pk_load_bytes(g16_ctx* ctx, int curve, int device, hipStream_t s, const uint8_t* bytes, uint64_t len, int compressed, int validate,
+                  g16_pk** out, void* info_out, uint64_t info_size);
+
 // ---- synthetic generators (synth.hip) -----------------------------------------------------------
 int mad_rate_device(hipStream_t st, double* mad_per_s);   // measured v_mad_u64_u32 lane-operations per second (diagnostic)
 template <class C> int synth_bases_device(int g2, uint64_t seed, uint64_t first, uint64_t n, void* out_dev, hipStream_t st);

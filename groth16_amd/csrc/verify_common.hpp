@@ -26,6 +26,11 @@ int subgroup_enqueue_proofs(hipStream_t s, int curve, const uint64_t* d_proofs, 
 // not decode.
 int decompress_enqueue_proofs(hipStream_t s, int curve, const uint8_t* d_bytes, uint64_t n, uint64_t* d_proofs, uint8_t* d_point_status,
                               uint8_t* d_status, int* d_summary);
+// The same two stages over n PACKED points of one group resident on the current device (key_bytes.hip: a proving key's queries): the
+// launches of g16_decompress_points / g16_check_subgroups without their uploads.  d_bytes: n compressed encodings, d_points: n affine
+// points (written by the first, read by the second), d_status / d_flags: one byte per point as those calls give it.
+int decompress_enqueue_points(hipStream_t s, int curve, int g2, const uint8_t* d_bytes, uint64_t n, uint64_t* d_points, uint8_t* d_status);
+int subgroup_enqueue_points(hipStream_t s, int curve, int g2, const uint64_t* d_points, uint64_t n, uint8_t* d_flags);
 // verify_aggregate.hip: the three single-key aggregate entry points, argument checks and the empty-batch rule included.  proofs
 // (affine) or bytes (compressed, decoded on the device; check must then be set), the other null
 int aggregate_call(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, const uint8_t* bytes, uint64_t n, const uint64_t* inputs,

@@ -88,6 +88,19 @@ int decompress_enqueue_proofs(hipStream_t s, int curve, const uint8_t* d_bytes, 
     return G16_ERR_BAD_ARG;
 }
 
+template <class C>
+int enqueue_decode_packed(hipStream_t s, int g2, const uint8_t* d_bytes, uint64_t n, uint64_t* d_points, uint8_t* d_status) {
+    constexpr int L = C::Fq::N / 2;
+    constexpr uint64_t FB = Decompress<C>::FQ_BYTES;
+    return enqueue_decode_points<C>(s, g2, d_bytes, g2 ? 2 * FB : FB, 0, d_points, g2 ? 4 * L : 2 * L, 0, 1, n, d_status);
+}
+
+int decompress_enqueue_points(hipStream_t s, int curve, int g2, const uint8_t* d_bytes, uint64_t n, uint64_t* d_points, uint8_t* d_status) {
+    if (curve == G16_BLS12_381) return enqueue_decode_packed<Bls12_381>(s, g2, d_bytes, n, d_points, d_status);
+    if (curve == G16_BN254) return enqueue_decode_packed<Bn254>(s, g2, d_bytes, n, d_points, d_status);
+    return G16_ERR_BAD_ARG;
+}
+
 // items: packed encodings (G1 or G2) or whole proofs (proofs = true); per item the affine form and one status byte, in input order
 template <class C>
 int decode_any(g16_ctx* ctx, bool proofs, int g2, const uint8_t* bytes, uint64_t n, uint64_t* out, uint8_t* status) {

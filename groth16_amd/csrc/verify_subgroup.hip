@@ -77,6 +77,12 @@ int subgroup_enqueue_proofs(hipStream_t s, int curve, const uint64_t* d_proofs, 
     return G16_ERR_BAD_ARG;
 }
 
+int subgroup_enqueue_points(hipStream_t s, int curve, int g2, const uint64_t* d_points, uint64_t n, uint8_t* d_flags) {
+    if (curve == G16_BLS12_381) return enqueue_points<Bls12_381>(s, g2, d_points, g2 ? 24 : 12, 0, 1, n, d_flags);
+    if (curve == G16_BN254) return enqueue_points<Bn254>(s, g2, d_points, g2 ? 16 : 8, 0, 1, n, d_flags);
+    return G16_ERR_BAD_ARG;
+}
+
 // items: packed points (words = 2 L or 4 L each) or whole proofs (proofs = true, 8 L words); one flag byte per item, in input order
 template <class C>
 int check_any(g16_ctx* ctx, bool proofs, int g2, const uint64_t* items, uint64_t n, uint8_t* flags) {

@@ -13,8 +13,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, PkInfoC, PkViewC, ProofC, QueryC, TimingsC, ToxicWasteC, lib,
-                      ptr32, ptr64, u64p)
+from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, TimingsC,
+                      ToxicWasteC, lib, ptr32, ptr64, u64p)
 
 _MODULUS_R = {
     "bls12_381": 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
@@ -250,6 +250,46 @@ class _DevicePk:
             self.ctx.lib.c.g16_pk_free(self.handle)
             self.handle = C.c_void_p()
 
+    @classmethod
+    def from_handle(cls, ctx: _Ctx, handle) -> "_DevicePk":
+        """a g16_pk the library made some other way (g16_pk_load_bytes)"""
+        self = cls.__new__(cls)
+        self.ctx, self.handle, self._keep = ctx, handle, []
+        return self
+
+
+class DeviceProvingKey:
+    """A proving key read from its bytes on the GPU (Groth16.load_proving_key_bytes, g16_pk_load_bytes): the five query arrays exist
+    only as the device-resident window tables behind the handle; the host holds the head of the file -- alpha_g1, beta_g1, delta_g1,
+    beta_g2, delta_g2, gamma_g2, gamma_abc_g1, so VerifyingKey.from_proving_key, prepare_verifying_key and rerandomize_proof take
+    it -- and `counts` (points per section of the file, by name) and `consumed` (bytes read).  It proves on the Groth16 object that
+    loaded it (or one sharing that object's device data), wherever a ProvingKey would; what needs the query arrays on the host
+    (shards, prove_partial*, ShardedProver, finalize_host, proving_key_to_bytes) raises TypeError."""
+
+    def __init__(self, curve: str, head: dict, counts: dict, consumed: int, ctx: _Ctx, dpk: _DevicePk):
+        self.curve = curve
+        for name, value in head.items():
+            setattr(self, name, value)
+        self.counts, self.consumed = counts, consumed
+        self._ctx, self._dpk = ctx, dpk
+
+    @property
+    def handle(self):
+        return self._dpk.handle
+
+    @property
+    def resident(self) -> bool:
+        return bool(self._dpk.handle)
+
+
+def _host_key(pk, what: str):
+    """refuse a DeviceProvingKey where the query arrays are read on the host"""
+    if isinstance(pk, DeviceProvingKey):
+        raise TypeError(f"{what} reads the key's query arrays on the host; a DeviceProvingKey (load_proving_key_bytes) holds them on "
+                        "the GPU only, as window tables: load the key with proving_key_from_bytes for this")
+    return pk
+
+
 def dist_h_indices(n: int, rank: int, world: int) -> np.ndarray:
     """h coefficients rank `rank` of `world` holds after the distributed witness map (g16_dwm_*): the BLOCK indices
     (rank * blk + j) + M * k1, j < blk = M / world, k1 < world, M = n / world, in the order [k1][j] -- the order its shard of
@@ -380,6 +420,7 @@ class Groth16:
         self.qap = qap
         self._ctx = _Ctx(curve, device)
         self._pks: Dict[Tuple[int, Tuple[int, int]], _DevicePk] = {}
+        self._byte_keys: List["DeviceProvingKey"] = []   # load_proving_key_bytes: freed by evict_pk / evict / close
         self._cks: Dict[int, _DeviceCircuit] = {}
         self._circuits_by_content: Dict[bytes, ConstraintMatrices] = {}   # create_proof_with_reduction: one upload per circuit
         self._owner: Optional["Groth16"] = None
@@ -399,6 +440,14 @@ class Groth16:
     def _pk(self, pk: ProvingKey, num_inputs: int, shard=(0, 1), dist_h: bool = False) -> _DevicePk:
         if self._owner is not None:
             return self._owner._pk(pk, num_inputs, shard, dist_h)
+        if isinstance(pk, DeviceProvingKey):
+            if tuple(shard) != (0, 1) or dist_h:
+                _host_key(pk, "a shard of a key")
+            if pk._ctx is not self._ctx:
+                raise ValueError("this DeviceProvingKey was loaded by another Groth16 object (its tables live in that object's context)")
+            if not pk.resident:
+                raise ValueError("this DeviceProvingKey was evicted: its tables are gone and the host holds no query arrays to reload them")
+            return pk._dpk
         if dist_h and self.qap is not LibsnarkReduction:
             # the block-order gather takes n = len(h_query) + 1 and feeds the distributed map, which is the Libsnark one
             raise ValueError("dist_h key shards (prove_partial_h, prove_partial_prepare(dist_h=True)) are for LibsnarkReduction only")
@@ -423,7 +472,12 @@ class Groth16:
 
     def evict_pk(self, pk: ProvingKey, shard=(0, 1)):
         """drop the device-resident copies of one key shard -- the contiguous cut and the block-order cut of the distributed
-        witness map alike (their window tables are 13x the shard)"""
+        witness map alike (their window tables are 13x the shard).  A DeviceProvingKey has nothing else: it cannot prove afterwards"""
+        if isinstance(pk, DeviceProvingKey):
+            if pk._ctx is self._ctx:
+                pk._dpk.close()
+                self._byte_keys = [k for k in self._byte_keys if k is not pk]
+            return
         for key in ((id(pk), shard), (id(pk), shard, "dist_h")):
             ent = self._pks.pop(key, None)
             if ent is not None:
@@ -435,6 +489,9 @@ class Groth16:
             p.close()
         for _, c in self._cks.values():
             c.close()
+        for k in self._byte_keys:
+            k._dpk.close()
+        self._byte_keys = []
         self._pks, self._cks = {}, {}
         self._circuits_by_content = {}
 
@@ -701,6 +758,39 @@ class Groth16:
         from .verifier import decompress_points
         return decompress_points(self._ctx, data, g2)
 
+    def decode_points(self, data, g2: bool = False, compressed: bool = True, validate: int = 2):
+        """encoded points of either form decoded AND validated on the GPU (g16_decode_points), point by point what
+        deserialize_points(compressed, validate) does to each: (points, status), status 1 and the point where that call accepts
+        it, else the identity and 0 the bytes do not decode / 2 off the curve / 3 outside the prime-order subgroup"""
+        from .verifier import decode_points
+        return decode_points(self._ctx, data, g2, compressed, validate)
+
+    def decode_points_host(self, data, g2: bool = False, compressed: bool = True, validate: int = 2):
+        """decode_points by the same templates on the CPU (g16_host_decode_points)"""
+        from .verifier import decode_points_host
+        return decode_points_host(self.curve, data, g2, compressed, validate)
+
+    def load_proving_key_bytes(self, data, compressed: bool = True, validate: int = 2) -> DeviceProvingKey:
+        """a serialized ProvingKey (proving_key_to_bytes' form) onto this object's GPU without the detour through host arrays
+        (g16_pk_load_bytes): the five queries are uploaded as bytes, decoded and validated on the device and turned into the
+        prover's window tables there.  validate as proving_key_from_bytes.  A key that call would refuse raises InvalidData
+        naming the first failing point in file order (.section, .index, .reason, .n_bad); nothing stays allocated.  Single-device
+        objects only."""
+        from .serialize import _Reader
+        if self._owner is not None:
+            raise ValueError("keys are loaded through the object that owns the device data (share_device_data_of)")
+        buf = bytes(data)   # (no copy of a bytes object)
+        info, handle, lb = PkBytesInfoC(), C.c_void_p(), self._ctx.lib
+        lb.check(lb.c.g16_pk_load_bytes(self._ctx.handle, buf, len(buf), int(bool(compressed)), int(validate), C.byref(handle), C.byref(info),
+                                        C.sizeof(info)), pk_bytes_info=info)
+        dpk = _DevicePk.from_handle(self._ctx, handle)
+        r = _Reader(self.curve, buf, compressed, 0)   # the head again, for the host (already validated by the call above)
+        head = dict(alpha_g1=r.point(False), beta_g2=r.point(True), gamma_g2=r.point(True), delta_g2=r.point(True), gamma_abc_g1=r.vec(False),
+                    beta_g1=r.point(False), delta_g1=r.point(False))
+        key = DeviceProvingKey(self.curve, head, info.counts(), int(info.consumed), self._ctx, dpk)
+        self._byte_keys.append(key)
+        return key
+
     def decompress_proofs(self, data):
         """compressed proofs A | B | C (proof_to_bytes(compressed=True), concatenated) decoded on the GPU (g16_decompress_proofs):
         (flat_proofs, status) -- the array verify_proofs takes and a byte per proof, 1 iff its three points decode"""
@@ -784,7 +874,7 @@ class Groth16:
         """the reference's signature ``(circuit, pk)`` (prover.rs:155-168), or the pure-data form
         ``(pk, matrices, num_inputs, num_constraints, full_assignment)``: r = s = 0"""
         zero = np.zeros(4, dtype=np.uint64)
-        if len(args) == 2 and not isinstance(args[0], ProvingKey):
+        if len(args) == 2 and not isinstance(args[0], (ProvingKey, DeviceProvingKey)):
             return self.create_proof_with_reduction(args[0], args[1], zero, zero)
         pk, matrices, num_inputs, num_constraints, full_assignment = args
         return self.create_proof_with_reduction_and_matrices(pk, zero, zero, matrices, num_inputs, num_constraints, full_assignment)
@@ -793,7 +883,7 @@ class Groth16:
     def create_random_proof_with_reduction(self, *args, rng=None) -> Proof:
         """the reference's signature ``(circuit, pk, rng)`` (prover.rs:138-150), or the pure-data form
         ``(pk, matrices, num_inputs, num_constraints, full_assignment[, rng])``: fresh r, s from rng"""
-        if not isinstance(args[0], ProvingKey):
+        if not isinstance(args[0], (ProvingKey, DeviceProvingKey)):
             circuit, pk = args[0], args[1]
             rng = args[2] if len(args) > 2 else rng
             return self.create_proof_with_reduction(circuit, pk, _rand_fr(self.curve, rng), _rand_fr(self.curve, rng))
@@ -856,6 +946,7 @@ class Groth16:
     # -- sharded form --------------------------------------------------------------------------
     def prove_partial(self, pk: ProvingKey, matrices: ConstraintMatrices, full_assignment: np.ndarray, shard: Tuple[int, int],
                       skip_b_g1: bool = False) -> bytes:
+        _host_key(pk, "prove_partial")
         dpk, dck = self._pk(pk, matrices.num_instance_variables, shard), self._ck(matrices)
         z = _c(full_assignment)
         part = PartialC()
@@ -868,6 +959,7 @@ class Groth16:
                               dist_h: bool = True):
         """g16_prove_partial_prepare: enqueue the witness digit/sort pass of the next prove_partial[_h] over this key shard and this
         DEVICE assignment now -- before the distributed witness map's stages -- so that the two run side by side"""
+        _host_key(pk, "prove_partial_prepare")
         dpk, dck = self._pk(pk, matrices.num_instance_variables, shard, dist_h=dist_h), self._ck(matrices)
         lb = self._ctx.lib
         lb.check(lb.c.g16_prove_partial_prepare(self._ctx.handle, dpk.handle, dck.handle, C.c_void_p(z_dev_ptr), n_assign))
@@ -876,6 +968,7 @@ class Groth16:
                                dist_h: bool = False):
         """g16_prove_finalize_prepare: start the (r, s)-only half of the glue of prover.rs:76-131 on a host thread now, so that it
         runs while the GPU computes this rank's partial sums; the next `finalize` over the same (key shard, r, s) picks it up"""
+        _host_key(pk, "prove_finalize_prepare")
         dpk = self._pk(pk, num_inputs, shard, dist_h=dist_h)
         lb = self._ctx.lib
         lb.check(lb.c.g16_prove_finalize_prepare(self._ctx.handle, dpk.handle, ptr64(np.ascontiguousarray(r, dtype=np.uint64)),
@@ -886,6 +979,7 @@ class Groth16:
         """g16_prove_partial_h: the shard's five partial sums with h supplied by the caller (device memory: this rank's block of
         the distributed witness map); the key shard is the one gathered in that block order (dist_h).  z_dev_ptr != 0: the
         assignment is taken from device memory (`full_assignment` then only gives the length)"""
+        _host_key(pk, "prove_partial_h")
         dpk, dck = self._pk(pk, matrices.num_instance_variables, shard, dist_h=True), self._ck(matrices)
         part = PartialC()
         lb = self._ctx.lib
@@ -901,6 +995,7 @@ class Groth16:
 
     def prove_finalize(self, pk: ProvingKey, num_inputs: int, parts: Sequence[bytes], r: np.ndarray, s: np.ndarray,
                        shard: Tuple[int, int] = (0, 1), dist_h: bool = False) -> Proof:
+        _host_key(pk, "prove_finalize")
         L = FQ_LIMBS[self.curve]
         dpk = self._pk(pk, num_inputs, shard, dist_h)   # any shard carries the eight fixed points the glue reads
         arr = (PartialC * len(parts))(*[PartialC.from_buffer_copy(p) for p in parts])
@@ -945,6 +1040,7 @@ def fixed_points_view(pk: "ProvingKey"):
 
 def finalize_host(curve: str, pk: "ProvingKey", parts: Sequence[bytes], r: np.ndarray, s: np.ndarray) -> "Proof":
     """g16_finalize_host: N-way EC fold of shard records + the prover.rs:76-131 glue, no GPU needed"""
+    _host_key(pk, "finalize_host")
     L = FQ_LIMBS[curve]
     view, keep = fixed_points_view(pk)
     arr = (PartialC * len(parts))(*[PartialC.from_buffer_copy(p) for p in parts])
@@ -1163,6 +1259,7 @@ class ShardedProver:
         (g16_pk_load_bucket_shard)"""
         if mode not in ("base", "bucket"):
             raise ValueError("mode is 'base' or 'bucket'")
+        _host_key(pk, "ShardedProver")
         self.prover, self.pk, self.matrices = prover, pk, matrices
         self.rank, self.world, self.mode = rank, world_size, mode
         self.shard = (rank, world_size, "bucket") if mode == "bucket" and world_size > 1 else (rank, world_size)

@@ -17,7 +17,7 @@ from typing import Tuple
 import numpy as np
 
 from .binding import CURVE_ID, FQ_LIMBS, lib, ptr64
-from .groth16 import Proof, ProvingKey
+from .groth16 import Proof, ProvingKey, _host_key
 
 
 def point_size(curve: str, g2: bool, compressed: bool) -> int:
@@ -94,6 +94,7 @@ def verifying_key_to_bytes(curve: str, pk: ProvingKey, compressed: bool = True) 
 
 
 def proving_key_to_bytes(curve: str, pk: ProvingKey, compressed: bool = True) -> bytes:
+    _host_key(pk, "proving_key_to_bytes")
     return (verifying_key_to_bytes(curve, pk, compressed) + serialize_points(curve, pk.beta_g1, False, compressed) +
             serialize_points(curve, pk.delta_g1, False, compressed) + _vec(curve, pk.a_query, False, compressed) +
             _vec(curve, pk.b_g1_query, False, compressed) + _vec(curve, pk.b_g2_query, True, compressed) +

@@ -240,6 +240,29 @@ def decompress_points_host(curve: str, data, g2: bool = False):
     return out, status
 
 
+def _decode_points(call, curve: str, data, g2: bool, compressed: bool, validate: int):
+    L = FQ_LIMBS[curve]
+    size = _fq_bytes(curve) * (2 if g2 else 1) * (1 if compressed else 2)
+    enc = _encoded(data, size)
+    n = enc.size // size
+    out = np.zeros((n, (4 if g2 else 2) * L), dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint8)
+    lib().check(call(int(bool(g2)), int(bool(compressed)), int(validate), _u8ptr(enc), n, ptr64(out.reshape(-1)) if n else None, _u8ptr(status)))
+    return out, status
+
+
+def decode_points(ctx, data, g2: bool = False, compressed: bool = True, validate: int = 2):
+    """g16_decode_points: packed encodings (either form) decoded and validated on the GPU, point by point what
+    deserialize_points(compressed, validate) does to each.  (points, status): status 1 and the point where that call accepts it,
+    else the identity and 0 the bytes do not decode / 2 off the curve / 3 outside the prime-order subgroup"""
+    return _decode_points(lambda *a: lib().c.g16_decode_points(ctx.handle, *a), ctx.curve, data, g2, compressed, validate)
+
+
+def decode_points_host(curve: str, data, g2: bool = False, compressed: bool = True, validate: int = 2):
+    """decode_points on the CPU through g16_host_decode_points (the same C++ templates, no GPU): (points, status)"""
+    return _decode_points(lambda *a: lib().c.g16_host_decode_points(CURVE_ID[curve], *a), curve, data, g2, compressed, validate)
+
+
 def verify_aggregate_bytes(ctx, pvk: PreparedVerifyingKey, data, public_inputs_list, coeffs=None) -> int:
     """g16_verify_aggregate_bytes' verdict over compressed proofs, decoded and membership-tested on the GPU: 1 every proof holds,
     0 the aggregate equation fails, 3 a point is outside its prime-order subgroup, 4 some proof's bytes do not decode (4 wins over 3)"""

@@ -724,6 +724,57 @@ int g16_host_decompress_points(int curve, int g2, const uint8_t* bytes, uint64_t
 int g16_verify_aggregate_bytes(g16_ctx* ctx, const g16_pvk* pvk, const uint8_t* proof_bytes, uint64_t n, const uint64_t* public_inputs,
                                uint64_t num_public, const uint64_t* coeffs, uint8_t* verdict);
 
+/* ---- a serialized proving key onto the GPU: bytes to window tables ----
+ * g16_decompress_points generalised to both encodings and the three validation levels of g16_deserialize_points, one point per GPU
+ * lane.  bytes: n packed encodings in host memory (g2 = 0: G1, 1: G2; compressed = 0: x | y, twice the size), points_out: n affine
+ * points, status: n bytes.  Per point, where g16_deserialize_points(compressed, validate) on that one point returns G16_OK the status
+ * is 1 and the point byte-equal to its output; otherwise the identity (all-zero) is stored and the status says why:
+ *   0  the bytes do not decode (flags, a coordinate >= p, infinity with a non-zero coordinate, a compressed x with no point)
+ *   2  decoded but off the curve          (uncompressed input with validate >= 1 only: validate = 0 makes no on-curve test)
+ *   3  on the curve, outside the subgroup (validate = 2 only)
+ * in that precedence.  Compressed input and the membership tests run the kernels of g16_decompress_points / g16_check_subgroups.
+ * n = 0 is G16_OK.  A multi-device ctx cuts the array into one chunk per device; outputs stay in input order. */
+int g16_decode_points(g16_ctx* ctx, int g2, int compressed, int validate, const uint8_t* bytes, uint64_t n, uint64_t* points_out,
+                      uint8_t* status);
+/* the same templates on the CPU (no GPU needed) */
+int g16_host_decode_points(int curve, int g2, int compressed, int validate, const uint8_t* bytes, uint64_t n, uint64_t* points_out,
+                           uint8_t* status);
+
+/* What a ProvingKey<E> in CanonicalSerialize form holds (src/data_structures.rs:31-44, 125-143), section by section in file order:
+ *   0 alpha_g1  1 beta_g2  2 gamma_g2  3 delta_g2  4 gamma_abc_g1 (Vec)  5 beta_g1  6 delta_g1
+ *   7 a_query   8 b_g1_query   9 b_g2_query (Vec<G2>)   10 h_query   11 l_query          (7 .. 11: Vec)
+ * A Vec is a little-endian u64 count followed by its points.  Not registered in g16_struct_size: the two functions below copy
+ * min(info_size, sizeof(g16_pk_bytes_info)) bytes, like the *_sized readers. */
+#define G16_PK_BYTES_SECTIONS 12
+typedef struct {
+    uint64_t consumed;                     /* bytes of the key (trailing bytes are not an error); 0 if the walk failed             */
+    uint64_t count[G16_PK_BYTES_SECTIONS]; /* points per section, 1 for a single point; a Vec's count as its length word states it */
+    int32_t bad_section;                   /* -1: nothing wrong; else the section of the first failure in file order               */
+    int32_t bad_reason;                    /* the point's status 0 / 2 / 3 as g16_decode_points, or 4: the bytes end inside this
+                                              section or its count does not fit what is left (bad_index and n_bad are then 0)      */
+    uint64_t bad_index;                    /* index of that point within its section                                               */
+    uint64_t n_bad;                        /* failing points in the whole key                                                      */
+} g16_pk_bytes_info;
+/* The container walk alone, on the host (no GPU needed): every count is checked against the bytes that are left, without overflow
+ * and before anything is allocated.  G16_ERR_BAD_LENGTH (bad_reason 4) for a key that ends early or a count that cannot fit. */
+int g16_host_pk_bytes_layout(int curve, const uint8_t* bytes, uint64_t len, int compressed, void* info, uint64_t info_size);
+/* g16_pk_load from the key's bytes (what proving_key_to_bytes writes), with the five queries decoded and validated on the GPU:
+ * after the walk above, the head (sections 0 .. 6, a handful of points) is read by g16_deserialize_points; each query is uploaded
+ * in chunks of 2^20 points (environment G16_PK_BYTES_CHUNK, read at call time, at least 64), decoded by g16_decode_points' kernels
+ * straight into one device array, membership-tested there when validate = 2, and its statuses folded into one record.  All five
+ * arrays then go to g16_pk_load as device pointers (a, b_g1, b_g2 from index 1; their first points return to the host for the
+ * glue) and are freed once the window tables are built: *out is an ordinary g16_pk.  The table fallbacks and the 2^27 limit are
+ * g16_pk_load's.  validate as g16_deserialize_points; a key it would refuse is refused here with G16_ERR_INVALID_DATA, *out NULL,
+ * nothing left allocated, and info naming the FIRST failing point in file order (whatever order the GPU met them in) and n_bad.
+ * G16_ERR_BAD_LENGTH as the walk, or for an empty a_query / b_g1_query / b_g2_query.  G16_ERR_BAD_ARG (g16_last_error says why) for
+ * a multi-device ctx: the bytes of a key are loaded whole, on one GPU.  info may be NULL. */
+int g16_pk_load_bytes(g16_ctx* ctx, const uint8_t* bytes, uint64_t len, int compressed, int validate, g16_pk** out, void* info,
+                      uint64_t info_size);
+/* milliseconds the last successful g16_pk_load_bytes on this thread spent: ms[0] walk + head (host clock), ms[1] uploads, ms[2] decode
+ * kernels, ms[3] membership kernels + folds (device events, summed over the chunks), ms[4] g16_pk_load (host clock; it ends in a
+ * device synchronise).  Writes min(n, 5) values. */
+int g16_pk_load_bytes_timings(double* ms, int n);
+
 const char* g16_strerror(int status);
 /* text of the last HIP error seen on this thread ("" if none) */
 const char* g16_last_error(void);
