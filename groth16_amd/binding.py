@@ -96,6 +96,20 @@ class ParamsViewC(C.Structure):
                [(n, C.c_void_p) for n in ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query")] + [("flags", C.c_uint32)]
 
 
+class SrsViewC(C.Structure):
+    """g16_srs_view"""
+    _fields_ = [("tau_g1", u64p), ("n_tau_g1", C.c_uint64), ("tau_g2", u64p), ("n_tau_g2", C.c_uint64), ("alpha_tau_g1", u64p),
+                ("beta_tau_g1", u64p), ("n_alpha_beta", C.c_uint64), ("beta_g2", u64p)]
+
+
+class SrsTimingsC(C.Structure):
+    """g16_srs_timings"""
+    _fields_ = [(n, C.c_double) for n in ("transforms_ms", "products_ms", "h_ms", "delta_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class VkViewC(C.Structure):
     _fields_ = [(n, u64p) for n in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")] + [("n_gamma_abc", C.c_uint64)]
 
@@ -185,6 +199,8 @@ EXPORTS = [
     "g16_circuit_load_qap", "g16_circuit_qap", "g16_generate_parameters_qap", "g16_h_query_len", "g16_host_h_query_scalars",
     "g16_circuit_attach_c", "g16_circuit_check", "g16_prove_checked", "g16_host_circuit_check",
     "g16_decode_points", "g16_host_decode_points", "g16_host_pk_bytes_layout", "g16_pk_load_bytes", "g16_pk_load_bytes_timings",
+    "g16_srs_segment_len", "g16_generate_parameters_srs", "g16_params_apply_delta", "g16_group_ntt", "g16_srs_from_trapdoor",
+    "g16_srs_get_timings", "g16_host_group_ntt", "g16_host_generate_parameters_srs",
 ]
 
 
@@ -329,6 +345,16 @@ class Lib:
         c.g16_host_pk_bytes_layout.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64]
         c.g16_pk_load_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64]
         c.g16_pk_load_bytes_timings.argtypes = [C.POINTER(C.c_double), C.c_int]
+        c.g16_srs_segment_len.argtypes = []
+        c.g16_srs_segment_len.restype = C.c_uint64
+        c.g16_generate_parameters_srs.argtypes = [C.c_void_p, C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
+                                                  C.POINTER(SrsViewC), C.POINTER(ParamsViewC)]
+        c.g16_host_generate_parameters_srs.argtypes = [C.c_int] + c.g16_generate_parameters_srs.argtypes[1:]
+        c.g16_params_apply_delta.argtypes = [C.c_void_p, u64p, C.POINTER(ParamsViewC), C.c_uint64, C.c_uint64]
+        c.g16_group_ntt.argtypes = [C.c_void_p, C.c_int, u64p, C.c_int, C.c_int, u64p]
+        c.g16_host_group_ntt.argtypes = [C.c_int, C.c_int, u64p, C.c_int, C.c_int, u64p]
+        c.g16_srs_from_trapdoor.argtypes = [C.c_void_p, u64p, u64p, u64p, u64p, u64p, C.c_uint64, C.c_uint64, C.POINTER(SrsViewC)]
+        c.g16_srs_get_timings.argtypes = [C.c_void_p, C.POINTER(SrsTimingsC)]
         c.g16_dev_fp30_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_fp30_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_dev_pairing_op.argtypes = [C.c_void_p, C.c_int, u32p, C.c_uint64, u32p]

@@ -14,10 +14,12 @@
 #include "prover.hpp"
 #include "proof_glue.hpp"
 #include "unit_api.hpp"
+#include "srs_setup.hpp"
 
 namespace {
 template <class C>
 struct Impl : KeyLoader<C>, Prover<C>, ProofGlue<C>, UnitApi<C> {
+    typedef C Curve;
     typedef typename C::Fr Fr;
     typedef typename C::Fq Fq;
     typedef typename C::Fq2 Fq2;
@@ -73,6 +75,49 @@ int ctx_devices(const g16_ctx* ctx, int* curve, std::vector<int>& devs, std::vec
     return G16_OK;
 }
 }  // namespace g16
+
+// ---- setup from an SRS: what the two entry points (device and host form) check alike ----
+// the SRS covers a domain of n points: tau_g1 up to index 2n - 2, the others up to n - 1 (an SRS longer than that is fine)
+static int srs_check_lengths(const g16_srs_view* srs, uint64_t n) {
+    const struct { const char* name; const void* p; uint64_t have, need; } arr[] = {
+        {"tau_g1", srs->tau_g1, srs->n_tau_g1, 2 * n - 1},
+        {"tau_g2", srs->tau_g2, srs->n_tau_g2, n},
+        {"alpha_tau_g1 / beta_tau_g1 (one count)", srs->alpha_tau_g1, srs->n_alpha_beta, n},
+    };
+    if (!srs->beta_tau_g1) return G16_ERR_BAD_ARG;
+    for (const auto& a : arr) {
+        if (!a.p) return G16_ERR_BAD_ARG;
+        if (a.have < a.need) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "SRS too short: %s holds %llu points, a domain of %llu needs %llu", a.name, (unsigned long long)a.have,
+                     (unsigned long long)n, (unsigned long long)a.need);
+            g_last_error = buf;
+            return G16_ERR_BAD_LENGTH;
+        }
+    }
+    return srs->beta_g2 ? G16_OK : G16_ERR_BAD_ARG;
+}
+
+template <class C>
+static int srs_generate_checked(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int qap, const g16_srs_view* srs,
+                                const g16_params_view* out) {
+    int log_n = 0;
+    G16_TRY(srs_domain_log<C>(ni, nc, nv, qap, &log_n));
+    G16_TRY(srs_check_lengths(srs, (uint64_t)1 << log_n));
+    if (!ctx) return srs_generate_host<C>(abc, ni, nc, nv, qap, srs, out);
+    double ms[3] = {0, 0, 0};
+    G16_TRY(srs_generate_device<C>(ctx->stream, ctx->arena, abc, ni, nc, nv, qap, srs, out, ms));
+    ctx->srs_tm.transforms_ms = ms[0];
+    ctx->srs_tm.products_ms = ms[1];
+    ctx->srs_tm.h_ms = ms[2];
+    return G16_OK;
+}
+
+static bool srs_params_ok(const g16_params_view* out, uint64_t ni, uint64_t nv) {
+    if (!out->alpha_g1 || !out->beta_g1 || !out->delta_g1 || !out->beta_g2 || !out->delta_g2 || !out->gamma_g2) return false;
+    if (out->flags & G16_PARAMS_DEVICE_PTRS) return false;
+    return out->gamma_abc_g1 && out->a_query && out->b_g1_query && out->b_g2_query && out->h_query && (out->l_query || nv <= ni);
+}
 
 // g16_pk_load on a multi-device context: the retry with base ranges after an automatic bucket-space load ran out of memory
 static thread_local bool g_multi_force_base = false;
@@ -1083,6 +1128,73 @@ int g16_host_qap_evaluations(int curve, const g16_csr_view abc[3], uint64_t num_
         return G16_ERR_OOM;
     }
     return G16_ERR_BAD_ARG;
+}
+
+// ---- setup from an SRS (srs_setup.hip) ----
+uint64_t g16_srs_segment_len(void) { return SRS_SEGMENT_LEN; }
+
+int g16_generate_parameters_srs(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints, uint64_t num_variables,
+                                int qap, const g16_srs_view* srs, const g16_params_view* out) {
+    if (!ctx || !abc || !srs || !out) return G16_ERR_BAD_ARG;
+    if (qap != G16_QAP_LIBSNARK && qap != G16_QAP_CIRCOM) return G16_ERR_BAD_ARG;
+    if (!srs_params_ok(out, num_inputs, num_variables)) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty()) return g16_generate_parameters_srs(ctx->subs[0], abc, num_inputs, num_constraints, num_variables, qap, srs, out);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->prep.valid) (void)hipStreamSynchronize(ctx->stream2);   // a dropped prepared sort still owns arena buffers
+    ctx->prep.valid = false;   // the generator resets the arena
+    G16_DISPATCH(ctx->curve, (srs_generate_checked<typename I::Curve>(ctx, abc, num_inputs, num_constraints, num_variables, qap, srs, out)));
+}
+
+int g16_host_generate_parameters_srs(int curve, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints,
+                                     uint64_t num_variables, int qap, const g16_srs_view* srs, const g16_params_view* out) {
+    if (!abc || !srs || !out) return G16_ERR_BAD_ARG;
+    if (qap != G16_QAP_LIBSNARK && qap != G16_QAP_CIRCOM) return G16_ERR_BAD_ARG;
+    if (!srs_params_ok(out, num_inputs, num_variables)) return G16_ERR_BAD_ARG;
+    G16_DISPATCH(curve, (srs_generate_checked<typename I::Curve>(nullptr, abc, num_inputs, num_constraints, num_variables, qap, srs, out)));
+}
+
+int g16_params_apply_delta(g16_ctx* ctx, const uint64_t delta[4], const g16_params_view* inout, uint64_t n_l_query, uint64_t n_h_query) {
+    if (!ctx || !delta || !inout || !inout->delta_g1 || !inout->delta_g2) return G16_ERR_BAD_ARG;
+    if ((inout->flags & G16_PARAMS_DEVICE_PTRS) || (n_l_query && !inout->l_query) || (n_h_query && !inout->h_query)) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty()) return g16_params_apply_delta(ctx->subs[0], delta, inout, n_l_query, n_h_query);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->prep.valid) (void)hipStreamSynchronize(ctx->stream2);
+    ctx->prep.valid = false;
+    G16_DISPATCH(ctx->curve, (srs_apply_delta_device<typename I::Curve>(ctx->stream, ctx->arena, delta, inout, n_l_query, n_h_query,
+                                                                         &ctx->srs_tm.delta_ms)));
+}
+
+int g16_group_ntt(g16_ctx* ctx, int g2, const uint64_t* points, int log_n, int inverse, uint64_t* out) {
+    if (!ctx || !points || !out) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty()) return g16_group_ntt(ctx->subs[0], g2, points, log_n, inverse, out);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->prep.valid) (void)hipStreamSynchronize(ctx->stream2);
+    ctx->prep.valid = false;
+    G16_DISPATCH(ctx->curve, (srs_group_ntt_device<typename I::Curve>(ctx->stream, ctx->arena, g2, points, log_n, inverse, out)));
+}
+
+int g16_host_group_ntt(int curve, int g2, const uint64_t* points, int log_n, int inverse, uint64_t* out) {
+    if (!points || !out) return G16_ERR_BAD_ARG;
+    G16_DISPATCH(curve, (srs_group_ntt_host<typename I::Curve>(g2, points, log_n, inverse, out)));
+}
+
+int g16_srs_from_trapdoor(g16_ctx* ctx, const uint64_t tau[4], const uint64_t alpha[4], const uint64_t beta[4], const uint64_t* g1_generator,
+                          const uint64_t* g2_generator, uint64_t n_tau_g1, uint64_t n_other, const g16_srs_view* out) {
+    if (!ctx || !tau || !alpha || !beta || !g1_generator || !g2_generator || !out) return G16_ERR_BAD_ARG;
+    if (!out->tau_g1 || !out->tau_g2 || !out->alpha_tau_g1 || !out->beta_tau_g1 || !out->beta_g2) return G16_ERR_BAD_ARG;
+    if (out->n_tau_g1 < n_tau_g1 || out->n_tau_g2 < n_other || out->n_alpha_beta < n_other) return G16_ERR_BAD_LENGTH;
+    if (!ctx->subs.empty()) return g16_srs_from_trapdoor(ctx->subs[0], tau, alpha, beta, g1_generator, g2_generator, n_tau_g1, n_other, out);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->prep.valid) (void)hipStreamSynchronize(ctx->stream2);
+    ctx->prep.valid = false;
+    G16_DISPATCH(ctx->curve, (srs_from_trapdoor_device<typename I::Curve>(ctx->stream, ctx->arena, tau, alpha, beta, g1_generator, g2_generator,
+                                                                           n_tau_g1, n_other, out)));
+}
+
+int g16_srs_get_timings(g16_ctx* ctx, g16_srs_timings* out) {
+    if (!ctx || !out) return G16_ERR_BAD_ARG;
+    *out = ctx->subs.empty() ? ctx->srs_tm : ctx->subs[0]->srs_tm;
+    return G16_OK;
 }
 
 uint64_t g16_serialized_point_size(int curve, int g2, int compressed) { return g16::serialized_point_size(curve, g2, compressed); }

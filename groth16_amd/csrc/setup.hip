@@ -12,6 +12,7 @@
 // The reference samples t itself (domain.sample_element_outside_domain, generator.rs:90); here the caller passes it with the
 // rest of the toxic waste, so that a run can be reproduced (the parity tests replay the oracle's trapdoor).
 #include "internal.hpp"
+#include "srs_setup.hpp"
 #include <algorithm>
 
 namespace g16 {
@@ -231,6 +232,45 @@ int generate_parameters_device(hipStream_t st, Arena& arena, const g16_csr_view 
     return Setup<C>::generate(st, arena, abc, ni, nc, nv, qap, tw, g1_gen, g2_gen, out);
 }
 
+// An SRS from known secrets with the fixed-base kernels above (a test and benchmark utility: a real SRS comes from a ceremony)
+template <class C>
+int srs_from_trapdoor_device(hipStream_t st, Arena& arena, const uint64_t* tau_, const uint64_t* alpha_, const uint64_t* beta_,
+                             const uint64_t* g1_gen, const uint64_t* g2_gen, uint64_t n_tau_g1, uint64_t n_other, const g16_srs_view* out) {
+    typedef typename C::Fr Fr;
+    typedef typename C::Fq Fq;
+    typedef typename C::Fq2 Fq2;
+    typedef Setup<C> S;
+    const Fr tau = S::load_fr(tau_), alpha = S::load_fr(alpha_), beta = S::load_fr(beta_);
+    std::vector<Fr> pw(std::max(n_tau_g1, n_other)), sc(n_other);
+    Fr p = Fr::one();
+    for (auto& x : pw) { x = p; p = p * tau; }
+    arena.reset();
+    Affine<Fq>* t1 = nullptr;
+    Affine<Fq2>* t2 = nullptr;
+    G16_TRY(arena.alloc_n((size_t)FB_WINDOWS * FB_DIGITS, &t1));
+    G16_TRY(arena.alloc_n((size_t)FB_WINDOWS * FB_DIGITS, &t2));
+    Affine<Fq> g1;
+    Affine<Fq2> g2;
+    memcpy(&g1, g1_gen, sizeof(g1));
+    memcpy(&g2, g2_gen, sizeof(g2));
+    const unsigned tb = (FB_WINDOWS * FB_DIGITS + 63) / 64;
+    hipLaunchKernelGGL((fixed_base_table_kernel<Fq>), dim3(tb), dim3(64), 0, st, g1, t1);
+    G16_LAUNCH_CHECK();
+    hipLaunchKernelGGL((fixed_base_table_kernel<Fq2>), dim3(tb), dim3(64), 0, st, g2, t2);
+    G16_LAUNCH_CHECK();
+    for (uint64_t i = 0; i < n_other; ++i) sc[i] = pw[i];
+    G16_TRY(S::template batch_mul<Fq2>(t2, sc, arena, st, out->tau_g2, false));
+    for (uint64_t i = 0; i < n_other; ++i) sc[i] = pw[i] * alpha;
+    G16_TRY(S::template batch_mul<Fq>(t1, sc, arena, st, out->alpha_tau_g1, false));
+    for (uint64_t i = 0; i < n_other; ++i) sc[i] = pw[i] * beta;
+    G16_TRY(S::template batch_mul<Fq>(t1, sc, arena, st, out->beta_tau_g1, false));
+    pw.resize(n_tau_g1);
+    G16_TRY(S::template batch_mul<Fq>(t1, pw, arena, st, out->tau_g1, false));
+    std::vector<Fr> b1(1, beta);
+    G16_TRY(S::template batch_mul<Fq2>(t2, b1, arena, st, out->beta_g2, false));
+    return G16_OK;
+}
+
 template <class C>
 int h_query_scalars_host(int qap, uint64_t domain_size, const uint64_t* t_, const uint64_t* delta_inverse, uint64_t* out) {
     typedef typename C::Fr Fr;
@@ -266,6 +306,8 @@ int qap_evaluations_host(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, ui
     template int generate_parameters_device<C>(hipStream_t, Arena&, const g16_csr_view*, uint64_t, uint64_t, uint64_t, int,             \
                                                const g16_toxic_waste*, const uint64_t*, const uint64_t*, const g16_params_view*);       \
     template int h_query_scalars_host<C>(int, uint64_t, const uint64_t*, const uint64_t*, uint64_t*);                                   \
+    template int srs_from_trapdoor_device<C>(hipStream_t, Arena&, const uint64_t*, const uint64_t*, const uint64_t*, const uint64_t*,   \
+                                             const uint64_t*, uint64_t, uint64_t, const g16_srs_view*);                                 \
     template int qap_evaluations_host<C>(const g16_csr_view*, uint64_t, uint64_t, uint64_t, const uint64_t*, uint64_t*, uint64_t*,      \
                                          uint64_t*, uint64_t*);
 G16_INSTANTIATE_SETUP(Bls12_381)

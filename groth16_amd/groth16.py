@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, TimingsC,
+from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, SrsTimingsC, SrsViewC, TimingsC,
                       ToxicWasteC, lib, ptr32, ptr64, u64p)
 
 _MODULUS_R = {
@@ -111,6 +111,85 @@ class ProvingKey:
     # the rest of the VerifyingKey (data_structures.rs:28-41); the prover never reads these
     gamma_g2: Optional[np.ndarray] = None
     gamma_abc_g1: Optional[np.ndarray] = None
+
+
+@dataclass
+class SRS:
+    """A phase-1 structured reference string (powers of tau) as g16_srs_view takes it: affine Montgomery limbs, one point per row.
+    tau_g1[i] = tau^i G1 (a domain of n points needs 2n - 1 of them), tau_g2[i] = tau^i G2, alpha_tau_g1[i] = alpha tau^i G1,
+    beta_tau_g1[i] = beta tau^i G1 (n each), beta_g2 = beta G2.  Longer arrays are fine: the prefix is used."""
+
+    curve: str
+    tau_g1: np.ndarray
+    tau_g2: np.ndarray
+    alpha_tau_g1: np.ndarray
+    beta_tau_g1: np.ndarray
+    beta_g2: np.ndarray
+
+    def view(self):
+        """(SrsViewC, the arrays it points into): hold both until the C call has returned"""
+        keep = [_c(getattr(self, n)) for n in ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2")]
+        t1, t2, a1, b1, b2 = keep
+        return SrsViewC(ptr64(t1.reshape(-1)), len(t1), ptr64(t2.reshape(-1)), len(t2), ptr64(a1.reshape(-1)), ptr64(b1.reshape(-1)),
+                        min(len(a1), len(b1)), ptr64(b2.reshape(-1))), keep
+
+
+def _blank_key(curve: str, qap, matrices: "ConstraintMatrices") -> "ProvingKey":
+    """a zeroed ProvingKey with the arrays a generator fills for these matrices"""
+    L = FQ_LIMBS[curve]
+    ni, nv = matrices.num_instance_variables, matrices.num_instance_variables + matrices.num_witness_variables
+    need, n = matrices.num_constraints + ni, 1
+    while n < need:
+        n <<= 1
+    g1 = lambda k: np.zeros((k, 2 * L), dtype=np.uint64)  # noqa: E731
+    g2 = lambda k: np.zeros((k, 4 * L), dtype=np.uint64)  # noqa: E731
+    return ProvingKey(curve, g1(1), g1(1), g1(1), g2(1), g2(1), g1(nv), g1(nv), g2(nv), g1(qap.h_query_len(n)), g1(nv - ni), g2(1), g1(ni))
+
+
+def _params_view(pk: "ProvingKey") -> ParamsViewC:
+    vp = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+    return ParamsViewC(ptr64(pk.alpha_g1), ptr64(pk.beta_g1), ptr64(pk.delta_g1), ptr64(pk.beta_g2), ptr64(pk.delta_g2), ptr64(pk.gamma_g2),
+                       ptr64(pk.gamma_abc_g1), vp(pk.a_query), vp(pk.b_g1_query), vp(pk.b_g2_query), vp(pk.h_query), vp(pk.l_query), 0)
+
+
+def _points_g2(curve: str, points: np.ndarray) -> bool:
+    """whether an (n, width) array of affine points holds G2 points, by its width"""
+    L = FQ_LIMBS[curve]
+    if points.ndim != 2 or points.shape[1] not in (2 * L, 4 * L):
+        raise ValueError(f"expected (n, {2 * L}) G1 or (n, {4 * L}) G2 affine points")
+    return points.shape[1] == 4 * L
+
+
+def _log2_exact(n: int) -> int:
+    if n < 1 or n & (n - 1):
+        raise ValueError("the number of points must be a power of two")
+    return n.bit_length() - 1
+
+
+def group_ntt_host(curve: str, points: np.ndarray, inverse: bool = False) -> np.ndarray:
+    """g16_host_group_ntt: the transform of Groth16.group_ntt in plain host code (no GPU)"""
+    pts = _c(points)
+    out = np.zeros_like(pts)
+    lb = lib()
+    lb.check(lb.c.g16_host_group_ntt(CURVE_ID[curve], int(_points_g2(curve, pts)), ptr64(pts.reshape(-1)), _log2_exact(len(pts)), int(inverse),
+                                     ptr64(out.reshape(-1))))
+    return out
+
+
+def generate_parameters_from_srs_host(curve: str, matrices: "ConstraintMatrices", srs: "SRS", qap=None) -> "ProvingKey":
+    """g16_host_generate_parameters_srs: Groth16.generate_parameters_from_srs in plain host code (no GPU; for small circuits)"""
+    qap = qap or LibsnarkReduction
+    if srs.curve != curve:
+        raise ValueError("the SRS is for another curve")
+    pk = _blank_key(curve, qap, matrices)
+    out = _params_view(pk)
+    views, keep = _csr_views(matrices)
+    sv, skeep = srs.view()
+    ni = matrices.num_instance_variables
+    lb = lib()
+    lb.check(lb.c.g16_host_generate_parameters_srs(CURVE_ID[curve], views, ni, matrices.num_constraints, ni + matrices.num_witness_variables,
+                                                   qap.QAP_ID, C.byref(sv), C.byref(out)))
+    return pk
 
 
 @dataclass
@@ -535,6 +614,70 @@ class Groth16:
                                                       ptr64(_c(g1_generator).reshape(-1)), ptr64(_c(g2_generator).reshape(-1)),
                                                       C.byref(out)))
         return pk
+
+    # -- setup without the toxic waste: a key from a powers-of-tau SRS, then delta contributions ------------------
+    def srs_from_trapdoor(self, n: int, tau: np.ndarray, alpha: np.ndarray, beta: np.ndarray, g1_generator: np.ndarray,
+                          g2_generator: np.ndarray) -> SRS:
+        """g16_srs_from_trapdoor -- a TEST AND BENCHMARK UTILITY: the SRS a domain of n points needs (2n - 1 powers in G1, n elsewhere)
+        from known secrets, on the GPU.  A real SRS comes from a ceremony whose secrets nobody holds."""
+        L = FQ_LIMBS[self.curve]
+        g1 = lambda k: np.zeros((k, 2 * L), dtype=np.uint64)  # noqa: E731
+        g2 = lambda k: np.zeros((k, 4 * L), dtype=np.uint64)  # noqa: E731
+        srs = SRS(self.curve, g1(2 * n - 1), g2(n), g1(n), g1(n), g2(1))
+        sv, keep = srs.view()
+        lb = self._ctx.lib
+        lb.check(lb.c.g16_srs_from_trapdoor(self._ctx.handle, ptr64(_c(tau).reshape(4)), ptr64(_c(alpha).reshape(4)), ptr64(_c(beta).reshape(4)),
+                                            ptr64(_c(g1_generator).reshape(-1)), ptr64(_c(g2_generator).reshape(-1)), 2 * n - 1, n, C.byref(sv)))
+        return srs
+
+    def generate_parameters_from_srs(self, matrices: ConstraintMatrices, srs: SRS) -> ProvingKey:
+        """g16_generate_parameters_srs: the circuit's key from the SRS by group operations alone, for this object's reduction, with
+        gamma = delta = 1 (gamma_g2 = delta_g2 = G2, delta_g1 = G1).  Nobody's secret goes in: follow it with contribute_delta, once
+        per party.  After ONE contribution the key equals generate_parameters_with_qap(alpha, beta, 1, delta, g1, g2, tau) exactly."""
+        if srs.curve != self.curve:
+            raise ValueError("the SRS is for another curve")
+        pk = _blank_key(self.curve, self.qap, matrices)
+        out = _params_view(pk)
+        views, keep = _csr_views(matrices)
+        sv, skeep = srs.view()
+        ni = matrices.num_instance_variables
+        lb = self._ctx.lib
+        lb.check(lb.c.g16_generate_parameters_srs(self._ctx.handle, views, ni, matrices.num_constraints, ni + matrices.num_witness_variables,
+                                                  self.qap.QAP_ID, C.byref(sv), C.byref(out)))
+        return pk
+
+    def contribute_delta(self, pk: ProvingKey, delta: np.ndarray) -> ProvingKey:
+        """g16_params_apply_delta on a copy of the key: delta_g1, delta_g2 <- delta (.), every l_query / h_query point <- delta^-1 (.).
+        `pk` itself is untouched.  UnexpectedIdentity for delta = 0."""
+        _host_key(pk, "contribute_delta")
+        if pk.curve != self.curve:
+            raise ValueError("proving key is for another curve")
+        cp = lambda a: None if a is None else _c(a).copy()  # noqa: E731
+        new = ProvingKey(pk.curve, *[cp(getattr(pk, n)) for n in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2", "a_query", "b_g1_query",
+                                                                  "b_g2_query", "h_query", "l_query", "gamma_g2", "gamma_abc_g1")])
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+        view = ParamsViewC(None, None, ptr64(new.delta_g1), None, ptr64(new.delta_g2), None, None, None, None, None, vp(new.h_query),
+                           vp(new.l_query), 0)
+        lb = self._ctx.lib
+        lb.check(lb.c.g16_params_apply_delta(self._ctx.handle, ptr64(_c(delta).reshape(4)), C.byref(view), len(new.l_query), len(new.h_query)))
+        return new
+
+    def group_ntt(self, points: np.ndarray, inverse: bool = False) -> np.ndarray:
+        """g16_group_ntt: out[i] = sum_k w^(ik) points[k] over n = 2^k affine points of G1 or G2 (told apart by the row width), w the
+        n-th root of the scalar transforms; inverse: w^-1 and the factor n^-1.  Natural order in and out."""
+        pts = _c(points)
+        out = np.zeros_like(pts)
+        lb = self._ctx.lib
+        lb.check(lb.c.g16_group_ntt(self._ctx.handle, int(_points_g2(self.curve, pts)), ptr64(pts.reshape(-1)), _log2_exact(len(pts)), int(inverse),
+                                    ptr64(out.reshape(-1))))
+        return out
+
+    def srs_timings(self) -> dict:
+        """g16_srs_get_timings: stream-event milliseconds of the last generate_parameters_from_srs (transforms, products, h) and
+        contribute_delta (delta) on this object"""
+        tm = SrsTimingsC()
+        self._ctx.lib.check(self._ctx.lib.c.g16_srs_get_timings(self._ctx.handle, C.byref(tm)))
+        return tm.as_dict()
 
     # -- generator.rs:20-45 (+ lib.rs:63-74 circuit_specific_setup) -------------------------------
     def generate_random_parameters_with_reduction(self, circuit, rng=None) -> ProvingKey:

@@ -422,6 +422,64 @@ int g16_host_qap_evaluations(int curve, const g16_csr_view abc[3], uint64_t num_
                              uint64_t num_variables, const uint64_t t[4], uint64_t* a_out, uint64_t* b_out,
                              uint64_t* c_out, uint64_t zt_out[4]);
 
+/* ---- setup from an SRS: a proving key nobody holds the toxic waste of ----
+ * The calls above take alpha, beta, gamma, delta and t as scalars: fine for benchmarks and parity tests, useless for a deployed
+ * verifier.  Here the key is derived from a phase-1 SRS (powers of tau) by group operations alone, then each party multiplies its
+ * delta in.  With n = the power of two >= num_constraints + num_inputs:
+ *   g16_generate_parameters_srs   the Lagrange-basis points [L_i(tau)] G as inverse n-point transforms over the group, the queries as
+ *                                 sparse products over those points, h_query from tau_g1[n ..] -- gamma = delta = 1;
+ *   g16_params_apply_delta        delta_g1, delta_g2 <- delta (.), every l_query / h_query point <- delta^-1 (.).
+ * A key made this way and given ONE delta equals g16_generate_parameters_qap(alpha, beta, gamma = 1, delta, t = tau) byte for byte.
+ * Not covered: .ptau / .zkey files, checking that an SRS is well formed or a contribution honest, phase 1 itself, gamma != 1. */
+typedef struct {
+    uint64_t* tau_g1;       /* tau^i G1, i < n_tau_g1: G1 affine, Montgomery limbs, host memory (as g16_params_view) */
+    uint64_t n_tau_g1;      /* needs >= 2n - 1                                                                     */
+    uint64_t* tau_g2;       /* tau^i G2, i < n_tau_g2                                                              */
+    uint64_t n_tau_g2;      /* needs >= n                                                                          */
+    uint64_t* alpha_tau_g1; /* alpha tau^i G1, i < n_alpha_beta                                                    */
+    uint64_t* beta_tau_g1;  /* beta tau^i G1, i < n_alpha_beta                                                     */
+    uint64_t n_alpha_beta;  /* needs >= n                                                                          */
+    uint64_t* beta_g2;      /* beta G2, one point                                                                  */
+} g16_srs_view;
+
+/* entries one lane of the sparse products walks at most: longer columns (the constant-one wire) are cut into segments of this
+ * length, one lane each, and the segment sums are folded the same way, level by level */
+#define G16_SRS_SEGMENT_LEN 32
+uint64_t g16_srs_segment_len(void);
+
+/* Stands in for evaluate_all_lagrange_coefficients + the batch multiplications of generator.rs:129-183 and for
+ * instance_map_with_evaluation / h_query_scalars (r1cs_to_qap.rs:120-170, 236-246), with points for scalars.  Arguments and matrix
+ * validation as g16_generate_parameters_qap (a multi-device context runs on its first device).  An SRS longer than needed is
+ * accepted and its prefix used; one too short gives G16_ERR_BAD_LENGTH with g16_last_error naming the array.  `out` as in
+ * g16_generate_parameters_qap, host memory only: G16_PARAMS_DEVICE_PTRS is refused with G16_ERR_BAD_ARG.
+ * out->gamma_g2 = out->delta_g2 = tau_g2[0], out->delta_g1 = tau_g1[0]. */
+int g16_generate_parameters_srs(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints,
+                                uint64_t num_variables, int qap, const g16_srs_view* srs, const g16_params_view* out);
+/* In place over delta_g1, delta_g2 and the first n_l_query / n_h_query points of l_query / h_query (host memory; the other fields
+ * of `inout` are not read).  G16_ERR_UNEXPECTED_IDENTITY for delta == 0 (generator.rs:110-111). */
+int g16_params_apply_delta(g16_ctx* ctx, const uint64_t delta[4], const g16_params_view* inout, uint64_t n_l_query,
+                           uint64_t n_h_query);
+/* The transform of step 1 on its own, as g16_ntt is for the scalar transforms: out[i] = sum_k w^(ik) points[k] over n = 2^log_n
+ * affine points (g2 = 0: G1, 1: G2), or with w^-1 and the factor n^-1 when `inverse`.  Natural order in and out, host memory;
+ * `out` may alias `points`. */
+int g16_group_ntt(g16_ctx* ctx, int g2, const uint64_t* points, int log_n, int inverse, uint64_t* out);
+/* A TEST AND BENCHMARK UTILITY: an SRS from known secrets (a real one comes from a ceremony whose secrets are gone), built with
+ * the fixed-base kernels of g16_generate_parameters.  Fills n_tau_g1 points of out->tau_g1, n_other points of tau_g2,
+ * alpha_tau_g1 and beta_tau_g1, and beta_g2; the counts in `out` say what the buffers hold and must not be smaller. */
+int g16_srs_from_trapdoor(g16_ctx* ctx, const uint64_t tau[4], const uint64_t alpha[4], const uint64_t beta[4],
+                          const uint64_t* g1_generator, const uint64_t* g2_generator, uint64_t n_tau_g1, uint64_t n_other,
+                          const g16_srs_view* out);
+/* stream-event times of the last g16_generate_parameters_srs (transforms, sparse products, h step) and g16_params_apply_delta
+ * (delta step) on this context, in milliseconds */
+typedef struct {
+    double transforms_ms, products_ms, h_ms, delta_ms;
+} g16_srs_timings;
+int g16_srs_get_timings(g16_ctx* ctx, g16_srs_timings* out);
+/* CPU only: the same butterflies and the same sums in plain host code over the same group arithmetic (the `not gpu` tests) */
+int g16_host_group_ntt(int curve, int g2, const uint64_t* points, int log_n, int inverse, uint64_t* out);
+int g16_host_generate_parameters_srs(int curve, const g16_csr_view abc[3], uint64_t num_inputs, uint64_t num_constraints,
+                                     uint64_t num_variables, int qap, const g16_srs_view* srs, const g16_params_view* out);
+
 /* ---- canonical (de)serialisation of points (CPU) ----
  * The element format behind `#[derive(CanonicalSerialize, CanonicalDeserialize)]` on Proof / VerifyingKey / ProvingKey
  * (src/data_structures.rs:8,31,125): BLS12-381 in the zcash / IETF form that ark-bls12-381 uses, BN254 in ark-ec's
