@@ -110,6 +110,19 @@ class SrsTimingsC(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CeremonyInfoC(C.Structure):
+    """g16_ceremony_info"""
+    _fields_ = [("flags", C.c_uint32), ("bad_array", C.c_uint32), ("bad_index", C.c_uint64), ("bad_reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CeremonyTimingsC(C.Structure):
+    """g16_ceremony_timings"""
+    _fields_ = [(n, C.c_double) for n in ("upload_ms", "membership_ms", "sort_ms", "passes_ms", "reductions_ms", "pairings_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class VkViewC(C.Structure):
     _fields_ = [(n, u64p) for n in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")] + [("n_gamma_abc", C.c_uint64)]
 
@@ -202,6 +215,11 @@ EXPORTS = [
     "g16_srs_segment_len", "g16_generate_parameters_srs", "g16_params_apply_delta", "g16_group_ntt", "g16_srs_from_trapdoor",
     "g16_srs_get_timings", "g16_host_group_ntt", "g16_host_generate_parameters_srs",
 ]
+# libg16_ceremony.so, the companion library of the ceremony checks (include/g16_ceremony.h)
+CEREMONY_EXPORTS = [
+    "g16_rlc_sums", "g16_rlc_plan", "g16_srs_check", "g16_params_check_delta", "g16_ceremony_get_timings", "g16_host_rlc_sums", "g16_host_srs_check",
+    "g16_host_params_check_delta",
+]
 
 
 def ptr64(a: Optional[np.ndarray]):
@@ -223,6 +241,7 @@ class Lib:
                 f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  groth16_amd has no CPU fallback.")
         self.path = path
+        self._cer = None
         # One HIP runtime per process: torch wheels bundle their own libamdhip64, and this library links the system one.  Whichever is
         # loaded first serves both (same soname); loaded in the order library -> torch, g16_ctx_create found no device on the GPU box
         # (round 3: `python __graft_entry__.py smoke`, where build() loads the library before smoke() imports torch).  So when torch is
@@ -365,6 +384,26 @@ class Lib:
                                            C.c_int]
         c.g16_dev_msm_sort_lab.argtypes = [C.c_void_p, u64p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(SortLabInfoC), u32p, u32p, u32p,
                                            C.c_uint64, u32p, C.c_uint64]
+
+    @property
+    def cer(self):
+        """libg16_ceremony.so beside the library, loaded on first use (it links against the library and shares its contexts)"""
+        if self._cer is None:
+            path = os.path.join(os.path.dirname(self.path), "libg16_ceremony.so")
+            if not os.path.exists(path):
+                raise ImportError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+            c = C.CDLL(path)
+            c.g16_rlc_sums.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, u64p, u64p, u64p]
+            c.g16_rlc_plan.argtypes = [C.c_uint64, u32p]
+            c.g16_host_rlc_sums.argtypes = [C.c_int, C.c_int, u64p, C.c_uint64, u64p, u64p, u64p]
+            c.g16_srs_check.argtypes = [C.c_void_p, C.POINTER(SrsViewC), u64p, C.c_uint64, C.POINTER(CeremonyInfoC)]
+            c.g16_host_srs_check.argtypes = [C.c_int] + c.g16_srs_check.argtypes[1:]
+            c.g16_params_check_delta.argtypes = [C.c_void_p, C.POINTER(ParamsViewC), C.POINTER(ParamsViewC), C.c_uint64, C.c_uint64, C.c_uint64,
+                                                 C.c_uint64, u64p, C.c_uint64, C.POINTER(CeremonyInfoC)]
+            c.g16_host_params_check_delta.argtypes = [C.c_int] + c.g16_params_check_delta.argtypes[1:]
+            c.g16_ceremony_get_timings.argtypes = [C.c_void_p, C.POINTER(CeremonyTimingsC)]
+            self._cer = c
+        return self._cer
 
     def check(self, status: int, check_result: "Optional[CheckResultC]" = None, pk_bytes_info: "Optional[PkBytesInfoC]" = None):
         """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable; pk_bytes_info: the g16_pk_bytes_info

@@ -15,6 +15,7 @@
 #include "proof_glue.hpp"
 #include "unit_api.hpp"
 #include "srs_setup.hpp"
+#include "ceremony.hpp"
 
 namespace {
 template <class C>
@@ -62,6 +63,21 @@ static void diag_counts(g16_diag* out) {
     // per lane of the pair: six pair products (two sweeps each), two pair squarings (one product each), Y as four sweeps + one reduction
     out->mads_per_add_g2 = 2 * (6 * two_sweeps + 2 * mul + four_sweeps + 3 * fs);
 }
+
+// what libg16_ceremony.so needs of a context (ceremony.hpp): the first device's stream and arena, made current and reset
+namespace g16 {
+int ceremony_enter(g16_ctx* ctx, CeremonyEnv* env, int* curve) {
+    if (!ctx) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty()) return ceremony_enter(ctx->subs[0], env, curve);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    ctx->reset_arena();
+    *env = CeremonyEnv{ctx->stream, &ctx->arena, ctx->ceremony_ms, &ctx->tm.window_bits, &ctx->tm.windows};
+    *curve = ctx->curve;
+    return G16_OK;
+}
+const double* ceremony_stage_ms(const g16_ctx* ctx) { return !ctx ? nullptr : ctx->subs.empty() ? ctx->ceremony_ms : ctx->subs[0]->ceremony_ms; }
+void set_last_error_text(const char* text) { g_last_error = text; }
+}  // namespace g16
 
 // the devices and streams of a context, for the verifier (verify.hip): one entry, or one per device of a multi-device context
 namespace g16 {

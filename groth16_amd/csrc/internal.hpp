@@ -273,6 +273,12 @@ struct ScalarSort {
 };
 template <class C> int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Arena& arena, hipStream_t st, ScalarSort* out,
                                     int shard_n = 1, int shard_r = 0);
+// Short scalars (the 128-bit coefficients of the ceremony library): a per-window plan over 128 scalar bits plus the signed-digit
+// carry, and the per-window sort from its second step on over digit planes the caller made (W planes of n u16 digits of
+// scalar + plan.K, as digits_kernel writes them; device memory) -- histogram, slot layout, scatter
+static constexpr int COEFF128_SWORDS = 7;   // 32-bit words of rho + K a digits kernel stages: six (the sixth is 0 for c <= 16) + a guard
+int coeffs128_plan(uint64_t n, MsmPlan* plan);
+int sort_digit_planes(const MsmPlan& plan, const uint16_t* planes, uint64_t n, Arena& arena, hipStream_t st, ScalarSort* out);
 // The tail of sort_scalars on its own (the pass lab runs it on caller-made counts): counts[M] -> offsets[M + 1] (every count rounded up
 // to a multiple of 2^R), nparts[M] = segments of length lseg each bucket touches, task_off[M + 1] = their exclusive prefix, and the heavy
 // list (heavy[0], zeroed by the caller, counts the buckets with more than HEAVY_PARTS partial sums; their ids follow in any order).

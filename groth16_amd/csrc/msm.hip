@@ -1297,6 +1297,72 @@ int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Aren
     return G16_OK;
 }
 
+#if G16_MSM_PART == 0
+// ---------------------------------------------------------------------------------------------
+// Sorting SHORT scalars (the ceremony library's 128-bit coefficients).  coeffs128_plan: a per-window plan over 128 scalar bits with
+// the "modulus" 2^128, so the smallest W with (2^128 - 1) + K < 2^(cW) -- the carry out of bit 127 and the top window's range -- is
+// the plan's business; about half the windows, digit planes, histograms and per-window reductions of an Fr plan.
+// sort_digit_planes: the per-window path from its second step on, over digit planes the caller made with a kernel of its own
+// (W planes of n u16 digits of scalar + K, as digits_kernel writes them): histogram, slot layout, scatter -- unchanged kernels.
+// ---------------------------------------------------------------------------------------------
+int coeffs128_plan(uint64_t n, MsmPlan* plan) {
+    if (n >= ((uint64_t)1 << 31)) return G16_ERR_BAD_LENGTH;
+    const uint32_t two128[5] = {0u, 0u, 0u, 0u, 1u};   // coefficients are < 2^128
+    G16_TRY(make_msm_plan(n, 128, two128, 5, 0, plan));
+    plan->affine_levels = 0;   // (the G16_MSM_AFFINE_LEVELS experiment pads bucket regions: not carried into this sort)
+    // rho + K < 2^(cW) <= 2^160 must fit COEFF128_SWORDS - 1 words, and the last window's second word must be the guard at most
+    if (plan->merged || plan->c > 16 || plan->c * plan->W > 32 * (COEFF128_SWORDS - 2)) return G16_ERR_INTERNAL;
+    for (int k = COEFF128_SWORDS - 2; k < 10; ++k)
+        if (plan->K[k]) return G16_ERR_INTERNAL;
+    return G16_OK;
+}
+
+int sort_digit_planes(const MsmPlan& plan, const uint16_t* planes, uint64_t n, Arena& arena, hipStream_t st, ScalarSort* out) {
+    if (plan.merged || plan.affine_levels || n >= ((uint64_t)1 << 31)) return G16_ERR_INTERNAL;
+    out->plan = plan;
+    out->n = n;
+    const uint32_t M = plan.buckets();
+    const uint64_t nw = n * (uint64_t)plan.W;
+    if (nw >= ((uint64_t)1 << 32)) return G16_ERR_BAD_LENGTH;
+    uint32_t *counts = nullptr, *nparts = nullptr, *block_sums = nullptr;
+    G16_TRY(arena.alloc_n((size_t)3 * M + 1, &counts));  // counts | scatter cursors | heavy count + list
+    uint32_t* cursor = counts + M;
+    out->heavy = counts + 2 * (size_t)M;
+    G16_TRY(arena.alloc_n((size_t)M + 1, &out->offsets));
+    G16_TRY(arena.alloc_n((size_t)M + 1, &out->task_off));
+    G16_TRY(arena.alloc_n((size_t)M, &nparts));
+    G16_TRY(arena.alloc_n((size_t)(M + SCAN_TILE - 1) / SCAN_TILE, &block_sums));
+    out->max_sorted = nw;
+    G16_TRY(arena.alloc_n(nw ? nw : 1, &out->sorted));
+    out->max_segments = (uint32_t)((nw + plan.Lmax - 1) / plan.Lmax);
+    out->max_tasks = out->max_segments + M;
+    G16_HIP_TRY(hipMemsetAsync(counts, 0, ((size_t)2 * M + 1) * sizeof(uint32_t), st));
+    const size_t lds = (size_t)plan.B * sizeof(uint32_t);
+    static PerDeviceOnce attr_once;
+    std::atomic<bool>& attr_set = attr_once.flag();
+    if (!attr_set) {
+        G16_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bucket_count_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        128 * 1024));
+        G16_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bucket_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        128 * 1024));
+        attr_set = true;
+    }
+    const unsigned nchunks = (unsigned)((n + plan.chunk - 1) / plan.chunk);
+    if (n) {
+        hipLaunchKernelGGL(bucket_count_kernel, dim3(nchunks, plan.W), dim3(SORT_THREADS), lds, st, planes, n, plan.chunk, plan.c, plan.B,
+                           counts);
+        G16_LAUNCH_CHECK();
+    }
+    G16_TRY(msm_slot_layout(counts, M, 0, plan.Lmax, out->offsets, nparts, out->task_off, out->heavy, block_sums, st));
+    if (n) {
+        hipLaunchKernelGGL(bucket_scatter_kernel, dim3(nchunks, plan.W), dim3(SORT_THREADS), lds, st, planes, n, plan.chunk, plan.c, plan.B,
+                           out->offsets, cursor, out->sorted);
+        G16_LAUNCH_CHECK();
+    }
+    return G16_OK;
+}
+#endif
+
 // buffers of one MSM's pass and reductions
 template <class F>
 static int alloc_msm_buffers(const ScalarSort& ss, Arena& arena, MsmBuffers<F>* out) {

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, SrsTimingsC, SrsViewC, TimingsC,
+from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CeremonyInfoC, CeremonyTimingsC, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, SrsTimingsC, SrsViewC, TimingsC,
                       ToxicWasteC, lib, ptr32, ptr64, u64p)
 
 _MODULUS_R = {
@@ -190,6 +190,134 @@ def generate_parameters_from_srs_host(curve: str, matrices: "ConstraintMatrices"
     lb.check(lb.c.g16_host_generate_parameters_srs(CURVE_ID[curve], views, ni, matrices.num_constraints, ni + matrices.num_witness_variables,
                                                    qap.QAP_ID, C.byref(sv), C.byref(out)))
     return pk
+
+
+# ---- ceremony checks (g16_rlc_sums / g16_srs_check / g16_params_check_delta) ----
+SRS_CHECK_FLAGS = {1: "BAD_POINT", 2: "TAU_G1", 4: "TAU_G2", 8: "ALPHA", 16: "BETA", 32: "BETA_G2"}
+KEY_CHECK_FLAGS = {1: "BAD_POINT", 2: "FIXED_PART", 4: "DELTA", 8: "L", 16: "H"}
+SRS_ARRAYS = ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2")
+KEY_POINT_ARRAYS = ("delta_g1", "delta_g2", "l_query", "h_query")
+KEY_FIXED_ARRAYS = ("alpha_g1", "beta_g1", "beta_g2", "gamma_g2", "gamma_abc_g1", "a_query", "b_g1_query", "b_g2_query")
+BAD_POINT_REASONS = {2: "off the curve", 3: "outside the prime-order subgroup", 4: "the identity"}
+
+
+@dataclass
+class CeremonyResult:
+    """g16_ceremony_info: what check_srs / check_delta_contribution found.  Falsy when any flag is set.  `failed`: the names of the
+    set flags; `array` / `index`: the first bad point (BAD_POINT) or the first differing point of the fixed part (FIXED_PART), else
+    None; `reason`: 2 off the curve, 3 outside the subgroup, 4 the identity (BAD_POINT), else 0"""
+
+    flags: int
+    failed: Tuple[str, ...]
+    array: Optional[str]
+    index: Optional[int]
+    reason: int
+
+    @property
+    def ok(self) -> bool:
+        return self.flags == 0
+
+    def __bool__(self) -> bool:
+        return self.flags == 0
+
+    @staticmethod
+    def from_info(info: CeremonyInfoC, names: dict, point_arrays, fixed_arrays=()) -> "CeremonyResult":
+        flags = int(info.flags)
+        failed = tuple(name for bit, name in names.items() if flags & bit)
+        array = index = None
+        if flags & 1:
+            array, index = point_arrays[info.bad_array], int(info.bad_index)
+        elif fixed_arrays and flags & 2:
+            array, index = fixed_arrays[info.bad_array], int(info.bad_index)
+        return CeremonyResult(flags, failed, array, index, int(info.bad_reason))
+
+
+class BadSRS(ValueError):
+    """generate_parameters_from_srs(check=True) met an SRS that fails check_srs; `.result` is the CeremonyResult"""
+
+    def __init__(self, result: CeremonyResult):
+        where = f" ({result.array}[{result.index}] is {BAD_POINT_REASONS.get(result.reason, '?')})" if result.array else ""
+        super().__init__("the SRS is not well formed: " + ", ".join(result.failed) + where)
+        self.result = result
+
+
+def _coeffs128(coeffs) -> Optional[np.ndarray]:
+    """128-bit coefficients as an (n, 2) array of little-endian words: from such an array, or from Python integers"""
+    if coeffs is None:
+        return None
+    if isinstance(coeffs, np.ndarray) and coeffs.dtype == np.uint64:
+        return _c(coeffs).reshape(-1, 2)
+    vals = [int(v) for v in coeffs]
+    if any(v < 0 or v >> 128 for v in vals):
+        raise ValueError("a coefficient does not fit 128 bits")
+    return np.array([[v & 0xFFFFFFFFFFFFFFFF, v >> 64] for v in vals], dtype=np.uint64).reshape(-1, 2)
+
+
+def _coeff_args(coeffs):
+    co = _coeffs128(coeffs)
+    return co, (None if co is None else ptr64(co.reshape(-1))), (0 if co is None else len(co))
+
+
+def _key_for_check(pk: "ProvingKey") -> "ProvingKey":
+    if pk.gamma_g2 is None or pk.gamma_abc_g1 is None:
+        raise ValueError("the key check compares the whole key: gamma_g2 and gamma_abc_g1 are missing")
+    names = ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2", "a_query", "b_g1_query", "b_g2_query", "h_query", "l_query", "gamma_g2",
+             "gamma_abc_g1")
+    return ProvingKey(pk.curve, *[_c(getattr(pk, n)) for n in names])
+
+
+def _delta_check_args(curve: str, before: "ProvingKey", after: "ProvingKey"):
+    if before.curve != curve or after.curve != curve:
+        raise ValueError("proving key is for another curve")
+    b, a = _key_for_check(before), _key_for_check(after)
+    for n in KEY_FIXED_ARRAYS + KEY_POINT_ARRAYS:
+        if getattr(b, n).shape != getattr(a, n).shape:
+            raise ValueError(f"the two keys differ in shape: {n} is {getattr(b, n).shape} before and {getattr(a, n).shape} after")
+    return b, a, (len(b.a_query), len(b.gamma_abc_g1), len(b.l_query), len(b.h_query))
+
+
+def rlc_plan(n_coeffs: int) -> dict:
+    """g16_rlc_plan: how n_coeffs 128-bit coefficients are sorted -- window_bits, windows, chunk (coefficients per histogram / scatter
+    workgroup), segment (entries one bucket-pass lane walks)"""
+    out = np.zeros(4, dtype=np.uint32)
+    lb = lib()
+    lb.check(lb.cer.g16_rlc_plan(n_coeffs, ptr32(out)))
+    return dict(window_bits=int(out[0]), windows=int(out[1]), chunk=int(out[2]), segment=int(out[3]))
+
+
+def rlc_sums_host(curve: str, points: np.ndarray, coeffs) -> Tuple[np.ndarray, np.ndarray]:
+    """g16_host_rlc_sums: Groth16.rlc_sums by plain scalar multiplications and additions (no GPU)"""
+    pts = _c(points)
+    lo, hi = np.zeros(pts.shape[1], dtype=np.uint64), np.zeros(pts.shape[1], dtype=np.uint64)
+    co, cp, _ = _coeff_args(coeffs)
+    if co is not None and len(co) < len(pts) - 1:
+        raise ValueError(f"{len(pts)} points need {len(pts) - 1} coefficients")
+    lb = lib()
+    lb.check(lb.cer.g16_host_rlc_sums(CURVE_ID[curve], int(_points_g2(curve, pts)), ptr64(pts.reshape(-1)), len(pts), cp, ptr64(lo), ptr64(hi)))
+    return lo, hi
+
+
+def check_srs_host(curve: str, srs: "SRS", coeffs=None) -> CeremonyResult:
+    """g16_host_srs_check: Groth16.check_srs in plain host code (no GPU; for small SRS)"""
+    if srs.curve != curve:
+        raise ValueError("the SRS is for another curve")
+    sv, keep = srs.view()
+    co, cp, nco = _coeff_args(coeffs)
+    info = CeremonyInfoC()
+    lb = lib()
+    lb.check(lb.cer.g16_host_srs_check(CURVE_ID[curve], C.byref(sv), cp, nco, C.byref(info)))
+    return CeremonyResult.from_info(info, SRS_CHECK_FLAGS, SRS_ARRAYS)
+
+
+def check_delta_contribution_host(curve: str, before: "ProvingKey", after: "ProvingKey", coeffs=None) -> CeremonyResult:
+    """g16_host_params_check_delta: Groth16.check_delta_contribution in plain host code (no GPU; for small keys)"""
+    b, a, (nv, ni, nl, nh) = _delta_check_args(curve, before, after)
+    co, cp, nco = _coeff_args(coeffs)
+    info = CeremonyInfoC()
+    bv, av = _params_view(b), _params_view(a)
+    lb = lib()
+    lb.check(lb.cer.g16_host_params_check_delta(CURVE_ID[curve], C.byref(bv), C.byref(av), nv, ni, nl, nh, cp, nco, C.byref(info)))
+    return CeremonyResult.from_info(info, KEY_CHECK_FLAGS, KEY_POINT_ARRAYS, KEY_FIXED_ARRAYS)
 
 
 @dataclass
@@ -630,12 +758,17 @@ class Groth16:
                                             ptr64(_c(g1_generator).reshape(-1)), ptr64(_c(g2_generator).reshape(-1)), 2 * n - 1, n, C.byref(sv)))
         return srs
 
-    def generate_parameters_from_srs(self, matrices: ConstraintMatrices, srs: SRS) -> ProvingKey:
+    def generate_parameters_from_srs(self, matrices: ConstraintMatrices, srs: SRS, check: bool = False) -> ProvingKey:
         """g16_generate_parameters_srs: the circuit's key from the SRS by group operations alone, for this object's reduction, with
         gamma = delta = 1 (gamma_g2 = delta_g2 = G2, delta_g1 = G1).  Nobody's secret goes in: follow it with contribute_delta, once
-        per party.  After ONE contribution the key equals generate_parameters_with_qap(alpha, beta, 1, delta, g1, g2, tau) exactly."""
+        per party.  After ONE contribution the key equals generate_parameters_with_qap(alpha, beta, 1, delta, g1, g2, tau) exactly.
+        check=True runs check_srs first and raises BadSRS (carrying the result) before anything is derived."""
         if srs.curve != self.curve:
             raise ValueError("the SRS is for another curve")
+        if check:
+            res = self.check_srs(srs)
+            if not res:
+                raise BadSRS(res)
         pk = _blank_key(self.curve, self.qap, matrices)
         out = _params_view(pk)
         views, keep = _csr_views(matrices)
@@ -671,6 +804,63 @@ class Groth16:
         lb.check(lb.c.g16_group_ntt(self._ctx.handle, int(_points_g2(self.curve, pts)), ptr64(pts.reshape(-1)), _log2_exact(len(pts)), int(inverse),
                                     ptr64(out.reshape(-1))))
         return out
+
+    # -- ceremony checks: is the SRS a sequence of powers, does a key descend from its predecessor ------------------
+    def rlc_sums(self, points: np.ndarray, coeffs) -> Tuple[np.ndarray, np.ndarray]:
+        """g16_rlc_sums: (sum_{i<n-1} rho_i X[i], sum_{i<n-1} rho_i X[i+1]) over n >= 1 affine points of G1 or G2 (told apart by the
+        row width) with 128-bit coefficients rho: an (n - 1, 2) array of little-endian words, Python integers, or None for fresh ones
+        from the operating system.  One sort of the coefficients, both sums in one bucket-pass launch."""
+        pts = _c(points)
+        lo, hi = np.zeros(pts.shape[1], dtype=np.uint64), np.zeros(pts.shape[1], dtype=np.uint64)
+        co, cp, _ = _coeff_args(coeffs)
+        if co is not None and len(co) < len(pts) - 1:
+            raise ValueError(f"{len(pts)} points need {len(pts) - 1} coefficients")
+        lb = self._ctx.lib
+        lb.check(lb.cer.g16_rlc_sums(self._ctx.handle, int(_points_g2(self.curve, pts)), ptr64(pts.reshape(-1)), len(pts), cp, ptr64(lo), ptr64(hi)))
+        return lo, hi
+
+    def check_srs(self, srs: SRS, coeffs=None) -> CeremonyResult:
+        """g16_srs_check: every point in its subgroup and not the identity, every array a sequence of powers of the tau that tau_g2[1]
+        holds, beta_g2 the beta of beta_tau_g1.  The WHOLE arrays are tested.  coeffs: as rlc_sums, at least max(array length) - 1 of
+        them, fixed AFTER the SRS; None draws fresh ones.  A malformed SRS passes any one equation with probability <= 2^-128."""
+        if srs.curve != self.curve:
+            raise ValueError("the SRS is for another curve")
+        sv, keep = srs.view()
+        co, cp, nco = _coeff_args(coeffs)
+        info = CeremonyInfoC()
+        lb = self._ctx.lib
+        lb.check(lb.cer.g16_srs_check(self._ctx.handle, C.byref(sv), cp, nco, C.byref(info)))
+        return CeremonyResult.from_info(info, SRS_CHECK_FLAGS, SRS_ARRAYS)
+
+    def check_delta_contribution(self, before: ProvingKey, after: ProvingKey, coeffs=None) -> CeremonyResult:
+        """g16_params_check_delta: `after` is `before` with more delta multiplied in (any number of contribute_delta calls): the part
+        no contribution touches is byte-equal, delta_g1 / delta_g2 moved by one ratio, and l_query / h_query by its inverse.  Who
+        contributed is not attested -- only that the chain of ratios holds.  ValueError for keys of different shapes."""
+        _host_key(before, "check_delta_contribution")
+        _host_key(after, "check_delta_contribution")
+        b, a, (nv, ni, nl, nh) = _delta_check_args(self.curve, before, after)
+        co, cp, nco = _coeff_args(coeffs)
+        info = CeremonyInfoC()
+        bv, av = _params_view(b), _params_view(a)
+        lb = self._ctx.lib
+        lb.check(lb.cer.g16_params_check_delta(self._ctx.handle, C.byref(bv), C.byref(av), nv, ni, nl, nh, cp, nco, C.byref(info)))
+        return CeremonyResult.from_info(info, KEY_CHECK_FLAGS, KEY_POINT_ARRAYS, KEY_FIXED_ARRAYS)
+
+    def check_parameters(self, matrices: ConstraintMatrices, srs: SRS, pk: ProvingKey, coeffs=None) -> CeremonyResult:
+        """What snarkjs calls `zkey verify`: check_srs, then the delta = 1 key of (matrices, srs) by generate_parameters_from_srs, then
+        check_delta_contribution(derived, pk).  Returns the first result that fails, else the passing key result."""
+        res = self.check_srs(srs, coeffs)
+        if not res:
+            return res
+        derived = self.generate_parameters_from_srs(matrices, srs)
+        return self.check_delta_contribution(derived, pk, coeffs)
+
+    def ceremony_timings(self) -> dict:
+        """g16_ceremony_get_timings: milliseconds of the last rlc_sums / check_srs / check_delta_contribution on this object (upload,
+        membership, sort, passes, reductions by stream events; pairings on the wall clock)"""
+        tm = CeremonyTimingsC()
+        self._ctx.lib.check(self._ctx.lib.cer.g16_ceremony_get_timings(self._ctx.handle, C.byref(tm)))
+        return tm.as_dict()
 
     def srs_timings(self) -> dict:
         """g16_srs_get_timings: stream-event milliseconds of the last generate_parameters_from_srs (transforms, products, h) and
