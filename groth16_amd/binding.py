@@ -123,6 +123,19 @@ class CeremonyTimingsC(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TauContributionC(C.Structure):
+    """g16_tau_contribution"""
+    _fields_ = [(n, u64p) for n in ("tau_g2", "alpha_g2", "beta_g2")]
+
+
+class Phase1TimingsC(C.Structure):
+    """g16_phase1_timings"""
+    _fields_ = [(n, C.c_double) for n in ("upload_ms", "powers_ms", "mul_g1_ms", "mul_g2_ms", "download_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class VkViewC(C.Structure):
     _fields_ = [(n, u64p) for n in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")] + [("n_gamma_abc", C.c_uint64)]
 
@@ -220,6 +233,11 @@ CEREMONY_EXPORTS = [
     "g16_rlc_sums", "g16_rlc_plan", "g16_srs_check", "g16_params_check_delta", "g16_ceremony_get_timings", "g16_host_rlc_sums", "g16_host_srs_check",
     "g16_host_params_check_delta",
 ]
+# libg16_phase1.so, the companion library of phase 1 (include/g16_phase1.h)
+PHASE1_EXPORTS = [
+    "g16_batch_scalar_mul", "g16_host_batch_scalar_mul", "g16_host_batch_scalar_mul_windowed", "g16_srs_contribute", "g16_host_srs_contribute",
+    "g16_phase1_get_timings", "g16_srs_check_contribution", "g16_host_srs_check_contribution",
+]
 
 
 def ptr64(a: Optional[np.ndarray]):
@@ -242,6 +260,7 @@ class Lib:
                 "(hipcc --offload-arch=gfx950).  groth16_amd has no CPU fallback.")
         self.path = path
         self._cer = None
+        self._ph1 = None
         # One HIP runtime per process: torch wheels bundle their own libamdhip64, and this library links the system one.  Whichever is
         # loaded first serves both (same soname); loaded in the order library -> torch, g16_ctx_create found no device on the GPU box
         # (round 3: `python __graft_entry__.py smoke`, where build() loads the library before smoke() imports torch).  So when torch is
@@ -404,6 +423,27 @@ class Lib:
             c.g16_ceremony_get_timings.argtypes = [C.c_void_p, C.POINTER(CeremonyTimingsC)]
             self._cer = c
         return self._cer
+
+    @property
+    def ph1(self):
+        """libg16_phase1.so beside the library, loaded on first use (it links against the library and the ceremony library)"""
+        if self._ph1 is None:
+            path = os.path.join(os.path.dirname(self.path), "libg16_phase1.so")
+            if not os.path.exists(path):
+                raise ImportError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+            c = C.CDLL(path)
+            c.g16_batch_scalar_mul.argtypes = [C.c_void_p, C.c_int, u64p, u64p, C.c_uint64, u64p]
+            c.g16_host_batch_scalar_mul.argtypes = [C.c_int, C.c_int, u64p, u64p, C.c_uint64, u64p]
+            c.g16_host_batch_scalar_mul_windowed.argtypes = c.g16_host_batch_scalar_mul.argtypes
+            c.g16_srs_contribute.argtypes = [C.c_void_p, u64p, u64p, u64p, C.POINTER(SrsViewC), C.POINTER(TauContributionC),
+                                             C.POINTER(Phase1TimingsC)]
+            c.g16_host_srs_contribute.argtypes = [C.c_int] + c.g16_srs_contribute.argtypes[1:]
+            c.g16_phase1_get_timings.argtypes = [C.c_void_p, C.POINTER(Phase1TimingsC)]
+            c.g16_srs_check_contribution.argtypes = [C.c_void_p, C.POINTER(SrsViewC), C.POINTER(SrsViewC), C.POINTER(TauContributionC), u64p,
+                                                     C.c_uint64, C.POINTER(CeremonyInfoC)]
+            c.g16_host_srs_check_contribution.argtypes = [C.c_int] + c.g16_srs_check_contribution.argtypes[1:]
+            self._ph1 = c
+        return self._ph1
 
     def check(self, status: int, check_result: "Optional[CheckResultC]" = None, pk_bytes_info: "Optional[PkBytesInfoC]" = None):
         """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable; pk_bytes_info: the g16_pk_bytes_info

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CeremonyInfoC, CeremonyTimingsC, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, SrsTimingsC, SrsViewC, TimingsC,
+from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CeremonyInfoC, CeremonyTimingsC, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, Phase1TimingsC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, SrsTimingsC, SrsViewC, TauContributionC, TimingsC,
                       ToxicWasteC, lib, ptr32, ptr64, u64p)
 
 _MODULUS_R = {
@@ -318,6 +318,82 @@ def check_delta_contribution_host(curve: str, before: "ProvingKey", after: "Prov
     lb = lib()
     lb.check(lb.cer.g16_host_params_check_delta(CURVE_ID[curve], C.byref(bv), C.byref(av), nv, ni, nl, nh, cp, nco, C.byref(info)))
     return CeremonyResult.from_info(info, KEY_CHECK_FLAGS, KEY_POINT_ARRAYS, KEY_FIXED_ARRAYS)
+
+
+# ---- phase 1 (g16_batch_scalar_mul / g16_srs_contribute / g16_srs_check_contribution; libg16_phase1.so) ----
+TAU_CHECK_FLAGS = {**SRS_CHECK_FLAGS, 64: "SHAPE", 128: "TAU_RATIO", 256: "ALPHA_RATIO", 512: "BETA_RATIO"}
+TAU_ARRAYS = SRS_ARRAYS + ("pub_tau_g2", "pub_alpha_g2", "pub_beta_g2", "before")
+
+
+@dataclass
+class TauContribution:
+    """g16_tau_contribution: a phase-1 contributor's public record -- tau' g2, alpha' g2, beta' g2 with g2 = tau_g2[0] of the SRS the
+    contribution was made to; one G2 affine point each (Montgomery limbs)"""
+
+    curve: str
+    tau_g2: np.ndarray
+    alpha_g2: np.ndarray
+    beta_g2: np.ndarray
+
+    def view(self):
+        """(TauContributionC, the arrays it points into): hold both until the C call has returned"""
+        keep = [_c(getattr(self, n)).reshape(-1) for n in ("tau_g2", "alpha_g2", "beta_g2")]
+        return TauContributionC(*[ptr64(a) for a in keep]), keep
+
+
+def _smul_args(curve: str, points: np.ndarray, scalars: np.ndarray):
+    pts, sc = _c(points), _c(scalars).reshape(-1, 4)
+    g2 = _points_g2(curve, pts)
+    if len(sc) != len(pts):
+        raise ValueError(f"{len(pts)} points need {len(pts)} scalars, got {len(sc)}")
+    return pts, sc, int(g2), np.zeros_like(pts)
+
+
+def batch_scalar_mul_host(curve: str, points: np.ndarray, scalars: np.ndarray, windowed: bool = False) -> np.ndarray:
+    """g16_host_batch_scalar_mul: Groth16.batch_scalar_mul by plain double-and-add on the host (no GPU).  windowed=True runs the
+    device kernel's own task -- signed 4-bit window, lazy 30-bit arithmetic, a lane pair emulated by its halves -- on the host instead"""
+    pts, sc, g2, out = _smul_args(curve, points, scalars)
+    lb = lib()
+    fn = lb.ph1.g16_host_batch_scalar_mul_windowed if windowed else lb.ph1.g16_host_batch_scalar_mul
+    lb.check(fn(CURVE_ID[curve], g2, ptr64(pts.reshape(-1)), ptr64(sc.reshape(-1)), len(pts), ptr64(out.reshape(-1))))
+    return out
+
+
+def _contribution_setup(curve: str, srs: "SRS", tau, alpha, beta):
+    if srs.curve != curve:
+        raise ValueError("the SRS is for another curve")
+    sec = [_rand_fr(curve, nonzero=True) if s is None else _c(s).reshape(4) for s in (tau, alpha, beta)]
+    new = SRS(curve, *[_c(getattr(srs, n)).copy() for n in SRS_ARRAYS])
+    L = FQ_LIMBS[curve]
+    pub = TauContribution(curve, *[np.zeros(4 * L, dtype=np.uint64) for _ in range(3)])
+    return sec, new, pub
+
+
+def contribute_tau_host(curve: str, srs: "SRS", tau=None, alpha=None, beta=None) -> Tuple["SRS", "TauContribution"]:
+    """g16_host_srs_contribute: Groth16.contribute_tau in plain host code (no GPU; for small SRS)"""
+    sec, new, pub = _contribution_setup(curve, srs, tau, alpha, beta)
+    sv, keep = new.view()
+    pv, pkeep = pub.view()
+    lb = lib()
+    lb.check(lb.ph1.g16_host_srs_contribute(CURVE_ID[curve], ptr64(sec[0]), ptr64(sec[1]), ptr64(sec[2]), C.byref(sv), C.byref(pv), None))
+    return new, pub
+
+
+def _tau_check_args(curve: str, before: "SRS", after: "SRS", contribution: "TauContribution"):
+    if before.curve != curve or after.curve != curve or contribution.curve != curve:
+        raise ValueError("the SRS or the contribution is for another curve")
+    (bv, bkeep), (av, akeep), (pv, pkeep) = before.view(), after.view(), contribution.view()
+    return bv, av, pv, (bkeep, akeep, pkeep)
+
+
+def check_tau_contribution_host(curve: str, before: "SRS", after: "SRS", contribution: "TauContribution", coeffs=None) -> CeremonyResult:
+    """g16_host_srs_check_contribution: Groth16.check_tau_contribution in plain host code (no GPU; for small SRS)"""
+    bv, av, pv, keep = _tau_check_args(curve, before, after, contribution)
+    co, cp, nco = _coeff_args(coeffs)
+    info = CeremonyInfoC()
+    lb = lib()
+    lb.check(lb.ph1.g16_host_srs_check_contribution(CURVE_ID[curve], C.byref(bv), C.byref(av), C.byref(pv), cp, nco, C.byref(info)))
+    return CeremonyResult.from_info(info, TAU_CHECK_FLAGS, TAU_ARRAYS)
 
 
 @dataclass
@@ -860,6 +936,47 @@ class Groth16:
         membership, sort, passes, reductions by stream events; pairings on the wall clock)"""
         tm = CeremonyTimingsC()
         self._ctx.lib.check(self._ctx.lib.cer.g16_ceremony_get_timings(self._ctx.handle, C.byref(tm)))
+        return tm.as_dict()
+
+    # -- phase 1: one scalar per point, a contribution to the powers of tau, its check ------------------------------
+    def batch_scalar_mul(self, points: np.ndarray, scalars: np.ndarray) -> np.ndarray:
+        """g16_batch_scalar_mul: out[i] = scalars[i] * points[i] over n affine points of G1 or G2 (told apart by the row width) and n
+        scalars (Fr, Montgomery limbs).  Exact for every scalar and every point with coordinates below the modulus, in the subgroup
+        or not; no membership test is made."""
+        pts, sc, g2, out = _smul_args(self.curve, points, scalars)
+        lb = self._ctx.lib
+        lb.check(lb.ph1.g16_batch_scalar_mul(self._ctx.handle, g2, ptr64(pts.reshape(-1)), ptr64(sc.reshape(-1)), len(pts), ptr64(out.reshape(-1))))
+        return out
+
+    def contribute_tau(self, srs: SRS, tau=None, alpha=None, beta=None) -> Tuple[SRS, "TauContribution"]:
+        """g16_srs_contribute on a copy of the SRS: tau_g1[i], tau_g2[i] <- tau^i (.), alpha_tau_g1[i] <- alpha tau^i (.),
+        beta_tau_g1[i] <- beta tau^i (.), beta_g2 <- beta (.); the contributor's public record comes back beside the new SRS.  `srs`
+        itself is untouched.  A secret left None is drawn from the operating system, non-zero, and is not returned.
+        UnexpectedIdentity for a zero secret."""
+        sec, new, pub = _contribution_setup(self.curve, srs, tau, alpha, beta)
+        sv, keep = new.view()
+        pv, pkeep = pub.view()
+        lb = self._ctx.lib
+        lb.check(lb.ph1.g16_srs_contribute(self._ctx.handle, ptr64(sec[0]), ptr64(sec[1]), ptr64(sec[2]), C.byref(sv), C.byref(pv), None))
+        return new, pub
+
+    def check_tau_contribution(self, before: SRS, after: SRS, contribution: "TauContribution", coeffs=None) -> CeremonyResult:
+        """g16_srs_check_contribution: `after` passes check_srs and descends from `before` by the contribution whose G2 images are
+        `contribution` -- the generators and lengths unchanged (SHAPE), tau_g1[1], alpha_tau_g1[0] and beta_tau_g1[0] moved by the
+        ratios the record holds (TAU_RATIO, ALPHA_RATIO, BETA_RATIO).  `before` is read at five points only.  Who contributed is not
+        attested.  coeffs: as check_srs."""
+        bv, av, pv, keep = _tau_check_args(self.curve, before, after, contribution)
+        co, cp, nco = _coeff_args(coeffs)
+        info = CeremonyInfoC()
+        lb = self._ctx.lib
+        lb.check(lb.ph1.g16_srs_check_contribution(self._ctx.handle, C.byref(bv), C.byref(av), C.byref(pv), cp, nco, C.byref(info)))
+        return CeremonyResult.from_info(info, TAU_CHECK_FLAGS, TAU_ARRAYS)
+
+    def phase1_timings(self) -> dict:
+        """g16_phase1_get_timings: stream-event milliseconds of the last batch_scalar_mul / contribute_tau on this object (upload,
+        powers, multiplications G1, multiplications G2, download), summed over the chunks"""
+        tm = Phase1TimingsC()
+        self._ctx.lib.check(self._ctx.lib.ph1.g16_phase1_get_timings(self._ctx.handle, C.byref(tm)))
         return tm.as_dict()
 
     def srs_timings(self) -> dict:

@@ -27,7 +27,8 @@ extern "C" {
  * the same uploaded copies (flag BAD_POINT) -- a malformed input passes any ONE equation with probability <= 2^-128 over the
  * coefficients.  Points: affine Montgomery limbs, host memory, as g16_srs_view / g16_params_view.  A multi-device context runs on
  * its first device.  NOT attested: who contributed (no proofs of knowledge, no transcript -- only that the chain of ratios holds),
- * phase-1 contributions, .ptau / .zkey files, gamma != 1. */
+ * .ptau / .zkey files, gamma != 1.  Phase-1 contributions are made and checked by libg16_phase1.so (g16_phase1.h), on top of
+ * g16_srs_check. */
 #define G16_SRS_BAD_POINT 1u /* exclusive: no pairing is computed, no other flag reported */
 #define G16_SRS_TAU_G1 2u    /* e(lo(tau_g1), tau_g2[1]) != e(hi(tau_g1), g2),  g2 = tau_g2[0]             */
 #define G16_SRS_TAU_G2 4u    /* e(tau_g1[1], lo(tau_g2)) != e(g1, hi(tau_g2)),  g1 = tau_g1[0]             */

@@ -431,7 +431,8 @@ int g16_host_qap_evaluations(int curve, const g16_csr_view abc[3], uint64_t num_
  *   g16_params_apply_delta        delta_g1, delta_g2 <- delta (.), every l_query / h_query point <- delta^-1 (.).
  * A key made this way and given ONE delta equals g16_generate_parameters_qap(alpha, beta, gamma = 1, delta, t = tau) byte for byte.
  * Whether an SRS is well formed and a contribution honest is tested by the companion library libg16_ceremony.so (g16_ceremony.h).
- * Not covered: .ptau / .zkey files, phase 1 itself, gamma != 1. */
+ * Phase 1 itself -- contributing to a powers-of-tau SRS and checking such a contribution -- is libg16_phase1.so (g16_phase1.h).
+ * Not covered: .ptau / .zkey files, proofs of knowledge and the transcript, gamma != 1. */
 typedef struct {
     uint64_t* tau_g1;       /* tau^i G1, i < n_tau_g1: G1 affine, Montgomery limbs, host memory (as g16_params_view) */
     uint64_t n_tau_g1;      /* needs >= 2n - 1                                                                     */
