@@ -136,6 +136,20 @@ class Phase1TimingsC(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class KeyFoldC(C.Structure):
+    """g16_key_fold"""
+    _fields_ = [(n, u64p) for n in ("a", "b_g1", "b_g2", "gamma_abc", "l", "h")]
+
+
+class KeycheckTimingsC(C.Structure):
+    """g16_keycheck_timings"""
+    _fields_ = [(n, C.c_double) for n in ("upload_ms", "membership_ms", "rows_ms", "transforms_ms", "sorts_ms", "passes_ms", "reductions_ms",
+                                          "pairings_ms", "window_bits", "windows")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class VkViewC(C.Structure):
     _fields_ = [(n, u64p) for n in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")] + [("n_gamma_abc", C.c_uint64)]
 
@@ -238,6 +252,11 @@ PHASE1_EXPORTS = [
     "g16_batch_scalar_mul", "g16_host_batch_scalar_mul", "g16_host_batch_scalar_mul_windowed", "g16_srs_contribute", "g16_host_srs_contribute",
     "g16_phase1_get_timings", "g16_srs_check_contribution", "g16_host_srs_check_contribution",
 ]
+# libg16_keycheck.so, the companion library of the key check without the derivation (include/g16_keycheck.h)
+KEYCHECK_EXPORTS = [
+    "g16_params_check_derivation", "g16_key_fold_from_srs", "g16_keycheck_get_timings", "g16_host_params_check_derivation",
+    "g16_host_key_fold_from_srs",
+]
 
 
 def ptr64(a: Optional[np.ndarray]):
@@ -261,6 +280,7 @@ class Lib:
         self.path = path
         self._cer = None
         self._ph1 = None
+        self._kc = None
         # One HIP runtime per process: torch wheels bundle their own libamdhip64, and this library links the system one.  Whichever is
         # loaded first serves both (same soname); loaded in the order library -> torch, g16_ctx_create found no device on the GPU box
         # (round 3: `python __graft_entry__.py smoke`, where build() loads the library before smoke() imports torch).  So when torch is
@@ -444,6 +464,23 @@ class Lib:
             c.g16_host_srs_check_contribution.argtypes = [C.c_int] + c.g16_srs_check_contribution.argtypes[1:]
             self._ph1 = c
         return self._ph1
+
+    @property
+    def kc(self):
+        """libg16_keycheck.so beside the library, loaded on first use (it links against the library and its two other companions)"""
+        if self._kc is None:
+            path = os.path.join(os.path.dirname(self.path), "libg16_keycheck.so")
+            if not os.path.exists(path):
+                raise ImportError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+            c = C.CDLL(path)
+            shape = [C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(SrsViewC)]
+            c.g16_params_check_derivation.argtypes = [C.c_void_p] + shape + [C.POINTER(ParamsViewC), u64p, C.c_uint64, C.POINTER(CeremonyInfoC)]
+            c.g16_host_params_check_derivation.argtypes = [C.c_int] + c.g16_params_check_derivation.argtypes[1:]
+            c.g16_key_fold_from_srs.argtypes = [C.c_void_p] + shape + [u64p, C.c_uint64, C.POINTER(KeyFoldC)]
+            c.g16_host_key_fold_from_srs.argtypes = [C.c_int] + c.g16_key_fold_from_srs.argtypes[1:]
+            c.g16_keycheck_get_timings.argtypes = [C.c_void_p, C.POINTER(KeycheckTimingsC)]
+            self._kc = c
+        return self._kc
 
     def check(self, status: int, check_result: "Optional[CheckResultC]" = None, pk_bytes_info: "Optional[PkBytesInfoC]" = None):
         """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable; pk_bytes_info: the g16_pk_bytes_info

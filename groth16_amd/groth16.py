@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CeremonyInfoC, CeremonyTimingsC, CheckResultC, CsrViewC, G16Error, ParamsViewC, PartialC, Phase1TimingsC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, SrsTimingsC, SrsViewC, TauContributionC, TimingsC,
+from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CeremonyInfoC, CeremonyTimingsC, CheckResultC, CsrViewC, G16Error, KeyFoldC, KeycheckTimingsC, ParamsViewC, PartialC, Phase1TimingsC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, SrsTimingsC, SrsViewC, TauContributionC, TimingsC,
                       ToxicWasteC, lib, ptr32, ptr64, u64p)
 
 _MODULUS_R = {
@@ -394,6 +394,73 @@ def check_tau_contribution_host(curve: str, before: "SRS", after: "SRS", contrib
     lb = lib()
     lb.check(lb.ph1.g16_host_srs_check_contribution(CURVE_ID[curve], C.byref(bv), C.byref(av), C.byref(pv), cp, nco, C.byref(info)))
     return CeremonyResult.from_info(info, TAU_CHECK_FLAGS, TAU_ARRAYS)
+
+
+# ---- the key check without the derivation (g16_params_check_derivation / g16_key_fold_from_srs; libg16_keycheck.so) ----
+KEY_DERIVATION_FLAGS = {1: "BAD_POINT", 2: "FIXED", 4: "DELTA", 8: "A", 16: "B_G1", 32: "B_G2", 64: "GAMMA_ABC", 128: "L", 256: "H"}
+KEY_DERIVATION_ARRAYS = ("a_query", "b_g1_query", "b_g2_query", "gamma_abc_g1", "l_query", "h_query", "delta_g1", "delta_g2")
+KEY_DERIVATION_FIXED = ("alpha_g1", "beta_g1", "beta_g2", "gamma_g2")
+KEY_FOLD_POINTS = ("a", "b_g1", "b_g2", "gamma_abc", "l", "h")
+
+
+def _derivation_shape(curve: str, matrices: "ConstraintMatrices", srs: "SRS"):
+    if srs.curve != curve:
+        raise ValueError("the SRS is for another curve")
+    ni = matrices.num_instance_variables
+    return ni, matrices.num_constraints, ni + matrices.num_witness_variables
+
+
+def _derivation_key(curve: str, qap, matrices: "ConstraintMatrices", pk: "ProvingKey") -> "ProvingKey":
+    """the key as contiguous arrays, its shape held against the circuit's (ValueError: a key of another shape is not a flag)"""
+    if pk.curve != curve:
+        raise ValueError("proving key is for another curve")
+    key = _key_for_check(pk)
+    blank = _blank_key(curve, qap, matrices)
+    for n in KEY_DERIVATION_ARRAYS + KEY_DERIVATION_FIXED:
+        if getattr(key, n).size != getattr(blank, n).size:   # (a single point may come flat or as one row)
+            raise ValueError(f"the key does not have the circuit's shape: {n} is {getattr(key, n).shape}, the circuit and this reduction "
+                             f"need {getattr(blank, n).shape}")
+    return key
+
+
+def _fold_out(curve: str):
+    L = FQ_LIMBS[curve]
+    pts = {n: np.zeros(4 * L if n == "b_g2" else 2 * L, dtype=np.uint64) for n in KEY_FOLD_POINTS}
+    return pts, KeyFoldC(*[ptr64(pts[n]) for n in KEY_FOLD_POINTS])
+
+
+def _fold_coeffs(coeffs):
+    if coeffs is None:
+        raise ValueError("fold_key_from_srs is the deterministic unit: it needs explicit coefficients")
+    return _coeff_args(coeffs)
+
+
+def check_key_derivation_host(curve: str, matrices: "ConstraintMatrices", srs: "SRS", pk: "ProvingKey", coeffs=None, qap=None) -> CeremonyResult:
+    """g16_host_params_check_derivation: Groth16.check_key_derivation in plain host code (no GPU; for small circuits)"""
+    qap = qap or LibsnarkReduction
+    ni, nc, nv = _derivation_shape(curve, matrices, srs)
+    key = _derivation_key(curve, qap, matrices, pk)
+    views, keep = _csr_views(matrices)
+    sv, skeep = srs.view()
+    kv = _params_view(key)
+    co, cp, nco = _coeff_args(coeffs)
+    info = CeremonyInfoC()
+    lb = lib()
+    lb.check(lb.kc.g16_host_params_check_derivation(CURVE_ID[curve], views, ni, nc, nv, qap.QAP_ID, C.byref(sv), C.byref(kv), cp, nco, C.byref(info)))
+    return CeremonyResult.from_info(info, KEY_DERIVATION_FLAGS, KEY_DERIVATION_ARRAYS, KEY_DERIVATION_FIXED)
+
+
+def fold_key_from_srs_host(curve: str, matrices: "ConstraintMatrices", srs: "SRS", coeffs, qap=None) -> Dict[str, np.ndarray]:
+    """g16_host_key_fold_from_srs: Groth16.fold_key_from_srs in plain host code (no GPU; for small circuits)"""
+    qap = qap or LibsnarkReduction
+    ni, nc, nv = _derivation_shape(curve, matrices, srs)
+    views, keep = _csr_views(matrices)
+    sv, skeep = srs.view()
+    co, cp, nco = _fold_coeffs(coeffs)
+    pts, out = _fold_out(curve)
+    lb = lib()
+    lb.check(lb.kc.g16_host_key_fold_from_srs(CURVE_ID[curve], views, ni, nc, nv, qap.QAP_ID, C.byref(sv), cp, nco, C.byref(out)))
+    return pts
 
 
 @dataclass
@@ -922,14 +989,61 @@ class Groth16:
         lb.check(lb.cer.g16_params_check_delta(self._ctx.handle, C.byref(bv), C.byref(av), nv, ni, nl, nh, cp, nco, C.byref(info)))
         return CeremonyResult.from_info(info, KEY_CHECK_FLAGS, KEY_POINT_ARRAYS, KEY_FIXED_ARRAYS)
 
-    def check_parameters(self, matrices: ConstraintMatrices, srs: SRS, pk: ProvingKey, coeffs=None) -> CeremonyResult:
+    def check_parameters(self, matrices: ConstraintMatrices, srs: SRS, pk: ProvingKey, coeffs=None, derive: bool = True) -> CeremonyResult:
         """What snarkjs calls `zkey verify`: check_srs, then the delta = 1 key of (matrices, srs) by generate_parameters_from_srs, then
-        check_delta_contribution(derived, pk).  Returns the first result that fails, else the passing key result."""
+        check_delta_contribution(derived, pk).  Returns the first result that fails, else the passing key result.
+        derive=False decides the same question without deriving the key: check_srs, then check_key_derivation (whose flags and
+        arrays the result then carries)."""
         res = self.check_srs(srs, coeffs)
         if not res:
             return res
+        if not derive:
+            return self.check_key_derivation(matrices, srs, pk, coeffs)
         derived = self.generate_parameters_from_srs(matrices, srs)
         return self.check_delta_contribution(derived, pk, coeffs)
+
+    # -- the key check without the derivation: the SRS folded under the circuit's matrices ----------------------------
+    def check_key_derivation(self, matrices: ConstraintMatrices, srs: SRS, pk: ProvingKey, coeffs=None) -> CeremonyResult:
+        """g16_params_check_derivation: `pk` is the key of (matrices, srs) for this object's reduction, after any number of delta
+        contributions -- decided by random linear combinations pushed through the matrices and the scalar transform onto the SRS
+        (a sparse mat-vec, seven scalar transforms, MSMs over the raw SRS points: no transform over the group).  PRECONDITION: the
+        SRS passes check_srs (check_parameters(derive=False) runs it first).  coeffs: 128-bit coefficients as in check_srs, at
+        least max(variables, len(h_query)) of them, fixed AFTER the key; None draws fresh ones.  With the key's points in their
+        subgroups (BAD_POINT otherwise) a key that differs from the true one in any point passes with probability <= 2^-128.
+        ValueError for a key of another shape; not attested: who contributed, gamma != 1."""
+        _host_key(pk, "check_key_derivation")
+        ni, nc, nv = _derivation_shape(self.curve, matrices, srs)
+        key = _derivation_key(self.curve, self.qap, matrices, pk)
+        views, keep = _csr_views(matrices)
+        sv, skeep = srs.view()
+        kv = _params_view(key)
+        co, cp, nco = _coeff_args(coeffs)
+        info = CeremonyInfoC()
+        lb = self._ctx.lib
+        lb.check(lb.kc.g16_params_check_derivation(self._ctx.handle, views, ni, nc, nv, self.qap.QAP_ID, C.byref(sv), C.byref(kv), cp, nco,
+                                                   C.byref(info)))
+        return CeremonyResult.from_info(info, KEY_DERIVATION_FLAGS, KEY_DERIVATION_ARRAYS, KEY_DERIVATION_FIXED)
+
+    def fold_key_from_srs(self, matrices: ConstraintMatrices, srs: SRS, coeffs) -> Dict[str, np.ndarray]:
+        """g16_key_fold_from_srs: the SRS side of check_key_derivation's equations A, B_G1, B_G2, GAMMA_ABC, L, H before any pairing --
+        a dict of six affine points (keys a, b_g1, b_g2, gamma_abc, l, h).  For the true key these are sum rho_j (query point j)
+        with delta = 1.  Deterministic: coeffs are required."""
+        ni, nc, nv = _derivation_shape(self.curve, matrices, srs)
+        views, keep = _csr_views(matrices)
+        sv, skeep = srs.view()
+        co, cp, nco = _fold_coeffs(coeffs)
+        pts, out = _fold_out(self.curve)
+        lb = self._ctx.lib
+        lb.check(lb.kc.g16_key_fold_from_srs(self._ctx.handle, views, ni, nc, nv, self.qap.QAP_ID, C.byref(sv), cp, nco, C.byref(out)))
+        return pts
+
+    def keycheck_timings(self) -> dict:
+        """g16_keycheck_get_timings: milliseconds of the last check_key_derivation / fold_key_from_srs on this object (upload,
+        membership, rows, transforms, sorts, passes, reductions by stream events; pairings on the wall clock) and the plan of the
+        full-size scalar sorts over the raw SRS bases (window_bits, windows)"""
+        tm = KeycheckTimingsC()
+        self._ctx.lib.check(self._ctx.lib.kc.g16_keycheck_get_timings(self._ctx.handle, C.byref(tm)))
+        return tm.as_dict()
 
     def ceremony_timings(self) -> dict:
         """g16_ceremony_get_timings: milliseconds of the last rlc_sums / check_srs / check_delta_contribution on this object (upload,
