@@ -233,6 +233,7 @@ EXPORTS = [
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
     "g16_dev_fp30_op", "g16_host_fp30_op", "g16_dev_msm_reduce_lab", "g16_dev_window_table_lab", "g16_dev_pairing_op", "g16_host_pairing_op",
     "g16_dev_msm_pass_lab", "g16_dev_msm_sort_lab",
+    "g16_dev_pvk_tables", "g16_dev_prepare_inputs", "g16_host_pvk_tables", "g16_host_prepare_inputs",
     "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
     "g16_decompress_points", "g16_decompress_proofs", "g16_host_decompress_points", "g16_verify_aggregate_bytes",
     "g16_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed", "g16_host_verify_aggregate_mixed_gt",
@@ -423,6 +424,10 @@ class Lib:
                                            C.c_int]
         c.g16_dev_msm_sort_lab.argtypes = [C.c_void_p, u64p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(SortLabInfoC), u32p, u32p, u32p,
                                            C.c_uint64, u32p, C.c_uint64]
+        c.g16_dev_pvk_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_int, u64p]
+        c.g16_dev_prepare_inputs.argtypes = [C.c_void_p, C.c_void_p, u64p, C.c_uint64, C.c_uint64, u64p]
+        c.g16_host_pvk_tables.argtypes = [C.c_int, C.POINTER(VkViewC), u64p]
+        c.g16_host_prepare_inputs.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, C.c_uint64, C.c_uint64, u64p]
 
     @property
     def cer(self):
@@ -589,6 +594,49 @@ def window_table_lab(lb: "Lib", ctx, g2: bool, points: np.ndarray, c: int, W: in
     assert points.ndim == 2
     out = np.full((max(W, 0), points.shape[0], points.shape[1]), fill, dtype=np.uint64)
     status = lb.c.g16_dev_window_table_lab(ctx, int(g2), ptr64(points), points.shape[0], c, W, ptr64(out))
+    return status, out
+
+
+PVK_WINDOWS, PVK_DIGITS = 64, 15   # a prepared key's window tables: [base][window][digit - 1]
+
+
+def _input_rows(inputs, num_public: int) -> np.ndarray:
+    """n rows of num_public Fr (Montgomery limbs) as uint64 [n, num_public, 4]"""
+    x = np.ascontiguousarray(inputs, dtype=np.uint64)
+    assert x.ndim == 3 and x.shape[1:] == (num_public, 4), "expected uint64 [n, num_public, 4]"
+    return x
+
+
+def dev_pvk_tables(lb: "Lib", ctx, pvk, num_public: int, fq_limbs: int, device_index: int = 0, fill: int = 0xDEADBEEFDEADBEEF):
+    """g16_dev_pvk_tables (test hook): the resident window tables of a prepared key's copy `device_index`.
+    ctx, pvk: the raw handles.  Returns (status, uint64 [num_public, 64, 15, 2 * fq_limbs]: entry [j, w, d - 1] is
+    d * 16^w * gamma_abc_g1[j + 1] in the ABI's affine form); the buffer is pre-filled with `fill`."""
+    out = np.full((num_public, PVK_WINDOWS, PVK_DIGITS, 2 * fq_limbs), fill, dtype=np.uint64)
+    status = lb.c.g16_dev_pvk_tables(ctx, pvk, device_index, ptr64(out))
+    return status, out
+
+
+def host_pvk_tables(lb: "Lib", curve_id: int, vk_view, num_public: int, fq_limbs: int, fill: int = 0xDEADBEEFDEADBEEF):
+    """g16_host_pvk_tables (test hook): the same tables built on the CPU by the table kernel's own function.  vk_view: a VkViewC."""
+    out = np.full((num_public, PVK_WINDOWS, PVK_DIGITS, 2 * fq_limbs), fill, dtype=np.uint64)
+    status = lb.c.g16_host_pvk_tables(curve_id, C.byref(vk_view), ptr64(out))
+    return status, out
+
+
+def dev_prepare_inputs(lb: "Lib", ctx, pvk, inputs, num_public: int, fq_limbs: int, fill: int = 0xDEADBEEFDEADBEEF):
+    """g16_dev_prepare_inputs (test hook): one GPU lane per row of `inputs` (uint64 [n, num_public, 4]) through prepare_inputs_tab on
+    the key's resident tables.  Returns (status, uint64 [n, 2 * fq_limbs] affine points, pre-filled with `fill`)."""
+    x = _input_rows(inputs, num_public)
+    out = np.full((x.shape[0], 2 * fq_limbs), fill, dtype=np.uint64)
+    status = lb.c.g16_dev_prepare_inputs(ctx, pvk, ptr64(x) if x.size else None, num_public, x.shape[0], ptr64(out))
+    return status, out
+
+
+def host_prepare_inputs(lb: "Lib", curve_id: int, vk_view, inputs, num_public: int, fq_limbs: int, fill: int = 0xDEADBEEFDEADBEEF):
+    """g16_host_prepare_inputs (test hook): the same on the CPU, tables built by the table kernel's own function"""
+    x = _input_rows(inputs, num_public)
+    out = np.full((x.shape[0], 2 * fq_limbs), fill, dtype=np.uint64)
+    status = lb.c.g16_host_prepare_inputs(curve_id, C.byref(vk_view), ptr64(x) if x.size else None, num_public, x.shape[0], ptr64(out))
     return status, out
 
 

@@ -47,19 +47,11 @@ __global__ void pairing_product_kernel(const typename C::G1A* g1s, const typenam
 // lane t < nb * WINDOWS * DIGITS: entry (j, w, d) = d * 2^(4w) * bases[j]
 template <class C>
 __global__ void verify_window_table_kernel(const typename C::G1A* bases, uint64_t nb, Aff1<C>* tables) {
-    typedef Pairing<C> PP;
-    typedef typename PP::F F;
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nb * WINDOWS * DIGITS) return;
     const uint64_t j = t / (WINDOWS * DIGITS);
     const int w = (int)(t / DIGITS % WINDOWS), d = (int)(t % DIGITS) + 1;
-    const typename C::G1A b = bases[j];
-    if (b.is_identity()) { tables[t] = Aff1<C>::identity(); return; }
-    const typename PP::A1 p = PP::g1_in(b);
-    uint32_t k[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    k[w >> 3] = (uint32_t)d << (4 * (w & 7));
-    const XYZZ<F> r = XYZZ<F>::from_affine(Aff1<C>{p.x, p.y}).mul_bits(k, 4 * w + 4);
-    tables[t] = r.to_affine();
+    tables[t] = window_table_entry<C>(bases[j], w, d);
 }
 
 // one lane per proof.  prepared: IC per proof given (n G1 affine), else computed from the public inputs

@@ -131,6 +131,20 @@ struct PvkDev {
     }
 };
 
+// one table entry: d * 2^(4w) * b for 0 <= w < WINDOWS, 1 <= d <= DIGITS (the identity for the identity).  The text of
+// verify_window_table_kernel and of the host builder behind g16_host_pvk_tables / g16_host_prepare_inputs (preplab.hip).
+template <class C>
+G16_HD Aff1<C> window_table_entry(const typename C::G1A& b, int w, int d) {
+    typedef Pairing<C> PP;
+    typedef typename PP::F F;
+    if (b.is_identity()) return Aff1<C>::identity();
+    const typename PP::A1 p = PP::g1_in(b);
+    uint32_t k[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    k[w >> 3] = (uint32_t)d << (4 * (w & 7));
+    const XYZZ<F> r = XYZZ<F>::from_affine(Aff1<C>{p.x, p.y}).mul_bits(k, 4 * w + 4);
+    return r.to_affine();
+}
+
 // acc += x gamma_abc[j + 1] from a key's window tables; x in Montgomery form
 template <class C>
 G16_HD void tab_accumulate(XYZZ<typename Pairing<C>::F>& acc, const Aff1<C>* tables, uint64_t j, const typename C::Fr& x) {

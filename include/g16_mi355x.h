@@ -676,7 +676,10 @@ int g16_pvk_alpha_beta(const g16_pvk* pvk, uint64_t* out_fq12);
 /* proofs: n x (A | B | C) affine; public_inputs: n x num_public Fr.  verdicts[i]: 1 accept, 0 the pairing equation fails,
  * 2 A, B or C is not on its curve (a superset of the reference, whose point types cannot hold such points).
  * G16_ERR_MALFORMED_VK fails the whole call when num_public + 1 != n_gamma_abc.  A multi-device ctx cuts the batch into one
- * chunk per device; verdicts stay in input order. */
+ * chunk per device; verdicts stay in input order.
+ * An input is four words of Montgomery limbs and is NOT compared with r: every verifier call -- this one, the prepared-input lab,
+ * the three aggregate calls, the mixed call and the g16_host_ forms -- reads words of any value m < 2^256 as the field element
+ * m R^-1 mod r, so x and x + r are the same input (a caller that keys anything on the raw words canonicalises them). */
 int g16_verify_batch(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* proofs, uint64_t n, const uint64_t* public_inputs,
                      uint64_t num_public, uint8_t* verdicts);
 /* the same with IC = prepare_inputs(..) given per proof (n G1 affine) */
@@ -738,6 +741,22 @@ int g16_host_verify_aggregate_mixed(int curve, const g16_vk_view* vks, uint64_t 
 int g16_host_verify_aggregate_mixed_gt(int curve, const g16_vk_view* vks, uint64_t n_keys, const uint32_t* key_of, const uint64_t* proofs,
                                        uint64_t n, const uint64_t* public_inputs, uint64_t n_public_total, const uint64_t* coeffs,
                                        uint64_t* lhs_fq12, uint64_t* rhs_fq12);
+
+/* ---- the input-preparation lab (test hooks): the verifier's window tables and prepared input in place ----
+ * Every verifier path first forms IC = gamma_abc_g1[0] + sum_j x_j gamma_abc_g1[j + 1] from a prepared key's window tables,
+ * tables[j][w][d - 1] = d * 16^w * gamma_abc_g1[j + 1] for 64 windows w and the digits d = 1 .. 15.  These calls show both.  Points
+ * leave in the ABI's G1 affine form (Montgomery limbs, the identity all-zero).
+ * g16_dev_pvk_tables copies the tables of the key's copy number device_index (0 for a single-device context) back:
+ * (n_gamma_abc - 1) * 64 * 15 points in the order [base][window][digit - 1]; G16_ERR_BAD_ARG for an index the key has no copy on
+ * or a key of another context.  g16_dev_prepare_inputs runs one GPU lane per row of num_public Fr (inputs: n rows, Montgomery
+ * limbs) on the resident tables of the key's first copy, the function the batch verifier's lanes call, and writes n points;
+ * G16_ERR_MALFORMED_VK when num_public + 1 != n_gamma_abc, n = 0 is G16_OK and writes nothing, n > 2^22 is G16_ERR_BAD_ARG.
+ * The g16_host_ forms build the tables on the CPU, entry by entry with the table kernel's own function, and run the same
+ * accumulation (no GPU needed).  An input row is read as g16_verify_batch reads it (see there: x and x + r are the same input). */
+int g16_dev_pvk_tables(g16_ctx* ctx, const g16_pvk* pvk, int device_index, uint64_t* out);
+int g16_dev_prepare_inputs(g16_ctx* ctx, const g16_pvk* pvk, const uint64_t* inputs, uint64_t num_public, uint64_t n, uint64_t* out);
+int g16_host_pvk_tables(int curve, const g16_vk_view* vk, uint64_t* out);
+int g16_host_prepare_inputs(int curve, const g16_vk_view* vk, const uint64_t* inputs, uint64_t num_public, uint64_t n, uint64_t* out);
 
 /* ---- prime-order subgroup membership on the GPU (the point checks of Validate::Yes, without the byte formats) ----
  * Endomorphism tests with public constants: BLS12-381 G1 phi(P) = -[x^2]P, BLS12-381 G2 psi(Q) = [x]Q,

@@ -94,6 +94,12 @@ int main(int argc, char** argv) {
         if (rc != G16_OK || memcmp(out, one_plus_one, sizeof out) != 0) ++failures;
         printf("\"field_op_%d\": %d,\n", curve, rc == G16_OK && memcmp(out, one_plus_one, sizeof out) == 0);
     }
+    /* the input-preparation lab is declared and links: a NULL key view is refused, nothing is touched */
+    rc = g16_host_pvk_tables(G16_BLS12_381, NULL, NULL);
+    if (rc != G16_ERR_BAD_ARG || g16_host_prepare_inputs(G16_BN254, NULL, NULL, 0, 0, NULL) != G16_ERR_BAD_ARG ||
+        g16_dev_pvk_tables(NULL, NULL, 0, NULL) != G16_ERR_BAD_ARG || g16_dev_prepare_inputs(NULL, NULL, NULL, 0, 0, NULL) != G16_ERR_BAD_ARG)
+        ++failures;
+    printf("\"prepare_lab_null\": %d,\n", rc);
     rc = g16_ctx_create(G16_BLS12_381, 0, &ctx);
     printf("\"ctx_create\": %d,\n", rc);
     if (rc == G16_OK) {

@@ -108,6 +108,11 @@ def test_identity_ic(setup):
         L = cp.fq_limbs64
         zero, gen = np.zeros(2 * L, np.uint64), g1_to_arr([cp.g1], cp)[0]
         assert (prover.prepare_inputs(pvk, x_good).reshape(-1) == zero).all() and (prover.prepare_inputs(pvk, x_bad).reshape(-1) == gen).all()
+        # and from the device's own preparation (prepare_inputs_tab on the key's resident tables), which the host route above is not
+        from groth16_amd import binding
+        for xs, want in ((x_good, zero), (x_bad, gen)):
+            st, ic = binding.dev_prepare_inputs(g.lib(), prover._ctx.handle, pvk.handle, xs.reshape(1, 1, 4), 1, L)
+            assert st == 0 and (ic[0] == want).all()
         from groth16_amd.verifier import verify_batch_prepared
         assert list(verify_batch_prepared(prover._ctx, pvk, flat, np.stack([zero] * n))) == [1] * n
         assert list(verify_batch_prepared(prover._ctx, pvk, flat, np.stack([zero, gen] + [zero] * (n - 2)))) == [1, 0] + [1] * (n - 2)
