@@ -272,6 +272,39 @@ def ptr32(a: np.ndarray):
     return a.ctypes.data_as(u32p)
 
 
+def _ceremony_argtypes(c):
+    c.g16_rlc_sums.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, u64p, u64p, u64p]
+    c.g16_rlc_plan.argtypes = [C.c_uint64, u32p]
+    c.g16_host_rlc_sums.argtypes = [C.c_int, C.c_int, u64p, C.c_uint64, u64p, u64p, u64p]
+    c.g16_srs_check.argtypes = [C.c_void_p, C.POINTER(SrsViewC), u64p, C.c_uint64, C.POINTER(CeremonyInfoC)]
+    c.g16_host_srs_check.argtypes = [C.c_int] + c.g16_srs_check.argtypes[1:]
+    c.g16_params_check_delta.argtypes = [C.c_void_p, C.POINTER(ParamsViewC), C.POINTER(ParamsViewC), C.c_uint64, C.c_uint64, C.c_uint64,
+                                         C.c_uint64, u64p, C.c_uint64, C.POINTER(CeremonyInfoC)]
+    c.g16_host_params_check_delta.argtypes = [C.c_int] + c.g16_params_check_delta.argtypes[1:]
+    c.g16_ceremony_get_timings.argtypes = [C.c_void_p, C.POINTER(CeremonyTimingsC)]
+
+
+def _phase1_argtypes(c):
+    c.g16_batch_scalar_mul.argtypes = [C.c_void_p, C.c_int, u64p, u64p, C.c_uint64, u64p]
+    c.g16_host_batch_scalar_mul.argtypes = [C.c_int, C.c_int, u64p, u64p, C.c_uint64, u64p]
+    c.g16_host_batch_scalar_mul_windowed.argtypes = c.g16_host_batch_scalar_mul.argtypes
+    c.g16_srs_contribute.argtypes = [C.c_void_p, u64p, u64p, u64p, C.POINTER(SrsViewC), C.POINTER(TauContributionC), C.POINTER(Phase1TimingsC)]
+    c.g16_host_srs_contribute.argtypes = [C.c_int] + c.g16_srs_contribute.argtypes[1:]
+    c.g16_phase1_get_timings.argtypes = [C.c_void_p, C.POINTER(Phase1TimingsC)]
+    c.g16_srs_check_contribution.argtypes = [C.c_void_p, C.POINTER(SrsViewC), C.POINTER(SrsViewC), C.POINTER(TauContributionC), u64p, C.c_uint64,
+                                             C.POINTER(CeremonyInfoC)]
+    c.g16_host_srs_check_contribution.argtypes = [C.c_int] + c.g16_srs_check_contribution.argtypes[1:]
+
+
+def _keycheck_argtypes(c):
+    shape = [C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(SrsViewC)]
+    c.g16_params_check_derivation.argtypes = [C.c_void_p] + shape + [C.POINTER(ParamsViewC), u64p, C.c_uint64, C.POINTER(CeremonyInfoC)]
+    c.g16_host_params_check_derivation.argtypes = [C.c_int] + c.g16_params_check_derivation.argtypes[1:]
+    c.g16_key_fold_from_srs.argtypes = [C.c_void_p] + shape + [u64p, C.c_uint64, C.POINTER(KeyFoldC)]
+    c.g16_host_key_fold_from_srs.argtypes = [C.c_int] + c.g16_key_fold_from_srs.argtypes[1:]
+    c.g16_keycheck_get_timings.argtypes = [C.c_void_p, C.POINTER(KeycheckTimingsC)]
+
+
 class Lib:
     def __init__(self, path: str = LIB_PATH):
         if not os.path.exists(path):
@@ -279,9 +312,7 @@ class Lib:
                 f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  groth16_amd has no CPU fallback.")
         self.path = path
-        self._cer = None
-        self._ph1 = None
-        self._kc = None
+        self._companions = {}   # file name -> the loaded companion library (cer, ph1, kc)
         # One HIP runtime per process: torch wheels bundle their own libamdhip64, and this library links the system one.  Whichever is
         # loaded first serves both (same soname); loaded in the order library -> torch, g16_ctx_create found no device on the GPU box
         # (round 3: `python __graft_entry__.py smoke`, where build() loads the library before smoke() imports torch).  So when torch is
@@ -429,63 +460,31 @@ class Lib:
         c.g16_host_pvk_tables.argtypes = [C.c_int, C.POINTER(VkViewC), u64p]
         c.g16_host_prepare_inputs.argtypes = [C.c_int, C.POINTER(VkViewC), u64p, C.c_uint64, C.c_uint64, u64p]
 
-    @property
-    def cer(self):
-        """libg16_ceremony.so beside the library, loaded on first use (it links against the library and shares its contexts)"""
-        if self._cer is None:
-            path = os.path.join(os.path.dirname(self.path), "libg16_ceremony.so")
+    def _companion(self, name: str, set_argtypes):
+        """a companion library beside the library, loaded on first use and kept; set_argtypes(c) declares its entry points"""
+        if name not in self._companions:
+            path = os.path.join(os.path.dirname(self.path), name)
             if not os.path.exists(path):
                 raise ImportError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
             c = C.CDLL(path)
-            c.g16_rlc_sums.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, u64p, u64p, u64p]
-            c.g16_rlc_plan.argtypes = [C.c_uint64, u32p]
-            c.g16_host_rlc_sums.argtypes = [C.c_int, C.c_int, u64p, C.c_uint64, u64p, u64p, u64p]
-            c.g16_srs_check.argtypes = [C.c_void_p, C.POINTER(SrsViewC), u64p, C.c_uint64, C.POINTER(CeremonyInfoC)]
-            c.g16_host_srs_check.argtypes = [C.c_int] + c.g16_srs_check.argtypes[1:]
-            c.g16_params_check_delta.argtypes = [C.c_void_p, C.POINTER(ParamsViewC), C.POINTER(ParamsViewC), C.c_uint64, C.c_uint64, C.c_uint64,
-                                                 C.c_uint64, u64p, C.c_uint64, C.POINTER(CeremonyInfoC)]
-            c.g16_host_params_check_delta.argtypes = [C.c_int] + c.g16_params_check_delta.argtypes[1:]
-            c.g16_ceremony_get_timings.argtypes = [C.c_void_p, C.POINTER(CeremonyTimingsC)]
-            self._cer = c
-        return self._cer
+            set_argtypes(c)
+            self._companions[name] = c
+        return self._companions[name]
+
+    @property
+    def cer(self):
+        """libg16_ceremony.so (it links against the library and shares its contexts)"""
+        return self._companion("libg16_ceremony.so", _ceremony_argtypes)
 
     @property
     def ph1(self):
-        """libg16_phase1.so beside the library, loaded on first use (it links against the library and the ceremony library)"""
-        if self._ph1 is None:
-            path = os.path.join(os.path.dirname(self.path), "libg16_phase1.so")
-            if not os.path.exists(path):
-                raise ImportError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-            c = C.CDLL(path)
-            c.g16_batch_scalar_mul.argtypes = [C.c_void_p, C.c_int, u64p, u64p, C.c_uint64, u64p]
-            c.g16_host_batch_scalar_mul.argtypes = [C.c_int, C.c_int, u64p, u64p, C.c_uint64, u64p]
-            c.g16_host_batch_scalar_mul_windowed.argtypes = c.g16_host_batch_scalar_mul.argtypes
-            c.g16_srs_contribute.argtypes = [C.c_void_p, u64p, u64p, u64p, C.POINTER(SrsViewC), C.POINTER(TauContributionC),
-                                             C.POINTER(Phase1TimingsC)]
-            c.g16_host_srs_contribute.argtypes = [C.c_int] + c.g16_srs_contribute.argtypes[1:]
-            c.g16_phase1_get_timings.argtypes = [C.c_void_p, C.POINTER(Phase1TimingsC)]
-            c.g16_srs_check_contribution.argtypes = [C.c_void_p, C.POINTER(SrsViewC), C.POINTER(SrsViewC), C.POINTER(TauContributionC), u64p,
-                                                     C.c_uint64, C.POINTER(CeremonyInfoC)]
-            c.g16_host_srs_check_contribution.argtypes = [C.c_int] + c.g16_srs_check_contribution.argtypes[1:]
-            self._ph1 = c
-        return self._ph1
+        """libg16_phase1.so (it links against the library and the ceremony library)"""
+        return self._companion("libg16_phase1.so", _phase1_argtypes)
 
     @property
     def kc(self):
-        """libg16_keycheck.so beside the library, loaded on first use (it links against the library and its two other companions)"""
-        if self._kc is None:
-            path = os.path.join(os.path.dirname(self.path), "libg16_keycheck.so")
-            if not os.path.exists(path):
-                raise ImportError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-            c = C.CDLL(path)
-            shape = [C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(SrsViewC)]
-            c.g16_params_check_derivation.argtypes = [C.c_void_p] + shape + [C.POINTER(ParamsViewC), u64p, C.c_uint64, C.POINTER(CeremonyInfoC)]
-            c.g16_host_params_check_derivation.argtypes = [C.c_int] + c.g16_params_check_derivation.argtypes[1:]
-            c.g16_key_fold_from_srs.argtypes = [C.c_void_p] + shape + [u64p, C.c_uint64, C.POINTER(KeyFoldC)]
-            c.g16_host_key_fold_from_srs.argtypes = [C.c_int] + c.g16_key_fold_from_srs.argtypes[1:]
-            c.g16_keycheck_get_timings.argtypes = [C.c_void_p, C.POINTER(KeycheckTimingsC)]
-            self._kc = c
-        return self._kc
+        """libg16_keycheck.so (it links against the library and its two other companions)"""
+        return self._companion("libg16_keycheck.so", _keycheck_argtypes)
 
     def check(self, status: int, check_result: "Optional[CheckResultC]" = None, pk_bytes_info: "Optional[PkBytesInfoC]" = None):
         """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable; pk_bytes_info: the g16_pk_bytes_info

@@ -21,18 +21,16 @@
 //                               identity is not allowed, the all-zero test of the point's words -> a reason; one ballot per wave, the
 //                               wave's first bad lane takes a 64-bit atomic minimum of (array, index, reason) on one record in HBM.
 //                               The minimum does not depend on the order the waves arrive in.  No LDS.
-// The host twins (g16_host_*) run plain scalar multiplications and additions, Subgroup<C> and the host pairing.
-#include "ceremony.hpp"
-#include "../../include/g16_ceremony.h"
-#include "subgroup.hpp"
-#include "verify_common.hpp"
+// The host twins (g16_host_*) run plain scalar multiplications and additions, Subgroup<C> and the host pairing.  The host helpers of
+// the three companion libraries (stage timers, the stream wait, uploads, Grp, flag -> reason, the bad-point record, pairs_equal, refuse,
+// the checks of an SRS view, the stage times as a timings struct) are ceremony_common.hpp's.
+#include "ceremony_common.hpp"
 
 using namespace g16;
 
 namespace g16 {
 
 constexpr int CEREMONY_BLOCK = 256;
-constexpr unsigned long long CEREMONY_NONE = ~0ull;
 
 struct DigitPlan {
     int c, W;
@@ -59,7 +57,7 @@ __global__ __launch_bounds__(256) void ceremony_digits128_kernel(const uint64_t*
     }
 }
 
-// key = array << 48 | index << 8 | reason  (index < 2^31)
+// key = array << 48 | index << 8 | reason  (index < 2^31): bad_key's layout (ceremony_common.hpp), written out here for the device
 __global__ __launch_bounds__(CEREMONY_BLOCK) void ceremony_first_bad_kernel(const uint8_t* __restrict__ flags, const uint64_t* __restrict__ points,
                                                                            uint32_t words, uint64_t n, uint32_t array, uint32_t allow_identity,
                                                                            unsigned long long* __restrict__ rec) {
@@ -83,35 +81,9 @@ __global__ __launch_bounds__(CEREMONY_BLOCK) void ceremony_first_bad_kernel(cons
 
 namespace {
 
-template <class C, int G2> struct Grp;
-template <class C>
-struct Grp<C, 0> {
-    typedef typename C::Fq F;
-    static constexpr uint32_t WORDS = C::Fq::N;   // 64-bit words of an affine point
-    static uint8_t flag(const Affine<F>& p) { return Subgroup<C>::g1_flag(p); }
-};
-template <class C>
-struct Grp<C, 1> {
-    typedef typename C::Fq2 F;
-    static constexpr uint32_t WORDS = 2 * C::Fq::N;
-    static uint8_t flag(const Affine<F>& p) { return Subgroup<C>::g2_flag(p); }
-};
+typedef StageTimes<g16_ceremony_timings, 6> Stages;
+g16_ceremony_timings* tm_of(const CeremonyEnv& env) { return Stages::of(env.stage_ms); }
 
-static_assert(sizeof(g16_ceremony_timings) == 6 * sizeof(double), "the context keeps the stage times as six doubles");
-g16_ceremony_timings* tm_of(const CeremonyEnv& env) { return reinterpret_cast<g16_ceremony_timings*>(env.stage_ms); }
-
-struct Timers {
-    std::vector<EventTimer> v;
-    Timers() { v.reserve(16); }
-    ~Timers() { for (auto& t : v) t.destroy(); }
-    EventTimer* add() { v.emplace_back(); return &v.back(); }
-    double total() { double s = 0; for (auto& t : v) s += t.ms(); return s; }
-};
-// kernels in flight read arena memory that the next call reuses and write host vectors of this one: every exit waits
-struct StreamWait {
-    hipStream_t s;
-    ~StreamWait() { (void)hipStreamSynchronize(s); }
-};
 struct CallTimers {
     Timers upload, membership, sort, passes, reductions;
     double pairings = 0;
@@ -120,22 +92,10 @@ struct CallTimers {
         tm->passes_ms = passes.total(); tm->reductions_ms = reductions.total(); tm->pairings_ms = pairings;
     }
 };
-double wall_ms() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
-
-template <class F>
-int upload_points(const CeremonyEnv& env, const uint64_t* host, uint64_t n, Affine<F>** out) {
-    G16_TRY(env.arena->alloc_n(n ? n : 1, out));
-    if (n) G16_HIP_TRY(hipMemcpyAsync(*out, host, n * sizeof(Affine<F>), hipMemcpyHostToDevice, env.st));
-    return G16_OK;
-}
 
 // the membership kernels over one uploaded array, then its first bad point into the call's record
 template <class C, int G2>
-int enqueue_membership(const CeremonyEnv& env, const Affine<typename Grp<C, G2>::F>* d_pts, uint64_t n, uint32_t array, bool allow_identity,
+int enqueue_membership(const CeremonyEnv& env, const typename Grp<C, G2>::A* d_pts, uint64_t n, uint32_t array, bool allow_identity,
                        unsigned long long* d_rec) {
     if (!n) return G16_OK;
     uint8_t* d_flags = nullptr;
@@ -148,27 +108,16 @@ int enqueue_membership(const CeremonyEnv& env, const Affine<typename Grp<C, G2>:
     return G16_OK;
 }
 
-void decode_bad(unsigned long long key, uint32_t flag, g16_ceremony_info* info) {
-    info->flags = flag;
-    info->bad_array = (uint32_t)(key >> 48);
-    info->bad_index = (key >> 8) & 0xffffffffffull;
-    info->bad_reason = (uint32_t)(key & 0xffu);
-}
-
 // host twin of the two stages above; true: a bad point was recorded (the first in call order wins: arrays are scanned in field order)
 template <class C, int G2>
 bool host_membership(const uint64_t* pts, uint64_t n, uint32_t array, bool allow_identity, unsigned long long* rec) {
-    typedef Affine<typename Grp<C, G2>::F> A;
-    if (*rec != CEREMONY_NONE) return true;
-    for (uint64_t i = 0; i < n; ++i) {
-        const A p = ld_any<A>(pts + i * Grp<C, G2>::WORDS);
-        const uint8_t f = Grp<C, G2>::flag(p);
-        const uint32_t reason = f == 2 ? 2u : f == 0 ? 3u : (!allow_identity && p.is_identity()) ? 4u : 0u;
-        if (reason) {
-            *rec = ((unsigned long long)array << 48) | ((unsigned long long)i << 8) | reason;
+    typedef typename Grp<C, G2>::A A;
+    if (*rec != BAD_NONE) return true;
+    for (uint64_t i = 0; i < n; ++i)
+        if (const uint32_t reason = point_reason<C, G2>(ld_any<A>(pts + i * Grp<C, G2>::WORDS), allow_identity)) {
+            *rec = bad_key(array, i, reason);
             return true;
         }
-    }
     return false;
 }
 
@@ -245,20 +194,6 @@ int sort_on_device(const CeremonyEnv& env, const uint64_t* rho, uint64_t m, Scal
     return G16_OK;
 }
 
-// e(a, b) == e(c, d), as the two-pair product e(a, b) e(-c, d) compared with 1.  On the host templates for the device forms too, as
-// the once-per-batch tail of verify_aggregate.hip: a lone GPU lane runs this chain several times slower than one host thread, and a
-// call has five of them at most whatever the size of its arrays
-template <class C>
-int pairs_equal(const typename C::G1A& a, const typename C::G2A& b, const typename C::G1A& c, const typename C::G2A& d, bool* equal) {
-    typedef Pairing<C> PP;
-    const typename C::G1A g1s[2] = {a, c.neg()};
-    const typename C::G2A g2s[2] = {b, d};
-    typename PP::F12 e;
-    *equal = host_pairing_product<C>(reinterpret_cast<const uint64_t*>(g1s), reinterpret_cast<const uint64_t*>(g2s), 2, e) &&
-             PP::equal(e, PP::F12::one());
-    return G16_OK;
-}
-
 template <class C, int G2>
 int rlc_device(const CeremonyEnv& env, const uint64_t* points, uint64_t n, const uint64_t* rho, uint64_t* out_lo, uint64_t* out_hi) {
     typedef typename Grp<C, G2>::F F;
@@ -267,7 +202,7 @@ int rlc_device(const CeremonyEnv& env, const uint64_t* points, uint64_t n, const
     Affine<F>* d_x = nullptr;
     EventTimer* tu = ct.upload.add();
     G16_TRY(tu->start(env.st));
-    G16_TRY(upload_points<F>(env, points, n, &d_x));
+    G16_TRY(upload(env, points, n, &d_x));
     G16_TRY(tu->stop(env.st));
     ScalarSort ss;
     G16_TRY(sort_on_device(env, rho, n - 1, &ss, ct));
@@ -319,7 +254,7 @@ struct SrsSums {
     typename C::G2A g2[2];   // lo / hi of tau_g2
 };
 
-// *bad: the record of the first bad point (CEREMONY_NONE: every point passed, and then `sums` is filled)
+// *bad: the record of the first bad point (BAD_NONE: every point passed, and then `sums` is filled)
 template <class C>
 int srs_sums_device(const CeremonyEnv& env, const g16_srs_view* srs, const uint64_t* rho, uint64_t m, unsigned long long* bad, SrsSums<C>* sums,
                     CallTimers& ct) {
@@ -332,11 +267,11 @@ int srs_sums_device(const CeremonyEnv& env, const g16_srs_view* srs, const uint6
     unsigned long long* d_rec = nullptr;
     EventTimer* tu = ct.upload.add();
     G16_TRY(tu->start(env.st));
-    G16_TRY(upload_points<Fq>(env, srs->tau_g1, N1, &d_t1));
-    G16_TRY(upload_points<Fq2>(env, srs->tau_g2, N2, &d_t2));
-    G16_TRY(upload_points<Fq>(env, srs->alpha_tau_g1, M, &d_a));
-    G16_TRY(upload_points<Fq>(env, srs->beta_tau_g1, M, &d_b));
-    G16_TRY(upload_points<Fq2>(env, srs->beta_g2, 1, &d_bg2));
+    G16_TRY(upload(env, srs->tau_g1, N1, &d_t1));
+    G16_TRY(upload(env, srs->tau_g2, N2, &d_t2));
+    G16_TRY(upload(env, srs->alpha_tau_g1, M, &d_a));
+    G16_TRY(upload(env, srs->beta_tau_g1, M, &d_b));
+    G16_TRY(upload(env, srs->beta_g2, 1, &d_bg2));
     G16_TRY(tu->stop(env.st));
     G16_TRY(env.arena->alloc_n(1, &d_rec));
     G16_HIP_TRY(hipMemsetAsync(d_rec, 0xff, sizeof(unsigned long long), env.st));
@@ -350,7 +285,7 @@ int srs_sums_device(const CeremonyEnv& env, const g16_srs_view* srs, const uint6
     G16_TRY(tm->stop(env.st));
     G16_HIP_TRY(hipMemcpyAsync(bad, d_rec, sizeof(unsigned long long), hipMemcpyDeviceToHost, env.st));
     G16_HIP_TRY(hipStreamSynchronize(env.st));
-    if (*bad != CEREMONY_NONE) return G16_OK;
+    if (*bad != BAD_NONE) return G16_OK;
     ScalarSort ss;
     G16_TRY(sort_on_device(env, rho, m, &ss, ct));
     G16_TRY((convert_bases<Fq>(d_t1, N1, env.st)));
@@ -371,7 +306,7 @@ void srs_sums_host(const g16_srs_view* srs, const uint64_t* rho, unsigned long l
     typedef typename C::Fq Fq;
     typedef typename C::Fq2 Fq2;
     const uint64_t N1 = srs->n_tau_g1, N2 = srs->n_tau_g2, M = srs->n_alpha_beta;
-    *bad = CEREMONY_NONE;
+    *bad = BAD_NONE;
     if (host_membership<C, 0>(srs->tau_g1, N1, 0, false, bad) || host_membership<C, 1>(srs->tau_g2, N2, 1, false, bad) ||
         host_membership<C, 0>(srs->alpha_tau_g1, M, 2, false, bad) || host_membership<C, 0>(srs->beta_tau_g1, M, 3, false, bad) ||
         host_membership<C, 1>(srs->beta_g2, 1, 4, false, bad))
@@ -400,7 +335,7 @@ int srs_check_any(const CeremonyEnv* env, const g16_srs_view* srs, const uint64_
     const uint64_t* rho = nullptr;
     G16_TRY(agg_coeffs(coeffs, m, own, &rho));
     SrsSums<C> s;
-    unsigned long long bad = CEREMONY_NONE;
+    unsigned long long bad = BAD_NONE;
     CallTimers ct;
     if (env) {
         const int rc = srs_sums_device<C>(*env, srs, rho, m, &bad, &s, ct);
@@ -409,7 +344,7 @@ int srs_check_any(const CeremonyEnv* env, const g16_srs_view* srs, const uint64_
     } else {
         srs_sums_host<C>(srs, rho, &bad, &s);
     }
-    if (bad != CEREMONY_NONE) { decode_bad(bad, G16_SRS_BAD_POINT, info); return G16_OK; }
+    if (bad != BAD_NONE) { decode_bad(bad, G16_SRS_BAD_POINT, info); return G16_OK; }
     const G1A g1 = ld_any<G1A>(srs->tau_g1), tau1 = ld_any<G1A>(srs->tau_g1 + W1), beta1 = ld_any<G1A>(srs->beta_tau_g1);
     const G2A g2 = ld_any<G2A>(srs->tau_g2), tau2 = ld_any<G2A>(srs->tau_g2 + W2), beta2 = ld_any<G2A>(srs->beta_g2);
     const double t0 = wall_ms();
@@ -452,12 +387,12 @@ int key_sums_device(const CeremonyEnv& env, const g16_params_view* before, const
     unsigned long long* d_rec = nullptr;
     EventTimer* tu = ct.upload.add();
     G16_TRY(tu->start(env.st));
-    G16_TRY(upload_points<Fq>(env, after->delta_g1, 1, &d_d1));
-    G16_TRY(upload_points<Fq2>(env, after->delta_g2, 1, &d_d2));
-    G16_TRY(upload_points<Fq>(env, after->l_query, n_l, &d_al));
-    G16_TRY(upload_points<Fq>(env, after->h_query, n_h, &d_ah));
-    G16_TRY(upload_points<Fq>(env, before->l_query, n_l, &d_bl));
-    G16_TRY(upload_points<Fq>(env, before->h_query, n_h, &d_bh));
+    G16_TRY(upload(env, after->delta_g1, 1, &d_d1));
+    G16_TRY(upload(env, after->delta_g2, 1, &d_d2));
+    G16_TRY(upload(env, after->l_query, n_l, &d_al));
+    G16_TRY(upload(env, after->h_query, n_h, &d_ah));
+    G16_TRY(upload(env, before->l_query, n_l, &d_bl));
+    G16_TRY(upload(env, before->h_query, n_h, &d_bh));
     G16_TRY(tu->stop(env.st));
     G16_TRY(env.arena->alloc_n(1, &d_rec));
     G16_HIP_TRY(hipMemsetAsync(d_rec, 0xff, sizeof(unsigned long long), env.st));
@@ -470,7 +405,7 @@ int key_sums_device(const CeremonyEnv& env, const g16_params_view* before, const
     G16_TRY(tm->stop(env.st));
     G16_HIP_TRY(hipMemcpyAsync(bad, d_rec, sizeof(unsigned long long), hipMemcpyDeviceToHost, env.st));
     G16_HIP_TRY(hipStreamSynchronize(env.st));
-    if (*bad != CEREMONY_NONE || !m) return G16_OK;
+    if (*bad != BAD_NONE || !m) return G16_OK;
     ScalarSort ss;
     G16_TRY(sort_on_device(env, rho, m, &ss, ct));
     G16_TRY((convert_bases<Fq>(d_al, n_l, env.st)));
@@ -496,7 +431,7 @@ int params_check_delta_any(const CeremonyEnv* env, const g16_params_view* before
     const uint64_t* rho = nullptr;
     G16_TRY(agg_coeffs(coeffs, m, own, &rho));
     G1A sums[4] = {G1A::identity(), G1A::identity(), G1A::identity(), G1A::identity()};   // after.l, before.l, after.h, before.h
-    unsigned long long bad = CEREMONY_NONE;
+    unsigned long long bad = BAD_NONE;
     CallTimers ct;
     if (env) {
         const int rc = key_sums_device<C>(*env, before, after, n_l, n_h, rho, m, &bad, sums, ct);
@@ -509,7 +444,7 @@ int params_check_delta_any(const CeremonyEnv* env, const g16_params_view* before
         sums[2] = host_sum<Fq>(after->h_query, n_h, 0, rho);
         sums[3] = host_sum<Fq>(before->h_query, n_h, 0, rho);
     }
-    if (bad != CEREMONY_NONE) { decode_bad(bad, G16_KEY_BAD_POINT, info); return G16_OK; }
+    if (bad != BAD_NONE) { decode_bad(bad, G16_KEY_BAD_POINT, info); return G16_OK; }
     uint32_t flags = 0;
     // the part no contribution may touch: a host compare, the first difference in field order
     const struct { const uint64_t *a, *b; uint64_t n; uint32_t words; } fixed[8] = {
@@ -547,24 +482,12 @@ int params_check_delta_any(const CeremonyEnv* env, const g16_params_view* before
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------------
 namespace {
-int refuse(int status, const char* fmt, unsigned long long a, unsigned long long b, unsigned long long c, const char* name = "") {
-    char buf[256];
-    snprintf(buf, sizeof(buf), fmt, name, a, b, c);
-    set_last_error_text(buf);
-    return status;
-}
-
 // what both forms of g16_srs_check refuse alike: every array long enough for one equation, enough explicit coefficients
-int srs_lengths(const g16_srs_view* srs, const uint64_t* coeffs, uint64_t n_coeffs) {
-    if (!srs->tau_g1 || !srs->tau_g2 || !srs->alpha_tau_g1 || !srs->beta_tau_g1 || !srs->beta_g2) return G16_ERR_BAD_ARG;
-    const struct { const char* name; uint64_t have, need; } arr[] = {
-        {"tau_g1", srs->n_tau_g1, 2}, {"tau_g2", srs->n_tau_g2, 2}, {"alpha_tau_g1 / beta_tau_g1", srs->n_alpha_beta, 1}};
-    uint64_t longest = 0;
-    for (const auto& a : arr) {
-        if (a.have < a.need) return refuse(G16_ERR_BAD_LENGTH, "SRS check: %s holds %llu points, the check needs %llu", a.have, a.need, 0, a.name);
-        if (a.have >= ((uint64_t)1 << 31)) return refuse(G16_ERR_BAD_LENGTH, "SRS check: %s holds 2^31 points or more", 0, 0, 0, a.name);
-        longest = std::max(longest, a.have);
-    }
+int srs_args(const g16_srs_view* srs, const uint64_t* coeffs, uint64_t n_coeffs) {
+    if (!srs_view_ok(srs)) return G16_ERR_BAD_ARG;
+    const SrsArray arr[] = {{"tau_g1", srs->n_tau_g1, 2}, {"tau_g2", srs->n_tau_g2, 2}, {"alpha_tau_g1 / beta_tau_g1", srs->n_alpha_beta, 1}};
+    G16_TRY(srs_lengths(arr, "SRS check: %s holds %llu points, the check needs %llu", 0, "SRS check: %s holds 2^31 points or more"));
+    const uint64_t longest = std::max(std::max(srs->n_tau_g1, srs->n_tau_g2), srs->n_alpha_beta);
     if (coeffs && n_coeffs < longest - 1)
         return refuse(G16_ERR_BAD_LENGTH, "SRS check%s: %llu coefficients, the longest array (%llu points) needs %llu", n_coeffs, longest, longest - 1);
     return G16_OK;
@@ -613,7 +536,7 @@ int g16_host_rlc_sums(int curve, int g2, const uint64_t* points, uint64_t n, con
 
 int g16_srs_check(g16_ctx* ctx, const g16_srs_view* srs, const uint64_t* coeffs, uint64_t n_coeffs, g16_ceremony_info* info) {
     if (!ctx || !srs || !info) return G16_ERR_BAD_ARG;
-    G16_TRY(srs_lengths(srs, coeffs, n_coeffs));
+    G16_TRY(srs_args(srs, coeffs, n_coeffs));
     CeremonyEnv env;
     int curve = -1;
     G16_TRY(ceremony_enter(ctx, &env, &curve));
@@ -622,7 +545,7 @@ int g16_srs_check(g16_ctx* ctx, const g16_srs_view* srs, const uint64_t* coeffs,
 
 int g16_host_srs_check(int curve, const g16_srs_view* srs, const uint64_t* coeffs, uint64_t n_coeffs, g16_ceremony_info* info) {
     if (!srs || !info) return G16_ERR_BAD_ARG;
-    G16_TRY(srs_lengths(srs, coeffs, n_coeffs));
+    G16_TRY(srs_args(srs, coeffs, n_coeffs));
     G16_VERIFY_DISPATCH(curve, (srs_check_any<CC>(nullptr, srs, coeffs, info)));
 }
 
@@ -644,10 +567,7 @@ int g16_host_params_check_delta(int curve, const g16_params_view* before, const 
 }
 
 int g16_ceremony_get_timings(g16_ctx* ctx, g16_ceremony_timings* out) {
-    const double* ms = ceremony_stage_ms(ctx);
-    if (!ms || !out) return G16_ERR_BAD_ARG;
-    memcpy(out, ms, sizeof(*out));
-    return G16_OK;
+    return Stages::get(ceremony_stage_ms(ctx), out);
 }
 
 }  // extern "C"

@@ -19,15 +19,14 @@
 //                                above give zeros.  Gather-bound like spmv3_kernel
 //   keycheck_scatter_odd_kernel  e[2j + 1] = rho_j, e[2j] = 0
 //   keycheck_add_kernel          out = a + b
-// The host twins run the same row walk (key_row_split), radix-2 transforms and a small bucket method in plain host C++.
-#include "ceremony.hpp"
+// The host twins run the same row walk (key_row_split), radix-2 transforms and a small bucket method in plain host C++.  The stage
+// timers, the stream wait, uploads, Grp, flag -> reason, the bad-point record, pairs_equal, refuse, the checks of an SRS view and the
+// stage times are ceremony_common.hpp's.
+#include "ceremony_common.hpp"
 #include "../../include/g16_keycheck.h"
 #include "csr_row_dot.hpp"
 #include "srs_setup.hpp"
-#include "subgroup.hpp"
-#include "verify_common.hpp"
 #include <algorithm>
-#include <deque>
 
 using namespace g16;
 
@@ -111,10 +110,9 @@ __global__ __launch_bounds__(KEYCHECK_BLOCK) void keycheck_add_kernel(const Fr* 
 
 namespace {
 
-constexpr unsigned long long KEYCHECK_NONE = ~0ull;
 inline unsigned kc_blocks(uint64_t n) { return (unsigned)((n + KEYCHECK_BLOCK - 1) / KEYCHECK_BLOCK); }
 
-static_assert(sizeof(g16_keycheck_timings) == 10 * sizeof(double), "the context keeps g16_keycheck_timings as ten doubles");
+typedef StageTimes<g16_keycheck_timings, 10> Stages;
 
 struct Shape {
     uint64_t ni, nc, nv, n, n_l, n_h, m;   // m: coefficients the call reads = max(nv, n_h)
@@ -131,17 +129,6 @@ struct KeySums {
                 b2(C::G2A::identity()) {}
 };
 
-struct Timers {
-    std::vector<EventTimer> v;
-    Timers() { v.reserve(64); }
-    ~Timers() { for (auto& t : v) t.destroy(); }
-    EventTimer* add() { v.emplace_back(); return &v.back(); }   // (at most 64 per stage: the pointers stay valid)
-    double total() { double s = 0; for (auto& t : v) s += t.ms(); return s; }
-};
-struct StreamWait {
-    hipStream_t s;
-    ~StreamWait() { (void)hipStreamSynchronize(s); }
-};
 struct CallTimers {
     Timers upload, membership, rows, transforms, sorts, passes, reductions;
     double pairings = 0, c = 0, W = 0;
@@ -151,18 +138,6 @@ struct CallTimers {
         tm->reductions_ms = reductions.total(); tm->pairings_ms = pairings; tm->window_bits = c; tm->windows = W;
     }
 };
-double wall_ms() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
-
-template <class T>
-int upload(const CeremonyEnv& env, const void* host, uint64_t n, T** out) {
-    G16_TRY(env.arena->alloc_n(n ? n : 1, out));
-    if (n) G16_HIP_TRY(hipMemcpyAsync(*out, host, n * sizeof(T), hipMemcpyHostToDevice, env.st));
-    return G16_OK;
-}
 
 template <class F>
 XYZZ<F> lift(const Affine<F>& p) { return XYZZ<F>::from_affine(p); }
@@ -248,34 +223,27 @@ Affine<F> sub2(const Affine<F>& a, const Affine<F>& b) {
 
 // the first bad point of one array of a key in host memory (flags as the membership kernels write them: 1 in, 2 off the curve, 0 out)
 void scan_flags(const std::vector<uint8_t>& flags, uint32_t array, unsigned long long* rec) {
-    if (*rec != KEYCHECK_NONE) return;
+    if (*rec != BAD_NONE) return;
     for (uint64_t i = 0; i < flags.size(); ++i)
-        if (flags[i] != 1) {
-            *rec = ((unsigned long long)array << 48) | ((unsigned long long)i << 8) | (flags[i] == 2 ? 2u : 3u);
+        if (const uint32_t reason = flag_reason(flags[i], true)) {   // the identity is a point of a query
+            *rec = bad_key(array, i, reason);
             return;
         }
 }
 template <class C, int G2>
 void host_flags(const uint64_t* pts, uint64_t n, std::vector<uint8_t>& flags) {
-    typedef typename std::conditional<G2 != 0, typename C::G2A, typename C::G1A>::type A;
-    constexpr size_t W = sizeof(A) / sizeof(uint64_t);
+    typedef Grp<C, G2> G;
     flags.resize(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        const A p = ld_any<A>(pts + i * W);
-        if constexpr (G2 != 0) flags[i] = Subgroup<C>::g2_flag(p);
-        else flags[i] = Subgroup<C>::g1_flag(p);
-    }
+    for (uint64_t i = 0; i < n; ++i) flags[i] = G::flag(ld_any<typename G::A>(pts + i * G::WORDS));
 }
 // the two deltas: on the host in both forms (two points); the identity is refused
 template <class C>
 void check_deltas(const g16_params_view* key, unsigned long long* rec) {
-    if (*rec != KEYCHECK_NONE) return;
-    const typename C::G1A d1 = ld_any<typename C::G1A>(key->delta_g1);
-    const typename C::G2A d2 = ld_any<typename C::G2A>(key->delta_g2);
-    const uint8_t f1 = Subgroup<C>::g1_flag(d1), f2 = Subgroup<C>::g2_flag(d2);
-    const uint32_t r1 = f1 == 2 ? 2u : f1 == 0 ? 3u : d1.is_identity() ? 4u : 0u, r2 = f2 == 2 ? 2u : f2 == 0 ? 3u : d2.is_identity() ? 4u : 0u;
-    if (r1) *rec = (6ull << 48) | r1;
-    else if (r2) *rec = (7ull << 48) | r2;
+    if (*rec != BAD_NONE) return;
+    const uint32_t r1 = point_reason<C, 0>(ld_any<typename C::G1A>(key->delta_g1), false);
+    const uint32_t r2 = point_reason<C, 1>(ld_any<typename C::G2A>(key->delta_g2), false);
+    if (r1) *rec = bad_key(6, 0, r1);
+    else if (r2) *rec = bad_key(7, 0, r2);
 }
 
 // ---- the host twin ----------------------------------------------------------------------------------------------------------------
@@ -288,7 +256,7 @@ int fold_host(const Shape& sh, const g16_csr_view abc[3], const g16_srs_view* sr
     typedef typename C::G1A A1;
     typedef typename C::G2A A2;
     const uint64_t n = sh.n;
-    *bad = KEYCHECK_NONE;
+    *bad = BAD_NONE;
     if (key) {
         std::vector<uint8_t> fl;
         const struct { const void* p; uint64_t cnt; int g2; } arr[6] = {{key->a_query, sh.nv, 0},      {key->b_g1_query, sh.nv, 0},
@@ -300,7 +268,7 @@ int fold_host(const Shape& sh, const g16_csr_view abc[3], const g16_srs_view* sr
             scan_flags(fl, k, bad);
         }
         check_deltas<C>(key, bad);
-        if (*bad != KEYCHECK_NONE) return G16_OK;
+        if (*bad != BAD_NONE) return G16_OK;
     }
     std::vector<Fr> rho(sh.m);
     for (uint64_t i = 0; i < sh.m; ++i) rho[i] = coeff_fr<Fr>(rho128 + 2 * i);
@@ -389,7 +357,7 @@ struct DomainHold {
 };
 
 template <class C, int G2>
-int device_flags(const CeremonyEnv& env, const void* d_pts, uint64_t n, std::vector<uint8_t>& host) {
+int device_flags(const CeremonyEnv& env, const typename Grp<C, G2>::A* d_pts, uint64_t n, std::vector<uint8_t>& host) {
     host.assign(n, 1);
     if (!n) return G16_OK;
     uint8_t* d_flags = nullptr;
@@ -409,7 +377,7 @@ int fold_device(const CeremonyEnv& env, const Shape& sh, const g16_csr_view abc[
     typedef typename C::G2A A2;
     const uint64_t n = sh.n, n_tau = 2 * n - 1;
     const hipStream_t st = env.st;
-    *bad = KEYCHECK_NONE;
+    *bad = BAD_NONE;
     DomainHold<C> dom, dom2;   // destroyed after the stream has drained (StreamWait is declared later, so it runs first)
     StreamWait wait{st};
     // ---- upload
@@ -458,7 +426,7 @@ int fold_device(const CeremonyEnv& env, const Shape& sh, const g16_csr_view abc[
         G16_HIP_TRY(hipStreamSynchronize(st));
         for (uint32_t k = 0; k < 6; ++k) scan_flags(fl[k], k, bad);
         check_deltas<C>(key, bad);
-        if (*bad != KEYCHECK_NONE) return G16_OK;
+        if (*bad != BAD_NONE) return G16_OK;
     }
     // ---- rows: rho as Fr, then the six row vectors
     Fr* d_rho = nullptr;
@@ -581,13 +549,6 @@ int fold_device(const CeremonyEnv& env, const Shape& sh, const g16_csr_view abc[
 }
 
 // ---- arguments ------------------------------------------------------------------------------------------------------------------------
-int refuse(int status, const char* fmt, unsigned long long a, unsigned long long b, unsigned long long c, const char* name = "") {
-    char buf[256];
-    snprintf(buf, sizeof(buf), fmt, name, a, b, c);
-    set_last_error_text(buf);
-    return status;
-}
-
 // the shape of the call, the matrices (every column below num_variables: the row kernel gathers by them), the SRS lengths the
 // equations need, the coefficients
 template <class C>
@@ -609,12 +570,11 @@ int check_args(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv,
         for (uint64_t k = v.row_ptr[0]; k < v.row_ptr[nc]; ++k)
             if (v.col[k] >= nv) return refuse(G16_ERR_BAD_LENGTH, "key check%s: matrix %llu names column %llu of %llu variables", m, v.col[k], nv);
     }
-    if (!srs->tau_g1 || !srs->tau_g2 || !srs->alpha_tau_g1 || !srs->beta_tau_g1 || !srs->beta_g2) return G16_ERR_BAD_ARG;
-    const struct { const char* name; uint64_t have, need; } arr[3] = {
+    if (!srs_view_ok(srs)) return G16_ERR_BAD_ARG;
+    const SrsArray arr[3] = {
         {"tau_g1", srs->n_tau_g1, 2 * n - 1}, {"tau_g2", srs->n_tau_g2, n}, {"alpha_tau_g1 / beta_tau_g1 (one count)", srs->n_alpha_beta, n}};
-    for (const auto& a : arr)
-        if (a.have < a.need)
-            return refuse(G16_ERR_BAD_LENGTH, "SRS too short: %s holds %llu points, a domain of %llu needs %llu", a.have, n, a.need, a.name);
+    // srs_lengths passes (name, have, need, n): the text names them in another order, hence the positions
+    G16_TRY(srs_lengths(arr, "SRS too short: %1$s holds %2$llu points, a domain of %4$llu needs %3$llu", n));
     if (coeffs && n_coeffs < sh->m)
         return refuse(G16_ERR_BAD_LENGTH, "key check%s: %llu coefficients, %llu variables and %llu points of h_query need more", n_coeffs, nv, sh->n_h);
     return G16_OK;
@@ -624,17 +584,6 @@ bool key_view_ok(const g16_params_view* k, const Shape& sh) {
     if (!k->alpha_g1 || !k->beta_g1 || !k->delta_g1 || !k->beta_g2 || !k->delta_g2 || !k->gamma_g2) return false;
     if (k->flags & G16_PARAMS_DEVICE_PTRS) return false;
     return k->gamma_abc_g1 && k->a_query && k->b_g1_query && k->b_g2_query && (k->h_query || !sh.n_h) && (k->l_query || !sh.n_l);
-}
-
-template <class C>
-int pairs_equal(const typename C::G1A& a, const typename C::G2A& b, const typename C::G1A& c, const typename C::G2A& d, bool* equal) {
-    typedef Pairing<C> PP;
-    const typename C::G1A g1s[2] = {a, c.neg()};
-    const typename C::G2A g2s[2] = {b, d};
-    typename PP::F12 e;
-    *equal = host_pairing_product<C>(reinterpret_cast<const uint64_t*>(g1s), reinterpret_cast<const uint64_t*>(g2s), 2, e) &&
-             PP::equal(e, PP::F12::one());
-    return G16_OK;
 }
 
 }  // namespace
@@ -655,7 +604,7 @@ int keycheck_any(const CeremonyEnv* env, g16_keycheck_timings* tm, const g16_csr
     const uint64_t* rho = nullptr;
     G16_TRY(agg_coeffs(coeffs, sh.m, own, &rho));
     KeySums<C> s_srs, s_key;
-    unsigned long long bad = KEYCHECK_NONE;
+    unsigned long long bad = BAD_NONE;
     if (env) {
         CallTimers ct;
         const int rc = fold_device<C>(*env, sh, abc, srs, key, rho, &s_srs, &s_key, &bad, ct);
@@ -673,13 +622,7 @@ int keycheck_any(const CeremonyEnv* env, g16_keycheck_timings* tm, const g16_csr
         memcpy(out->h, &s_srs.h, sizeof(G1A));
         return G16_OK;
     }
-    if (bad != KEYCHECK_NONE) {
-        info->flags = G16_KEYCHECK_BAD_POINT;
-        info->bad_array = (uint32_t)(bad >> 48);
-        info->bad_index = (bad >> 8) & 0xffffffffffull;
-        info->bad_reason = (uint32_t)(bad & 0xffu);
-        return G16_OK;
-    }
+    if (bad != BAD_NONE) { decode_bad(bad, G16_KEYCHECK_BAD_POINT, info); return G16_OK; }
     uint32_t flags = 0;
     const struct { const uint64_t *a, *b; size_t bytes; } fixed[4] = {{key->alpha_g1, srs->alpha_tau_g1, sizeof(G1A)},
                                                                       {key->beta_g1, srs->beta_tau_g1, sizeof(G1A)},
@@ -725,7 +668,7 @@ int g16_params_check_derivation(g16_ctx* ctx, const g16_csr_view abc[3], uint64_
     CeremonyEnv env;
     int curve = -1;
     G16_TRY(ceremony_enter(ctx, &env, &curve));
-    g16_keycheck_timings* tm = reinterpret_cast<g16_keycheck_timings*>(keycheck_stage_ms(ctx));
+    g16_keycheck_timings* tm = Stages::of(keycheck_stage_ms(ctx));
     G16_VERIFY_DISPATCH(curve, (keycheck_any<CC>(&env, tm, abc, num_inputs, num_constraints, num_variables, qap, srs, key, coeffs, n_coeffs, nullptr,
                                                  info)));
 }
@@ -746,7 +689,7 @@ int g16_key_fold_from_srs(g16_ctx* ctx, const g16_csr_view abc[3], uint64_t num_
     CeremonyEnv env;
     int curve = -1;
     G16_TRY(ceremony_enter(ctx, &env, &curve));
-    g16_keycheck_timings* tm = reinterpret_cast<g16_keycheck_timings*>(keycheck_stage_ms(ctx));
+    g16_keycheck_timings* tm = Stages::of(keycheck_stage_ms(ctx));
     G16_VERIFY_DISPATCH(curve, (keycheck_any<CC>(&env, tm, abc, num_inputs, num_constraints, num_variables, qap, srs, nullptr, coeffs, n_coeffs, out,
                                                  nullptr)));
 }
@@ -759,10 +702,7 @@ int g16_host_key_fold_from_srs(int curve, const g16_csr_view abc[3], uint64_t nu
 }
 
 int g16_keycheck_get_timings(g16_ctx* ctx, g16_keycheck_timings* out) {
-    const double* ms = keycheck_stage_ms(ctx);
-    if (!ms || !out) return G16_ERR_BAD_ARG;
-    memcpy(out, ms, sizeof(*out));
-    return G16_OK;
+    return Stages::get(keycheck_stage_ms(ctx), out);
 }
 
 }  // extern "C"

@@ -9,11 +9,10 @@
 //                             run.  The output feeds the kernel above on the device; it is the toxic waste and never leaves it.
 // A contribution walks each array in chunks: upload, powers, multiply in place, download; the scalar buffer and the park buffer are
 // zeroed on the stream before the call returns.  The check is g16_srs_check on `after` plus three two-pair products on the host.
-#include "ceremony.hpp"
+// The stage timers, the stream wait, Grp, the reason of a bad point, pairs_equal and the stage times are ceremony_common.hpp's.
+#include "ceremony_common.hpp"
 #include "../../include/g16_phase1.h"
 #include "scalar_mul.hpp"
-#include "subgroup.hpp"
-#include "verify_common.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -66,11 +65,7 @@ template <class F> struct Lazy;
 template <class P> struct Lazy<Fp<P>> { typedef Fp30<P> type; };
 template <class P> struct Lazy<Fp2<P>> { typedef Fp2p30<P> type; };
 
-template <class C, int G2> struct Grp;
-template <class C> struct Grp<C, 0> { typedef typename C::Fq F; static constexpr uint32_t WORDS = C::Fq::N; };
-template <class C> struct Grp<C, 1> { typedef typename C::Fq2 F; static constexpr uint32_t WORDS = 2 * C::Fq::N; };
-
-static_assert(sizeof(g16_phase1_timings) == 5 * sizeof(double), "the context keeps the stage times as five doubles");
+typedef StageTimes<g16_phase1_timings, 5> Stages;
 
 uint64_t env_u64(const char* name, uint64_t dflt, uint64_t lo, uint64_t hi) {
     const char* e = getenv(name);
@@ -86,13 +81,6 @@ size_t park_words(uint64_t count) {
     return (size_t)(SMUL_SLOTS * TableLane<F30>::B::NL + SMUL_KWORDS) * count * F30::LANES_PER_TASK;
 }
 
-struct Timers {
-    std::vector<EventTimer> v;
-    Timers() { v.reserve(64); }
-    ~Timers() { for (auto& t : v) t.destroy(); }
-    EventTimer* add() { v.emplace_back(); return &v.back(); }   // (a pointer is used before the next add)
-    double total() { double s = 0; for (auto& t : v) s += t.ms(); return s; }
-};
 struct CallTimers {
     Timers upload, powers, mul[2], download;
     void store(g16_phase1_timings* tm) {
@@ -122,14 +110,12 @@ struct Work {
         return G16_OK;
     }
 };
-// every exit wipes and waits: kernels in flight read arena memory that the next call reuses and write the caller's arrays
+// every exit wipes and waits: kernels in flight read arena memory that the next call reuses and write the caller's arrays.  The order
+// is the language's: this destructor's body queues the wipes, then the member `wait` is destroyed and waits for them
 struct WipeAndWait {
     const Work& w;
-    hipStream_t st;
-    ~WipeAndWait() {
-        if (w.scalars) (void)w.wipe(st);
-        (void)hipStreamSynchronize(st);
-    }
+    StreamWait wait;
+    ~WipeAndWait() { if (w.scalars) (void)w.wipe(wait.s); }
 };
 
 template <class C, int G2>
@@ -171,7 +157,7 @@ int batch_mul_device(const CeremonyEnv& env, const uint64_t* points, const uint6
     const uint64_t chunk = std::min(n, phase1_chunk());
     Work w;
     G16_TRY(w.alloc<C>(env, chunk, G2 != 0));
-    WipeAndWait guard{w, env.st};
+    WipeAndWait guard{w, {env.st}};
     for (uint64_t first = 0; first < n; first += chunk) {
         const uint64_t count = std::min(chunk, n - first);
         G16_TRY((copy_in<C, G2>(env, w, points + first * Grp<C, G2>::WORDS, count, ct)));
@@ -357,7 +343,7 @@ int srs_contribute_any(const CeremonyEnv* env, const uint64_t* tau_, const uint6
         G16_TRY(w.alloc<C>(*env, chunk, true));
         int rc;
         {
-            WipeAndWait guard{w, env->st};
+            WipeAndWait guard{w, {env->st}};
             auto body = [&]() -> int {
                 G16_TRY((contribute_array<C, 0>(*env, w, chunk, run, io->tau_g1 + W1, N1 - 1, s.tau, Fr::one(), 1, ct)));
                 G16_TRY((contribute_array<C, 1>(*env, w, chunk, run, io->tau_g2 + W2, N2 - 1, s.tau, Fr::one(), 1, ct)));
@@ -391,27 +377,6 @@ int srs_contribute_any(const CeremonyEnv* env, const uint64_t* tau_, const uint6
 }
 
 // ---- the check of a contribution ----------------------------------------------------------------------------------------------
-namespace {
-template <class C>
-int pairs_equal(const typename C::G1A& a, const typename C::G2A& b, const typename C::G1A& c, const typename C::G2A& d, bool* equal) {
-    typedef Pairing<C> PP;
-    const typename C::G1A g1s[2] = {a, c.neg()};
-    const typename C::G2A g2s[2] = {b, d};
-    typename PP::F12 e;
-    *equal = host_pairing_product<C>(reinterpret_cast<const uint64_t*>(g1s), reinterpret_cast<const uint64_t*>(g2s), 2, e) &&
-             PP::equal(e, PP::F12::one());
-    return G16_OK;
-}
-template <class C> uint32_t bad_reason(const typename C::G1A& p) {
-    const uint8_t f = Subgroup<C>::g1_flag(p);
-    return f == 2 ? 2u : f == 0 ? 3u : p.is_identity() ? 4u : 0u;
-}
-template <class C> uint32_t bad_reason(const typename C::G2A& p) {
-    const uint8_t f = Subgroup<C>::g2_flag(p);
-    return f == 2 ? 2u : f == 0 ? 3u : p.is_identity() ? 4u : 0u;
-}
-}  // namespace
-
 template <class C>
 int srs_check_contribution_any(g16_ctx* ctx, const g16_srs_view* before, const g16_srs_view* after, const g16_tau_contribution* pub,
                                const uint64_t* coeffs, uint64_t n_coeffs, g16_ceremony_info* info) {
@@ -427,16 +392,16 @@ int srs_check_contribution_any(g16_ctx* ctx, const g16_srs_view* before, const g
     const G2A b_g2 = ld_any<G2A>(before->tau_g2);
     auto bad = [&](uint32_t array, uint64_t index, uint32_t reason) {
         *info = g16_ceremony_info{};
-        info->flags = G16_TAU_BAD_POINT; info->bad_array = array; info->bad_index = index; info->bad_reason = reason;
+        decode_bad(bad_key(array, index, reason), G16_TAU_BAD_POINT, info);
         return G16_OK;
     };
     for (uint32_t k = 0; k < 3; ++k)
-        if (const uint32_t r = bad_reason<C>(p2[k])) return bad(5 + k, 0, r);
-    if (const uint32_t r = bad_reason<C>(b_g1)) return bad(8, 0, r);
-    if (const uint32_t r = bad_reason<C>(b_tau1)) return bad(8, 1, r);
-    if (const uint32_t r = bad_reason<C>(b_g2)) return bad(8, 2, r);
-    if (const uint32_t r = bad_reason<C>(b_alpha)) return bad(8, 3, r);
-    if (const uint32_t r = bad_reason<C>(b_beta)) return bad(8, 4, r);
+        if (const uint32_t r = point_reason<C, 1>(p2[k], false)) return bad(5 + k, 0, r);
+    if (const uint32_t r = point_reason<C, 0>(b_g1, false)) return bad(8, 0, r);
+    if (const uint32_t r = point_reason<C, 0>(b_tau1, false)) return bad(8, 1, r);
+    if (const uint32_t r = point_reason<C, 1>(b_g2, false)) return bad(8, 2, r);
+    if (const uint32_t r = point_reason<C, 0>(b_alpha, false)) return bad(8, 3, r);
+    if (const uint32_t r = point_reason<C, 0>(b_beta, false)) return bad(8, 4, r);
     uint32_t flags = info->flags;
     if (before->n_tau_g1 != after->n_tau_g1 || before->n_tau_g2 != after->n_tau_g2 || before->n_alpha_beta != after->n_alpha_beta ||
         memcmp(before->tau_g1, after->tau_g1, sizeof(G1A)) != 0 || memcmp(before->tau_g2, after->tau_g2, sizeof(G2A)) != 0)
@@ -461,7 +426,7 @@ int unit_args(int g2, const uint64_t* points, const uint64_t* scalars, uint64_t 
 }
 int contribute_args(const uint64_t* tau, const uint64_t* alpha, const uint64_t* beta, const g16_srs_view* io, const g16_tau_contribution* pub) {
     if (!tau || !alpha || !beta || !io || !pub || !pub->tau_g2 || !pub->alpha_g2 || !pub->beta_g2) return G16_ERR_BAD_ARG;
-    if (!io->tau_g1 || !io->tau_g2 || !io->alpha_tau_g1 || !io->beta_tau_g1 || !io->beta_g2) return G16_ERR_BAD_ARG;
+    if (!srs_view_ok(io)) return G16_ERR_BAD_ARG;
     if (io->n_tau_g1 < 1 || io->n_tau_g2 < 1) return G16_ERR_BAD_LENGTH;
     if (io->n_tau_g1 >= ((uint64_t)1 << 31) || io->n_tau_g2 >= ((uint64_t)1 << 31) || io->n_alpha_beta >= ((uint64_t)1 << 31)) return G16_ERR_BAD_LENGTH;
     return G16_OK;
@@ -488,7 +453,7 @@ int g16_batch_scalar_mul(g16_ctx* ctx, int g2, const uint64_t* points, const uin
     CeremonyEnv env;
     int curve = -1;
     G16_TRY(ceremony_enter(ctx, &env, &curve));
-    g16_phase1_timings* tm = reinterpret_cast<g16_phase1_timings*>(phase1_stage_ms(ctx));
+    g16_phase1_timings* tm = Stages::of(phase1_stage_ms(ctx));
     *tm = g16_phase1_timings{};
     G16_VERIFY_DISPATCH(curve, (batch_scalar_mul_any<CC>(&env, g2, points, scalars, n, out, tm)));
 }
@@ -510,7 +475,7 @@ int g16_srs_contribute(g16_ctx* ctx, const uint64_t tau[4], const uint64_t alpha
     CeremonyEnv env;
     int curve = -1;
     G16_TRY(ceremony_enter(ctx, &env, &curve));
-    g16_phase1_timings* kept = reinterpret_cast<g16_phase1_timings*>(phase1_stage_ms(ctx));
+    g16_phase1_timings* kept = Stages::of(phase1_stage_ms(ctx));
     *kept = g16_phase1_timings{};
     int rc = G16_ERR_BAD_ARG;
     try {
@@ -531,10 +496,7 @@ int g16_host_srs_contribute(int curve, const uint64_t tau[4], const uint64_t alp
 }
 
 int g16_phase1_get_timings(g16_ctx* ctx, g16_phase1_timings* out) {
-    const double* ms = phase1_stage_ms(ctx);
-    if (!ms || !out) return G16_ERR_BAD_ARG;
-    memcpy(out, ms, sizeof(*out));
-    return G16_OK;
+    return Stages::get(phase1_stage_ms(ctx), out);
 }
 
 int g16_srs_check_contribution(g16_ctx* ctx, const g16_srs_view* before, const g16_srs_view* after, const g16_tau_contribution* pub,
