@@ -29,6 +29,11 @@ Reference interface mirrored (paths relative to /root/reference):
                                                     no counterpart in the reference (snarkjs' `zkey verify` without re-deriving the key;
       libg16_keycheck.so): random linear combinations pushed through the matrices and the scalar transform onto the SRS -- the
       prover's row walk, transforms and MSMs, no transform over the group (host twins: check_key_derivation_host, fold_key_from_srs_host)
+  Groth16.prepare_srs / generate_parameters_from_lagrange / group_ntt_windowed / lagrange_timings, LagrangeSRS (save / load)
+                                                    no counterpart in the reference (snarkjs' `powersoftau prepare phase2`; libg16_lagrange.so):
+      the Lagrange form of an SRS made once per domain, every circuit's key from it by the sparse products alone; the transforms on
+      phase 1's windowed scalar multiplication (host twins: prepare_srs_host, generate_parameters_from_lagrange_host,
+      group_ntt_windowed_host)
   rerandomize_proof / Groth16.rerandomize_proof      src/prover.rs:223-250 (host: three scalar multiplications)
   Groth16.create_proof_with_reduction / prove / setup src/prover.rs:173-217, src/lib.rs:63-82, src/generator.rs:20-45 -- host-side
       synthesis (groth16_amd.r1cs: ConstraintSystem, Variable, lc, ConstraintSynthesizer) in front of the GPU calls
@@ -45,7 +50,8 @@ from .groth16 import (CheckResult, CircomReduction, ConstraintMatrices, DevicePr
                       host_check_assignment, rerandomize_proof, shard_ranges, SRS, group_ntt_host, generate_parameters_from_srs_host,
                       BadSRS, CeremonyResult, rlc_plan, rlc_sums_host, check_srs_host, check_delta_contribution_host,
                       TauContribution, batch_scalar_mul_host, contribute_tau_host, check_tau_contribution_host,
-                      check_key_derivation_host, fold_key_from_srs_host)
+                      check_key_derivation_host, fold_key_from_srs_host,
+                      LagrangeSRS, group_ntt_windowed_host, prepare_srs_host, generate_parameters_from_lagrange_host)
 from .binding import InvalidData, MalformedVerifyingKey, Unsatisfiable  # noqa: F401
 from .verifier import (PreparedVerifyingKey, VerifyingKey, check_subgroups_host, decompress_points_host, host_pairing, verify_proof_host,  # noqa: F401
                        verify_proofs_aggregate_host, verify_proofs_aggregate_mixed_host, decode_points_host)
@@ -60,4 +66,5 @@ __all__ = [
     "BadSRS", "CeremonyResult", "rlc_plan", "rlc_sums_host", "check_srs_host", "check_delta_contribution_host",
     "TauContribution", "batch_scalar_mul_host", "contribute_tau_host", "check_tau_contribution_host",
     "check_key_derivation_host", "fold_key_from_srs_host",
+    "LagrangeSRS", "group_ntt_windowed_host", "prepare_srs_host", "generate_parameters_from_lagrange_host",
 ]

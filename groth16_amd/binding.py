@@ -150,6 +150,20 @@ class KeycheckTimingsC(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class LagrangeSrsViewC(C.Structure):
+    """g16_lagrange_srs_view"""
+    _fields_ = [(n, u64p) for n in ("u_g1", "alpha_u_g1", "beta_u_g1", "u_g2", "h_g1", "tau_g1_0", "alpha_g1_0", "beta_g1_0", "tau_g2_0", "beta_g2")] + \
+               [("log_n", C.c_int32), ("qap", C.c_int32)]
+
+
+class LagrangeTimingsC(C.Structure):
+    """g16_lagrange_timings"""
+    _fields_ = [(n, C.c_double) for n in ("u_g1_ms", "alpha_u_g1_ms", "beta_u_g1_ms", "u_g2_ms", "h_ms", "products_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class VkViewC(C.Structure):
     _fields_ = [(n, u64p) for n in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1")] + [("n_gamma_abc", C.c_uint64)]
 
@@ -258,6 +272,11 @@ KEYCHECK_EXPORTS = [
     "g16_params_check_derivation", "g16_key_fold_from_srs", "g16_keycheck_get_timings", "g16_host_params_check_derivation",
     "g16_host_key_fold_from_srs",
 ]
+# libg16_lagrange.so, the companion library of the Lagrange form of an SRS and the key from it (include/g16_lagrange.h)
+LAGRANGE_EXPORTS = [
+    "g16_group_ntt_windowed", "g16_host_group_ntt_windowed", "g16_srs_lagrange", "g16_host_srs_lagrange", "g16_generate_parameters_lagrange",
+    "g16_host_generate_parameters_lagrange", "g16_lagrange_get_timings",
+]
 
 
 def ptr64(a: Optional[np.ndarray]):
@@ -305,6 +324,17 @@ def _keycheck_argtypes(c):
     c.g16_keycheck_get_timings.argtypes = [C.c_void_p, C.POINTER(KeycheckTimingsC)]
 
 
+def _lagrange_argtypes(c):
+    c.g16_group_ntt_windowed.argtypes = [C.c_void_p, C.c_int, u64p, C.c_int, C.c_int, u64p]
+    c.g16_host_group_ntt_windowed.argtypes = [C.c_int, C.c_int, u64p, C.c_int, C.c_int, u64p]
+    c.g16_srs_lagrange.argtypes = [C.c_void_p, C.POINTER(SrsViewC), C.c_int, C.c_int, C.POINTER(LagrangeSrsViewC)]
+    c.g16_host_srs_lagrange.argtypes = [C.c_int] + c.g16_srs_lagrange.argtypes[1:]
+    c.g16_generate_parameters_lagrange.argtypes = [C.c_void_p, C.POINTER(CsrViewC), C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(LagrangeSrsViewC),
+                                                   C.POINTER(ParamsViewC)]
+    c.g16_host_generate_parameters_lagrange.argtypes = [C.c_int] + c.g16_generate_parameters_lagrange.argtypes[1:]
+    c.g16_lagrange_get_timings.argtypes = [C.c_void_p, C.POINTER(LagrangeTimingsC)]
+
+
 class Lib:
     def __init__(self, path: str = LIB_PATH):
         if not os.path.exists(path):
@@ -312,7 +342,7 @@ class Lib:
                 f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  groth16_amd has no CPU fallback.")
         self.path = path
-        self._companions = {}   # file name -> the loaded companion library (cer, ph1, kc)
+        self._companions = {}   # file name -> the loaded companion library (cer, ph1, kc, lag)
         # One HIP runtime per process: torch wheels bundle their own libamdhip64, and this library links the system one.  Whichever is
         # loaded first serves both (same soname); loaded in the order library -> torch, g16_ctx_create found no device on the GPU box
         # (round 3: `python __graft_entry__.py smoke`, where build() loads the library before smoke() imports torch).  So when torch is
@@ -485,6 +515,11 @@ class Lib:
     def kc(self):
         """libg16_keycheck.so (it links against the library and its two other companions)"""
         return self._companion("libg16_keycheck.so", _keycheck_argtypes)
+
+    @property
+    def lag(self):
+        """libg16_lagrange.so (it links against the library and its three other companions)"""
+        return self._companion("libg16_lagrange.so", _lagrange_argtypes)
 
     def check(self, status: int, check_result: "Optional[CheckResultC]" = None, pk_bytes_info: "Optional[PkBytesInfoC]" = None):
         """check_result: the g16_check_result a checked call filled, carried by Unsatisfiable; pk_bytes_info: the g16_pk_bytes_info

@@ -78,6 +78,7 @@ int ceremony_enter(g16_ctx* ctx, CeremonyEnv* env, int* curve) {
 const double* ceremony_stage_ms(const g16_ctx* ctx) { return !ctx ? nullptr : ctx->subs.empty() ? ctx->ceremony_ms : ctx->subs[0]->ceremony_ms; }
 double* phase1_stage_ms(g16_ctx* ctx) { return !ctx ? nullptr : ctx->subs.empty() ? ctx->phase1_ms : ctx->subs[0]->phase1_ms; }
 double* keycheck_stage_ms(g16_ctx* ctx) { return !ctx ? nullptr : ctx->subs.empty() ? ctx->keycheck_ms : ctx->subs[0]->keycheck_ms; }
+double* lagrange_stage_ms(g16_ctx* ctx) { return !ctx ? nullptr : ctx->subs.empty() ? ctx->lagrange_ms : ctx->subs[0]->lagrange_ms; }
 void set_last_error_text(const char* text) { g_last_error = text; }
 }  // namespace g16
 

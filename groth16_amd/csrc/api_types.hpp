@@ -131,6 +131,7 @@ struct g16_ctx {
     double ceremony_ms[6] = {};   // the stage times of the companion library's last call on this context (ceremony.hpp)
     double phase1_ms[5] = {};     // the same for libg16_phase1.so: upload, powers, multiplications G1, multiplications G2, download
     double keycheck_ms[10] = {};  // the same for libg16_keycheck.so: g16_keycheck_timings, eight stage times and the Fr plan's c and W
+    double lagrange_ms[6] = {};   // the same for libg16_lagrange.so: g16_lagrange_timings, the four arrays, the h basis, the products
     EventTimer t_wm, t_prep_h, t_prep_z, t_bucket[5], t_ntt[2];
     hipEvent_t ev_z = nullptr, ev_h = nullptr, ev_wm = nullptr, ev_done[5] = {};
     // g16_prove_finalize_prepare: the (r, s)-only half of the host glue, running on a host thread (api.hip: FinalizePrep)

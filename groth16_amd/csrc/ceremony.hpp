@@ -17,6 +17,7 @@ int ceremony_enter(g16_ctx* ctx, CeremonyEnv* env, int* curve);
 const double* ceremony_stage_ms(const g16_ctx* ctx);
 double* phase1_stage_ms(g16_ctx* ctx);      // [5]: the stage times of libg16_phase1.so's last call (kept in the context)
 double* keycheck_stage_ms(g16_ctx* ctx);    // [10]: g16_keycheck_timings of libg16_keycheck.so's last call (kept in the context)
+double* lagrange_stage_ms(g16_ctx* ctx);    // [6]: g16_lagrange_timings of libg16_lagrange.so's last call (kept in the context)
 void set_last_error_text(const char* text);   // what g16_last_error returns next on this thread
 
 }  // namespace g16

@@ -24,6 +24,10 @@
 //   4. A delta contribution: delta_g1, delta_g2 <- delta (.) (two points: host), l_query and h_query <- delta^-1 (.)
 //      (srs_scale_kernel: every lane shares the scalar, so its bits steer the whole wave the same way).
 //
+// The derivation is cut where the Lagrange points and the h points are complete: plan_queries (host: transposition, segment plans) and
+// run_queries_device / queries_host are step 2 as pieces of their own, so that libg16_lagrange.so (lagrange.hip) can
+// run them on Lagrange points that were made once and kept (srs_queries_device / srs_queries_host in srs_setup.hpp).
+//
 // Affine Montgomery coordinates are canonical: the key equals generate_parameters_with_qap(alpha, beta, 1, delta, t = tau) bit for bit
 // however the sums were grouped.  The *_host functions run the same butterflies and the same sums in plain host C++ (no GPU).
 #include "srs_setup.hpp"
@@ -432,6 +436,95 @@ struct Srs {
         memcpy(out->gamma_g2, srs->tau_g2, sizeof(Affine<Fq2>));        // gamma = 1
     }
 
+    // ---- the tail of the derivation: the queries from complete Lagrange points ------------------------------------------------------
+    // (generate_device runs it after its transforms; srs_queries_device below runs it on Lagrange points that were made earlier)
+    struct SrsQueries {
+        SrsCsc csc[3];   // a_query; b_g1_query and b_g2_query; gamma_abc_g1 | l_query over [u | alpha u | beta u]
+        SrsPlan pl[3];
+        uint64_t nnz[3], voff[3], one_val;
+    };
+    // host: the transposition and the segment plans over a domain of n points
+    static int plan_queries(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, uint64_t n, SrsQueries* q) {
+        if (3 * n + ni >= ((uint64_t)1 << 32)) return G16_ERR_DEGREE_TOO_LARGE;   // point indices are 32 bits wide
+        for (int m = 0; m < 3; ++m) q->nnz[m] = abc[m].row_ptr[nc] - abc[m].row_ptr[0];
+        q->voff[0] = 0; q->voff[1] = q->nnz[0]; q->voff[2] = q->nnz[0] + q->nnz[1];
+        q->one_val = q->nnz[0] + q->nnz[1] + q->nnz[2];
+        if (q->one_val >= ((uint64_t)1 << 32) - 1) return G16_ERR_BAD_LENGTH;
+        const g16_csr_view* ma[1] = {&abc[0]};
+        const g16_csr_view* mb[1] = {&abc[1]};
+        const g16_csr_view* mm[3] = {&abc[0], &abc[1], &abc[2]};
+        const uint64_t p0[1] = {0}, pm[3] = {2 * n, n, 0};
+        G16_TRY(transpose(ma, p0, &q->voff[0], 1, nc, nv, true, ni, nc, q->one_val, &q->csc[0]));
+        G16_TRY(transpose(mb, p0, &q->voff[1], 1, nc, nv, false, ni, 0, q->one_val, &q->csc[1]));
+        G16_TRY(transpose(mm, pm, q->voff, 3, nc, nv, true, ni, 2 * n + nc, q->one_val, &q->csc[2]));
+        for (int k = 0; k < 3; ++k) plan(q->csc[k].col_ptr, &q->pl[k]);
+        return G16_OK;
+    }
+    // device: the coefficients and the plans into the arena (on top of what the caller holds there), the column sums, the copies out.
+    // d_u1: u | alpha u | beta u, 3n points; d_u2: n points.  The uploads read q and abc: the caller waits for the stream before
+    // either goes away
+    static int run_queries_device(hipStream_t st, Arena& arena, const SrsQueries& q, const g16_csr_view abc[3], uint64_t ni, uint64_t nv,
+                                  const Affine<Fq>* d_u1, const Affine<Fq2>* d_u2, const g16_params_view* out, EventTimer& tm) {
+        typedef Affine<Fq> A1;
+        typedef Affine<Fq2> A2;
+        Fr* d_vals = nullptr;
+        A1* d_q1 = nullptr;
+        A2* d_q2 = nullptr;
+        G16_TRY(arena.alloc_n(q.one_val + 1, &d_vals));
+        for (int m = 0; m < 3; ++m)
+            if (q.nnz[m])
+                G16_HIP_TRY(hipMemcpyAsync(d_vals + q.voff[m], abc[m].val + 4 * abc[m].row_ptr[0], q.nnz[m] * sizeof(Fr), hipMemcpyHostToDevice, st));
+        const Fr one = Fr::one();
+        G16_HIP_TRY(hipMemcpyAsync(d_vals + q.one_val, &one, sizeof(Fr), hipMemcpyHostToDevice, st));
+        DevPlan dp[3];
+        uint64_t t0 = 1, t1 = 1;
+        for (int k = 0; k < 3; ++k) {
+            G16_TRY(upload_plan(q.csc[k], q.pl[k], arena, st, &dp[k]));
+            t0 = std::max<uint64_t>(t0, dp[k].n_tasks[0]);
+            if (dp[k].n_tasks.size() > 1) t1 = std::max<uint64_t>(t1, dp[k].n_tasks[1]);
+        }
+        XYZZ<Fq>*pa1 = nullptr, *pb1 = nullptr;
+        XYZZ<Fq2>*pa2 = nullptr, *pb2 = nullptr;
+        G16_TRY(arena.alloc_n(t0, &pa1));
+        G16_TRY(arena.alloc_n(t1, &pb1));
+        G16_TRY(arena.alloc_n(t0, &pa2));
+        G16_TRY(arena.alloc_n(t1, &pb2));
+        G16_TRY(arena.alloc_n(nv, &d_q1));
+        G16_TRY(arena.alloc_n(nv, &d_q2));
+        G16_TRY(tm.start(st));
+        G16_TRY(col_sums<Fq>(dp[0], d_u1, d_vals, pa1, pb1, d_q1, st));
+        G16_HIP_TRY(hipMemcpyAsync(out->a_query, d_q1, nv * sizeof(A1), hipMemcpyDeviceToHost, st));
+        G16_TRY(col_sums<Fq>(dp[1], d_u1, d_vals, pa1, pb1, d_q1, st));
+        G16_HIP_TRY(hipMemcpyAsync(out->b_g1_query, d_q1, nv * sizeof(A1), hipMemcpyDeviceToHost, st));
+        G16_TRY(col_sums<Fq2>(dp[1], d_u2, d_vals, pa2, pb2, d_q2, st));
+        G16_HIP_TRY(hipMemcpyAsync(out->b_g2_query, d_q2, nv * sizeof(A2), hipMemcpyDeviceToHost, st));
+        G16_TRY(col_sums<Fq>(dp[2], d_u1, d_vals, pa1, pb1, d_q1, st));
+        G16_HIP_TRY(hipMemcpyAsync(out->gamma_abc_g1, d_q1, ni * sizeof(A1), hipMemcpyDeviceToHost, st));
+        if (nv > ni) G16_HIP_TRY(hipMemcpyAsync(out->l_query, d_q1 + ni, (nv - ni) * sizeof(A1), hipMemcpyDeviceToHost, st));
+        G16_TRY(tm.stop(st));
+        return G16_OK;
+    }
+    // the tail as a call of its own: the matrices are checked, d_u1 / d_u2 are the caller's (in `arena`, which is not reset here), the
+    // fixed points come from index 0 of `fixed`'s arrays.  Returns after the stream has drained
+    static int queries_device(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int log_n,
+                              const uint64_t* d_u1, const uint64_t* d_u2, const g16_srs_view* fixed, const g16_params_view* out, double* products_ms) {
+        G16_TRY(check_matrices(abc, nc));
+        SrsQueries q;
+        G16_TRY(plan_queries(abc, ni, nc, nv, (uint64_t)1 << log_n, &q));
+        EventTimer tm;
+        const int rc = run_queries_device(st, arena, q, abc, ni, nv, reinterpret_cast<const Affine<Fq>*>(d_u1), reinterpret_cast<const Affine<Fq2>*>(d_u2),
+                                          out, tm);
+        const hipError_t se = hipStreamSynchronize(st);
+        if (rc == G16_OK && se == hipSuccess) {
+            if (products_ms) *products_ms = tm.ms();
+            copy_fixed(fixed, out);
+        }
+        tm.destroy();
+        if (rc != G16_OK) return rc;
+        G16_HIP_TRY(se);
+        return G16_OK;
+    }
+
     static int generate_device(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int qap,
                                const g16_srs_view* srs, const g16_params_view* out, double phase_ms[3]) {
         typedef Affine<Fq> A1;
@@ -440,24 +533,9 @@ struct Srs {
         G16_TRY(srs_domain_log<C>(ni, nc, nv, qap, &log_n));
         G16_TRY(check_matrices(abc, nc));
         const uint64_t n = (uint64_t)1 << log_n;
-        if (3 * n + ni >= ((uint64_t)1 << 32)) return G16_ERR_DEGREE_TOO_LARGE;   // point indices are 32 bits wide
         const bool circom = qap == G16_QAP_CIRCOM;
-        // transposed matrices and their segment plans
-        const uint64_t nnz[3] = {abc[0].row_ptr[nc] - abc[0].row_ptr[0], abc[1].row_ptr[nc] - abc[1].row_ptr[0], abc[2].row_ptr[nc] - abc[2].row_ptr[0]};
-        const uint64_t voff[3] = {0, nnz[0], nnz[0] + nnz[1]}, one_val = nnz[0] + nnz[1] + nnz[2];
-        if (one_val >= ((uint64_t)1 << 32) - 1) return G16_ERR_BAD_LENGTH;
-        SrsCsc csc[3];   // a_query; b_g1_query and b_g2_query; gamma_abc_g1 | l_query over [u | alpha u | beta u]
-        SrsPlan pl[3];
-        {
-            const g16_csr_view* ma[1] = {&abc[0]};
-            const g16_csr_view* mb[1] = {&abc[1]};
-            const g16_csr_view* mm[3] = {&abc[0], &abc[1], &abc[2]};
-            const uint64_t p0[1] = {0}, pm[3] = {2 * n, n, 0};
-            G16_TRY(transpose(ma, p0, &voff[0], 1, nc, nv, true, ni, nc, one_val, &csc[0]));
-            G16_TRY(transpose(mb, p0, &voff[1], 1, nc, nv, false, ni, 0, one_val, &csc[1]));
-            G16_TRY(transpose(mm, pm, voff, 3, nc, nv, true, ni, 2 * n + nc, one_val, &csc[2]));
-            for (int k = 0; k < 3; ++k) plan(csc[k].col_ptr, &pl[k]);
-        }
+        SrsQueries q;   // transposed matrices and their segment plans: before any device work, so that a bad matrix is refused at once
+        G16_TRY(plan_queries(abc, ni, nc, nv, n, &q));
         // inverse twiddles: w^-e, e < n / 2 -- or rho^-e, e < n, of the 2n-point domain (w = rho^2: the n-point stages read every other one)
         const Fr root = root_of(log_n + (circom ? 1 : 0));
         const std::vector<Fr> tw = power_table(root.inverse(), circom ? n : n / 2);
@@ -466,9 +544,9 @@ struct Srs {
         arena.reset();
         EventTimer tm[3];
         auto body = [&]() -> int {
-            Fr *d_tw = nullptr, *d_vals = nullptr;
-            A1 *d_tau1 = nullptr, *d_in1 = nullptr, *d_u1 = nullptr, *d_q1 = nullptr;
-            A2 *d_tau2 = nullptr, *d_u2 = nullptr, *d_q2 = nullptr;
+            Fr* d_tw = nullptr;
+            A1 *d_tau1 = nullptr, *d_in1 = nullptr, *d_u1 = nullptr;
+            A2 *d_tau2 = nullptr, *d_u2 = nullptr;
             XYZZ<Fq>* work1 = nullptr;
             XYZZ<Fq2>* work2 = nullptr;
             const uint64_t n_tau = 2 * n - 1, n_h = circom ? n : n - 1;
@@ -512,38 +590,7 @@ struct Srs {
             if (n_h) G16_HIP_TRY(hipMemcpyAsync(out->h_query, d_h, n_h * sizeof(A1), hipMemcpyDeviceToHost, st));
             G16_TRY(tm[2].stop(st));
             // 2. the queries
-            G16_TRY(arena.alloc_n(one_val + 1, &d_vals));
-            for (int m = 0; m < 3; ++m)
-                if (nnz[m])
-                    G16_HIP_TRY(hipMemcpyAsync(d_vals + voff[m], abc[m].val + 4 * abc[m].row_ptr[0], nnz[m] * sizeof(Fr), hipMemcpyHostToDevice, st));
-            const Fr one = Fr::one();
-            G16_HIP_TRY(hipMemcpyAsync(d_vals + one_val, &one, sizeof(Fr), hipMemcpyHostToDevice, st));
-            DevPlan dp[3];
-            uint64_t t0 = 1, t1 = 1;
-            for (int k = 0; k < 3; ++k) {
-                G16_TRY(upload_plan(csc[k], pl[k], arena, st, &dp[k]));
-                t0 = std::max<uint64_t>(t0, dp[k].n_tasks[0]);
-                if (dp[k].n_tasks.size() > 1) t1 = std::max<uint64_t>(t1, dp[k].n_tasks[1]);
-            }
-            XYZZ<Fq>*pa1 = nullptr, *pb1 = nullptr;
-            XYZZ<Fq2>*pa2 = nullptr, *pb2 = nullptr;
-            G16_TRY(arena.alloc_n(t0, &pa1));
-            G16_TRY(arena.alloc_n(t1, &pb1));
-            G16_TRY(arena.alloc_n(t0, &pa2));
-            G16_TRY(arena.alloc_n(t1, &pb2));
-            G16_TRY(arena.alloc_n(nv, &d_q1));
-            G16_TRY(arena.alloc_n(nv, &d_q2));
-            G16_TRY(tm[1].start(st));
-            G16_TRY(col_sums<Fq>(dp[0], d_u1, d_vals, pa1, pb1, d_q1, st));
-            G16_HIP_TRY(hipMemcpyAsync(out->a_query, d_q1, nv * sizeof(A1), hipMemcpyDeviceToHost, st));
-            G16_TRY(col_sums<Fq>(dp[1], d_u1, d_vals, pa1, pb1, d_q1, st));
-            G16_HIP_TRY(hipMemcpyAsync(out->b_g1_query, d_q1, nv * sizeof(A1), hipMemcpyDeviceToHost, st));
-            G16_TRY(col_sums<Fq2>(dp[1], d_u2, d_vals, pa2, pb2, d_q2, st));
-            G16_HIP_TRY(hipMemcpyAsync(out->b_g2_query, d_q2, nv * sizeof(A2), hipMemcpyDeviceToHost, st));
-            G16_TRY(col_sums<Fq>(dp[2], d_u1, d_vals, pa1, pb1, d_q1, st));
-            G16_HIP_TRY(hipMemcpyAsync(out->gamma_abc_g1, d_q1, ni * sizeof(A1), hipMemcpyDeviceToHost, st));
-            if (nv > ni) G16_HIP_TRY(hipMemcpyAsync(out->l_query, d_q1 + ni, (nv - ni) * sizeof(A1), hipMemcpyDeviceToHost, st));
-            G16_TRY(tm[1].stop(st));
+            G16_TRY(run_queries_device(st, arena, q, abc, ni, nv, d_u1, d_u2, out, tm[1]));
             return G16_OK;
         };
         const int rc = body();
@@ -577,6 +624,35 @@ struct Srs {
         for (uint64_t j = lo; j < hi; ++j) o[j - lo] = acc[j].to_affine();
     }
 
+    // the tail on the host: the queries from complete Lagrange points (n points each), in the matrices' row order
+    static int queries_host(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, const Affine<Fq>* u, const Affine<Fq>* au,
+                            const Affine<Fq>* bu, const Affine<Fq2>* u2, const g16_params_view* out) {
+        {
+            std::vector<XYZZ<Fq>> a(nv, XYZZ<Fq>::identity());
+            for (uint64_t j = 0; j < ni; ++j) a[j] = XYZZ<Fq>::from_affine(u[nc + j]);
+            G16_TRY(accumulate_host<Fq>(abc[0], nc, nv, u, a));
+            store_host<Fq>(a, 0, nv, out->a_query);
+        }
+        {
+            std::vector<XYZZ<Fq>> b(nv, XYZZ<Fq>::identity());
+            G16_TRY(accumulate_host<Fq>(abc[1], nc, nv, u, b));
+            store_host<Fq>(b, 0, nv, out->b_g1_query);
+            std::vector<XYZZ<Fq2>> b2(nv, XYZZ<Fq2>::identity());
+            G16_TRY(accumulate_host<Fq2>(abc[1], nc, nv, u2, b2));
+            store_host<Fq2>(b2, 0, nv, out->b_g2_query);
+        }
+        {
+            std::vector<XYZZ<Fq>> m(nv, XYZZ<Fq>::identity());
+            for (uint64_t j = 0; j < ni; ++j) m[j] = XYZZ<Fq>::from_affine(bu[nc + j]);
+            G16_TRY(accumulate_host<Fq>(abc[0], nc, nv, bu, m));
+            G16_TRY(accumulate_host<Fq>(abc[1], nc, nv, au, m));
+            G16_TRY(accumulate_host<Fq>(abc[2], nc, nv, u, m));
+            store_host<Fq>(m, 0, ni, out->gamma_abc_g1);
+            store_host<Fq>(m, ni, nv, out->l_query);
+        }
+        return G16_OK;
+    }
+
     static int generate_host(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int qap, const g16_srs_view* srs,
                              const g16_params_view* out) {
         typedef Affine<Fq> A1;
@@ -596,29 +672,7 @@ struct Srs {
         lagrange_host<Fq>(reinterpret_cast<const A1*>(srs->alpha_tau_g1), log_n, tw.data(), tw_extra, au.data());
         lagrange_host<Fq>(reinterpret_cast<const A1*>(srs->beta_tau_g1), log_n, tw.data(), tw_extra, bu.data());
         lagrange_host<Fq2>(reinterpret_cast<const A2*>(srs->tau_g2), log_n, tw.data(), tw_extra, u2.data());
-        {
-            std::vector<XYZZ<Fq>> a(nv, XYZZ<Fq>::identity());
-            for (uint64_t j = 0; j < ni; ++j) a[j] = XYZZ<Fq>::from_affine(u[nc + j]);
-            G16_TRY(accumulate_host<Fq>(abc[0], nc, nv, u.data(), a));
-            store_host<Fq>(a, 0, nv, out->a_query);
-        }
-        {
-            std::vector<XYZZ<Fq>> b(nv, XYZZ<Fq>::identity());
-            G16_TRY(accumulate_host<Fq>(abc[1], nc, nv, u.data(), b));
-            store_host<Fq>(b, 0, nv, out->b_g1_query);
-            std::vector<XYZZ<Fq2>> b2(nv, XYZZ<Fq2>::identity());
-            G16_TRY(accumulate_host<Fq2>(abc[1], nc, nv, u2.data(), b2));
-            store_host<Fq2>(b2, 0, nv, out->b_g2_query);
-        }
-        {
-            std::vector<XYZZ<Fq>> m(nv, XYZZ<Fq>::identity());
-            for (uint64_t j = 0; j < ni; ++j) m[j] = XYZZ<Fq>::from_affine(bu[nc + j]);
-            G16_TRY(accumulate_host<Fq>(abc[0], nc, nv, bu.data(), m));
-            G16_TRY(accumulate_host<Fq>(abc[1], nc, nv, au.data(), m));
-            G16_TRY(accumulate_host<Fq>(abc[2], nc, nv, u.data(), m));
-            store_host<Fq>(m, 0, ni, out->gamma_abc_g1);
-            store_host<Fq>(m, ni, nv, out->l_query);
-        }
+        G16_TRY(queries_host(abc, ni, nc, nv, u.data(), au.data(), bu.data(), u2.data(), out));
         A1* h = reinterpret_cast<A1*>(out->h_query);
         if (!circom) {
             for (uint64_t i = 0; i + 1 < n; ++i) {
@@ -735,6 +789,21 @@ int srs_generate_host(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint6
     return Srs<C>::generate_host(abc, ni, nc, nv, qap, srs, out);
 }
 template <class C>
+int srs_queries_device(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int log_n, const uint64_t* d_lag_g1,
+                       const uint64_t* d_lag_g2, const g16_srs_view* fixed, const g16_params_view* out, double* products_ms) {
+    return Srs<C>::queries_device(st, arena, abc, ni, nc, nv, log_n, d_lag_g1, d_lag_g2, fixed, out, products_ms);
+}
+template <class C>
+int srs_queries_host(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, const uint64_t* u, const uint64_t* alpha_u, const uint64_t* beta_u,
+                     const uint64_t* u_g2, const g16_srs_view* fixed, const g16_params_view* out) {
+    typedef Affine<typename C::Fq> A1;
+    G16_TRY(Srs<C>::check_matrices(abc, nc));
+    G16_TRY(Srs<C>::queries_host(abc, ni, nc, nv, reinterpret_cast<const A1*>(u), reinterpret_cast<const A1*>(alpha_u), reinterpret_cast<const A1*>(beta_u),
+                                 reinterpret_cast<const Affine<typename C::Fq2>*>(u_g2), out));
+    Srs<C>::copy_fixed(fixed, out);
+    return G16_OK;
+}
+template <class C>
 int srs_apply_delta_device(hipStream_t st, Arena& arena, const uint64_t* delta, const g16_params_view* inout, uint64_t n_l, uint64_t n_h,
                            double* delta_ms) {
     return Srs<C>::apply_delta_device(st, arena, delta, inout, n_l, n_h, delta_ms);
@@ -747,6 +816,10 @@ int srs_apply_delta_device(hipStream_t st, Arena& arena, const uint64_t* delta, 
     template int srs_generate_device<C>(hipStream_t, Arena&, const g16_csr_view*, uint64_t, uint64_t, uint64_t, int, const g16_srs_view*,  \
                                         const g16_params_view*, double*);                                                                  \
     template int srs_generate_host<C>(const g16_csr_view*, uint64_t, uint64_t, uint64_t, int, const g16_srs_view*, const g16_params_view*); \
+    template int srs_queries_device<C>(hipStream_t, Arena&, const g16_csr_view*, uint64_t, uint64_t, uint64_t, int, const uint64_t*,      \
+                                       const uint64_t*, const g16_srs_view*, const g16_params_view*, double*);                             \
+    template int srs_queries_host<C>(const g16_csr_view*, uint64_t, uint64_t, uint64_t, const uint64_t*, const uint64_t*, const uint64_t*,  \
+                                     const uint64_t*, const g16_srs_view*, const g16_params_view*);                                        \
     template int srs_apply_delta_device<C>(hipStream_t, Arena&, const uint64_t*, const g16_params_view*, uint64_t, uint64_t, double*);
 G16_INSTANTIATE_SRS(Bls12_381)
 G16_INSTANTIATE_SRS(Bn254)

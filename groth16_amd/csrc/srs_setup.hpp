@@ -22,6 +22,17 @@ template <class C> int srs_generate_device(hipStream_t st, Arena& arena, const g
 template <class C> int srs_generate_host(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int qap, const g16_srs_view* srs,
                                          const g16_params_view* out);
 
+// The tail of the derivation alone (libg16_lagrange.so): the transposition, the segment plans, the sparse products and the copies out,
+// from Lagrange points that are complete.  The matrices are checked here; log_n is the caller's to hold against the circuit.
+// Device form: d_lag_g1 = u | alpha u | beta u (3n points, ONE array: the products index it as one), d_lag_g2 = u in G2 (n points),
+// both in `arena`, which is not reset; it returns after the stream has drained.  Host form: four host arrays of n points.
+// fixed: index 0 of tau_g1, alpha_tau_g1, beta_tau_g1, tau_g2 and beta_g2 is read (the key's single points); h_query is the caller's
+template <class C> int srs_queries_device(hipStream_t st, Arena& arena, const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, int log_n,
+                                          const uint64_t* d_lag_g1, const uint64_t* d_lag_g2, const g16_srs_view* fixed, const g16_params_view* out,
+                                          double* products_ms);
+template <class C> int srs_queries_host(const g16_csr_view abc[3], uint64_t ni, uint64_t nc, uint64_t nv, const uint64_t* u, const uint64_t* alpha_u,
+                                        const uint64_t* beta_u, const uint64_t* u_g2, const g16_srs_view* fixed, const g16_params_view* out);
+
 // step 4 in place: delta_g1, delta_g2 <- delta (.) on the host; the n_l + n_h points of l_query / h_query <- delta^-1 (.) on the GPU
 template <class C> int srs_apply_delta_device(hipStream_t st, Arena& arena, const uint64_t* delta, const g16_params_view* inout, uint64_t n_l,
                                               uint64_t n_h, double* delta_ms);

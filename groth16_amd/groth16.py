@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CeremonyInfoC, CeremonyTimingsC, CheckResultC, CsrViewC, G16Error, KeyFoldC, KeycheckTimingsC, ParamsViewC, PartialC, Phase1TimingsC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, SrsTimingsC, SrsViewC, TauContributionC, TimingsC,
+from .binding import (CURVE_ID, FQ_LIMBS, QAP_CIRCOM, QAP_LIBSNARK, CeremonyInfoC, CeremonyTimingsC, CheckResultC, CsrViewC, G16Error, KeyFoldC, KeycheckTimingsC, LagrangeSrsViewC, LagrangeTimingsC, ParamsViewC, PartialC, Phase1TimingsC, PkBytesInfoC, PkInfoC, PkViewC, ProofC, QueryC, SrsTimingsC, SrsViewC, TauContributionC, TimingsC,
                       ToxicWasteC, lib, ptr32, ptr64, u64p)
 
 _MODULUS_R = {
@@ -189,6 +189,133 @@ def generate_parameters_from_srs_host(curve: str, matrices: "ConstraintMatrices"
     lb = lib()
     lb.check(lb.c.g16_host_generate_parameters_srs(CURVE_ID[curve], views, ni, matrices.num_constraints, ni + matrices.num_witness_variables,
                                                    qap.QAP_ID, C.byref(sv), C.byref(out)))
+    return pk
+
+
+# ---- the Lagrange form of an SRS and the key from it (g16_srs_lagrange / g16_generate_parameters_lagrange; libg16_lagrange.so) ----
+LAGRANGE_ARRAYS = ("u_g1", "alpha_u_g1", "beta_u_g1", "u_g2", "h_g1", "tau_g1_0", "alpha_g1_0", "beta_g1_0", "tau_g2_0", "beta_g2")
+
+
+@dataclass
+class LagrangeSRS:
+    """The Lagrange form of an SRS for one domain of 2^log_n points and one reduction (g16_lagrange_srs_view): what snarkjs'
+    `powersoftau prepare phase2` leaves.  u_g1, alpha_u_g1, beta_u_g1, u_g2: the inverse transforms over the group of the first n
+    points of tau_g1, alpha_tau_g1, beta_tau_g1, tau_g2; h_g1: the delta = 1 h_query of the reduction; the five single points the
+    key copies.  Made once by Groth16.prepare_srs, kept with save / load, it serves every circuit of that domain."""
+
+    curve: str
+    log_n: int
+    qap: int   # QAP_LIBSNARK or QAP_CIRCOM (R1CSToQAP.QAP_ID)
+    u_g1: np.ndarray
+    alpha_u_g1: np.ndarray
+    beta_u_g1: np.ndarray
+    u_g2: np.ndarray
+    h_g1: np.ndarray
+    tau_g1_0: np.ndarray
+    alpha_g1_0: np.ndarray
+    beta_g1_0: np.ndarray
+    tau_g2_0: np.ndarray
+    beta_g2: np.ndarray
+
+    @staticmethod
+    def blank(curve: str, log_n: int, qap) -> "LagrangeSRS":
+        """zeroed arrays of the shapes a domain of 2^log_n points and the reduction `qap` need"""
+        L, n = FQ_LIMBS[curve], 1 << log_n
+        g1 = lambda k: np.zeros((k, 2 * L), dtype=np.uint64)  # noqa: E731
+        g2 = lambda k: np.zeros((k, 4 * L), dtype=np.uint64)  # noqa: E731
+        return LagrangeSRS(curve, log_n, qap.QAP_ID, g1(n), g1(n), g1(n), g2(n), g1(qap.h_query_len(n)), g1(1), g1(1), g1(1), g2(1), g2(1))
+
+    def view(self):
+        """(LagrangeSrsViewC, the arrays it points into): hold both until the C call has returned.  The shapes are held against
+        log_n and qap here: the C view carries no lengths"""
+        L, n = FQ_LIMBS[self.curve], 1 << self.log_n
+        n_h = n if self.qap == QAP_CIRCOM else n - 1
+        want = {"u_g1": (n, 2 * L), "alpha_u_g1": (n, 2 * L), "beta_u_g1": (n, 2 * L), "u_g2": (n, 4 * L), "h_g1": (n_h, 2 * L),
+                "tau_g1_0": (1, 2 * L), "alpha_g1_0": (1, 2 * L), "beta_g1_0": (1, 2 * L), "tau_g2_0": (1, 4 * L), "beta_g2": (1, 4 * L)}
+        keep = [_c(getattr(self, k)) for k in LAGRANGE_ARRAYS]
+        for k, a in zip(LAGRANGE_ARRAYS, keep):
+            if a.size != want[k][0] * want[k][1]:
+                raise ValueError(f"LagrangeSRS.{k} has shape {a.shape}, a domain of 2^{self.log_n} points needs {want[k]}")
+        empty = np.zeros(1, dtype=np.uint64)   # behind an array of no points (h_g1 of a one-point Libsnark domain): never read or written
+        ptr = lambda a: ptr64(a.reshape(-1) if a.size else empty)  # noqa: E731
+        return LagrangeSrsViewC(*[ptr(a) for a in keep], self.log_n, self.qap), keep + [empty]
+
+    def save(self, path):
+        """one .npz holding the curve, log_n, qap and the arrays (np.savez appends .npz to a name without it)"""
+        np.savez(path, curve=np.array(self.curve), log_n=np.array(self.log_n, dtype=np.int64), qap=np.array(self.qap, dtype=np.int64),
+                 **{k: _c(getattr(self, k)) for k in LAGRANGE_ARRAYS})
+
+    @staticmethod
+    def load(path) -> "LagrangeSRS":
+        with np.load(path, allow_pickle=False) as z:
+            return LagrangeSRS(str(z["curve"]), int(z["log_n"]), int(z["qap"]), *[np.ascontiguousarray(z[k], dtype=np.uint64) for k in LAGRANGE_ARRAYS])
+
+
+def _qap_of(qap_id: int):
+    return CircomReduction if qap_id == QAP_CIRCOM else LibsnarkReduction
+
+
+def _domain_log(matrices: "ConstraintMatrices") -> int:
+    need, log_n = matrices.num_constraints + matrices.num_instance_variables, 0
+    while (1 << log_n) < need:
+        log_n += 1
+    return log_n
+
+
+def _prepare_args(curve: str, qap, srs: "SRS", log_n, matrices):
+    if srs.curve != curve:
+        raise ValueError("the SRS is for another curve")
+    if (log_n is None) == (matrices is None):
+        raise ValueError("prepare_srs takes the domain from log_n or from the circuit's matrices: give one of the two")
+    log_n = _domain_log(matrices) if matrices is not None else int(log_n)
+    if log_n < 0:
+        raise ValueError("log_n is negative")
+    return LagrangeSRS.blank(curve, log_n, qap)
+
+
+def _lagrange_key_args(curve: str, qap, matrices: "ConstraintMatrices", lagrange_srs: "LagrangeSRS"):
+    """the refusals that need the object's reduction (the C view carries the Lagrange form's own): G16Error with the library's
+    status for a bad argument"""
+    if lagrange_srs.curve != curve:
+        raise ValueError("the Lagrange SRS is for another curve")
+    if lagrange_srs.qap != qap.QAP_ID:
+        raise G16Error(3, f"bad argument | Lagrange SRS: prepared for the reduction qap = {lagrange_srs.qap} ({_qap_of(lagrange_srs.qap).__name__}), "
+                          f"this key is derived for qap = {qap.QAP_ID} ({qap.__name__})")
+    pk = _blank_key(curve, qap, matrices)
+    ni = matrices.num_instance_variables
+    return pk, (ni, matrices.num_constraints, ni + matrices.num_witness_variables)
+
+
+def group_ntt_windowed_host(curve: str, points: np.ndarray, inverse: bool = False) -> np.ndarray:
+    """g16_host_group_ntt_windowed: Groth16.group_ntt_windowed with the device kernels' own tasks run on the host (no GPU)"""
+    pts = _c(points)
+    out = np.zeros_like(pts)
+    lb = lib()
+    lb.check(lb.lag.g16_host_group_ntt_windowed(CURVE_ID[curve], int(_points_g2(curve, pts)), ptr64(pts.reshape(-1)), _log2_exact(len(pts)),
+                                                int(inverse), ptr64(out.reshape(-1))))
+    return out
+
+
+def prepare_srs_host(curve: str, srs: "SRS", log_n: Optional[int] = None, matrices: Optional["ConstraintMatrices"] = None, qap=None) -> "LagrangeSRS":
+    """g16_host_srs_lagrange: Groth16.prepare_srs in plain host code (no GPU; for small domains)"""
+    qap = qap or LibsnarkReduction
+    out = _prepare_args(curve, qap, srs, log_n, matrices)
+    sv, skeep = srs.view()
+    lv, lkeep = out.view()
+    lb = lib()
+    lb.check(lb.lag.g16_host_srs_lagrange(CURVE_ID[curve], C.byref(sv), out.log_n, qap.QAP_ID, C.byref(lv)))
+    return out
+
+
+def generate_parameters_from_lagrange_host(curve: str, matrices: "ConstraintMatrices", lagrange_srs: "LagrangeSRS", qap=None) -> "ProvingKey":
+    """g16_host_generate_parameters_lagrange: Groth16.generate_parameters_from_lagrange in plain host code (no GPU)"""
+    qap = qap or LibsnarkReduction
+    pk, (ni, nc, nv) = _lagrange_key_args(curve, qap, matrices, lagrange_srs)
+    out = _params_view(pk)
+    views, keep = _csr_views(matrices)
+    lv, lkeep = lagrange_srs.view()
+    lb = lib()
+    lb.check(lb.lag.g16_host_generate_parameters_lagrange(CURVE_ID[curve], views, ni, nc, nv, C.byref(lv), C.byref(out)))
     return pk
 
 
@@ -947,6 +1074,50 @@ class Groth16:
         lb.check(lb.c.g16_group_ntt(self._ctx.handle, int(_points_g2(self.curve, pts)), ptr64(pts.reshape(-1)), _log2_exact(len(pts)), int(inverse),
                                     ptr64(out.reshape(-1))))
         return out
+
+    # -- the Lagrange form of an SRS: transform once, derive every circuit's key from it ------------------------------
+    def prepare_srs(self, srs: SRS, log_n: Optional[int] = None, matrices: Optional[ConstraintMatrices] = None) -> "LagrangeSRS":
+        """g16_srs_lagrange: the Lagrange form of `srs` for a domain of 2^log_n points -- or the domain of the circuit `matrices` --
+        and this object's reduction: the four inverse transforms over the group and the delta = 1 h basis, everything of
+        generate_parameters_from_srs that does not depend on the circuit.  The transforms run on the windowed scalar
+        multiplication of phase 1 (group_ntt_windowed).  The SRS is not checked here (check_srs does that)."""
+        out = _prepare_args(self.curve, self.qap, srs, log_n, matrices)
+        sv, skeep = srs.view()
+        lv, lkeep = out.view()
+        lb = self._ctx.lib
+        lb.check(lb.lag.g16_srs_lagrange(self._ctx.handle, C.byref(sv), out.log_n, self.qap.QAP_ID, C.byref(lv)))
+        return out
+
+    def generate_parameters_from_lagrange(self, matrices: ConstraintMatrices, lagrange_srs: "LagrangeSRS") -> ProvingKey:
+        """g16_generate_parameters_lagrange: the key of generate_parameters_from_srs(matrices, srs), byte for byte, from
+        prepare_srs(srs) -- the sparse products and the copies only.  G16Error for a Lagrange form of another domain or another
+        reduction than the circuit's and this object's.  A Lagrange form from elsewhere needs no check of its own: a key derived
+        from a bad one fails check_key_derivation against the raw SRS."""
+        pk, (ni, nc, nv) = _lagrange_key_args(self.curve, self.qap, matrices, lagrange_srs)
+        out = _params_view(pk)
+        views, keep = _csr_views(matrices)
+        lv, lkeep = lagrange_srs.view()
+        lb = self._ctx.lib
+        lb.check(lb.lag.g16_generate_parameters_lagrange(self._ctx.handle, views, ni, nc, nv, C.byref(lv), C.byref(out)))
+        return pk
+
+    def group_ntt_windowed(self, points: np.ndarray, inverse: bool = False) -> np.ndarray:
+        """g16_group_ntt_windowed: group_ntt, bit for bit, with every butterfly's twiddle multiplication on the windowed task of
+        batch_scalar_mul and affine points between the stages.  G16_LAGRANGE_CHUNK (read at every call) bounds the butterflies of
+        one launch."""
+        pts = _c(points)
+        out = np.zeros_like(pts)
+        lb = self._ctx.lib
+        lb.check(lb.lag.g16_group_ntt_windowed(self._ctx.handle, int(_points_g2(self.curve, pts)), ptr64(pts.reshape(-1)), _log2_exact(len(pts)),
+                                               int(inverse), ptr64(out.reshape(-1))))
+        return out
+
+    def lagrange_timings(self) -> dict:
+        """g16_lagrange_get_timings: stream-event milliseconds of the last prepare_srs on this object, per array and for the h
+        basis (uploads and downloads included), and of the products of the last generate_parameters_from_lagrange"""
+        tm = LagrangeTimingsC()
+        self._ctx.lib.check(self._ctx.lib.lag.g16_lagrange_get_timings(self._ctx.handle, C.byref(tm)))
+        return tm.as_dict()
 
     # -- ceremony checks: is the SRS a sequence of powers, does a key descend from its predecessor ------------------
     def rlc_sums(self, points: np.ndarray, coeffs) -> Tuple[np.ndarray, np.ndarray]:
