@@ -246,7 +246,7 @@ EXPORTS = [
     "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
     "g16_dev_fp30_op", "g16_host_fp30_op", "g16_dev_msm_reduce_lab", "g16_dev_window_table_lab", "g16_dev_pairing_op", "g16_host_pairing_op",
-    "g16_dev_msm_pass_lab", "g16_dev_msm_sort_lab",
+    "g16_dev_msm_pass_lab", "g16_dev_msm_sort_lab", "g16_dev_msm_parts_lab", "g16_host_msm_parts_lab",
     "g16_dev_pvk_tables", "g16_dev_prepare_inputs", "g16_host_pvk_tables", "g16_host_prepare_inputs",
     "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
     "g16_decompress_points", "g16_decompress_proofs", "g16_host_decompress_points", "g16_verify_aggregate_bytes",
@@ -483,6 +483,8 @@ class Lib:
         c.g16_dev_window_table_lab.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, C.c_int, C.c_int, u64p]
         c.g16_dev_msm_pass_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PassLabJobC),
                                            C.c_int]
+        c.g16_dev_msm_parts_lab.argtypes = c.g16_dev_msm_pass_lab.argtypes
+        c.g16_host_msm_parts_lab.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PassLabJobC)]
         c.g16_dev_msm_sort_lab.argtypes = [C.c_void_p, u64p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(SortLabInfoC), u32p, u32p, u32p,
                                            C.c_uint64, u32p, C.c_uint64]
         c.g16_dev_pvk_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_int, u64p]
@@ -566,7 +568,7 @@ PASS_LAB_GUARDS = 8
 
 
 def msm_pass_lab(lb: "Lib", ctx, g2: bool, merged: bool, c: int, groups: int, G: int, lseg: int, rows: int, jobs, record_words: int,
-                 affine_words: int):
+                 affine_words: int, walk: str = "segment"):
     """g16_dev_msm_pass_lab (test hook): the bucket pass's walk on caller-made sorted lists, all jobs in one launch.
     jobs: a list of dicts with table (uint64 [rows * base_count, affine words]), base_count, shift, counts (uint32 [M]) and sorted
     (uint32 [S]).  Returns (status, results); results is None unless status == 0, else per job a dict: records (uint32
@@ -589,12 +591,31 @@ def msm_pass_lab(lb: "Lib", ctx, g2: bool, merged: bool, c: int, groups: int, G:
         j.counts, j.sorted, j.n_sorted, j.record_cap = ptr32(counts), ptr32(srt), int(job.get("n_sorted", len(srt))), cap
         j.records, j.offsets, j.task_off, j.heavy, j.out_affine = (ptr32(o["records"].reshape(-1)), ptr32(o["offsets"]), ptr32(o["task_off"]),
                                                                    ptr32(o["heavy"]), ptr64(o["out"]))
-    status = lb.c.g16_dev_msm_pass_lab(ctx, int(g2), int(merged), c, groups, G, lseg, rows, arr, len(jobs))
+    if walk == "host":
+        assert len(jobs) == 1 and not g2
+        status = lb.c.g16_host_msm_parts_lab(ctx, int(merged), c, groups, lseg, rows, arr)
+    else:
+        entry = lb.c.g16_dev_msm_parts_lab if walk == "parts" else lb.c.g16_dev_msm_pass_lab
+        status = entry(ctx, int(g2), int(merged), c, groups, G, lseg, rows, arr, len(jobs))
     if status != 0:
         return status, None
     for k, o in enumerate(outs):
-        o["records"] = o["records"][:arr[k].n_records + PASS_LAB_GUARDS]
+        o["records"] = o["records"][:arr[k].n_records + (0 if walk == "host" else PASS_LAB_GUARDS)]
     return status, outs
+
+
+def msm_parts_lab(lb: "Lib", ctx, g2: bool, merged: bool, c: int, groups: int, G: int, lmax: int, rows: int, jobs, record_words: int,
+                  affine_words: int):
+    """g16_dev_msm_parts_lab (test hook): msm_pass_lab with the bucket-part walk, lmax the longest part"""
+    return msm_pass_lab(lb, ctx, g2, merged, c, groups, G, lmax, rows, jobs, record_words, affine_words, walk="parts")
+
+
+def host_msm_parts_lab(lb: "Lib", curve_id: int, merged: bool, c: int, groups: int, lmax: int, rows: int, job, record_words: int,
+                       affine_words: int):
+    """g16_host_msm_parts_lab (host twin, G1): one job through the layout rule and the per-task walk compiled for the host.
+    Returns (status, result) as msm_pass_lab does for one job; the records carry no guards."""
+    status, outs = msm_pass_lab(lb, curve_id, False, merged, c, groups, 8, lmax, rows, [job], record_words, affine_words, walk="host")
+    return status, (outs[0] if outs else None)
 
 
 def msm_sort_lab(lb: "Lib", ctx, scalars: np.ndarray, merged_c: int = 0, shard_n: int = 1, shard_r: int = 0):

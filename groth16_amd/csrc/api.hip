@@ -1028,6 +1028,14 @@ int g16_dev_msm_pass_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, in
     G16_DISPATCH(ctx->curve, I::template msm_pass_lab<typename I::Fq2>(ctx, merged, c, groups, G, lseg, rows, jobs, n_jobs));
 }
 
+int g16_dev_msm_parts_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, int lmax, int rows, g16_pass_lab_job* jobs, int n_jobs) {
+    if (!ctx || !jobs) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty()) return g16_dev_msm_parts_lab(ctx->subs[0], g2, merged, c, groups, G, lmax, rows, jobs, n_jobs);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    if (!g2) G16_DISPATCH(ctx->curve, I::template msm_pass_lab<typename I::Fq>(ctx, merged, c, groups, G, lmax, rows, jobs, n_jobs, true));
+    G16_DISPATCH(ctx->curve, I::template msm_pass_lab<typename I::Fq2>(ctx, merged, c, groups, G, lmax, rows, jobs, n_jobs, true));
+}
+
 int g16_dev_msm_sort_lab(g16_ctx* ctx, const uint64_t* scalars, uint64_t n, int merged_c, int shard_n, int shard_r, g16_sort_lab_info* info,
                          uint32_t* offsets, uint32_t* task_off, uint32_t* heavy, uint64_t bucket_cap, uint32_t* sorted, uint64_t sorted_cap) {
     if (!ctx || !info || !offsets || !task_off || !heavy || !sorted || (n && !scalars)) return G16_ERR_BAD_ARG;

@@ -1,6 +1,7 @@
 // Internal plumbing shared by the translation units of libg16_mi355x.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -230,6 +231,10 @@ struct MsmPlan {
     // 2^(c-1) buckets -- its reductions shrink shard_n-fold too.  groups * B >= ceil(2^(c-1) / shard_n) local buckets; fold_windows
     // turns the local sums into the rank's share  sum_{b owned} (b+1) S_b = shard_n sum_k (k+1) S_k + (shard_r + 1 - shard_n) sum_k S_k.
     int shard_n = 1, shard_r = 0;
+    // How the bucket pass cuts the sorted list into tasks (msm.hip step 5).  MSM_WALK_SEGMENT: fixed segments of Lmax entries, a lane
+    // flushes at every bucket boundary it crosses.  MSM_WALK_PARTS: whole parts of one bucket, at most Lmax entries each, ordered by
+    // length (part_walk.hpp); the prover's merged-window sorts ask for it (msm_prover_walk), everything else keeps the segments.
+    int walk = 0;
     uint32_t buckets() const { return B * (uint32_t)groups; }
     // Reduction of one group of B buckets: chunks of min(G, B) buckets per lane give (sum_b (b - b_lo + 1) S_b, sum_b S_b);
     // the chunk offsets b_lo = G * ch are applied WITHOUT a scalar multiplication in the dependent chain: the window level
@@ -243,6 +248,10 @@ struct MsmPlan {
     int outputs() const { return groups * planes(); }             // XYZZ sums leaving the device per MSM (<= 224)
 };
 static constexpr int MSM_MAX_OUTPUTS = 256;
+static constexpr int MSM_WALK_SEGMENT = 0, MSM_WALK_PARTS = 1;
+// the walk the prover asks its sorts for: MSM_WALK_PARTS, or what G16_MSM_WALK=segment|parts forces (A/B)
+int msm_prover_walk();
+struct PartTask;   // part_walk.hpp
 static constexpr int MSM_MERGED_MIN_C = 9, MSM_MERGED_MAX_C = 20;   // merged entries pack window j < 32 and point i < 2^26
 static constexpr uint64_t MSM_MERGED_MAX_N = (uint64_t)1 << 26;
 // merged_c = 0: per-window plan, window size from the cost model (or G16_MSM_WINDOW); else a merged plan with that c
@@ -265,14 +274,18 @@ struct ScalarSort {
     uint64_t n = 0;
     uint32_t* sorted = nullptr;    // [<= n*W] point index | sign<<31 (merged: | window<<26), grouped by bucket
     uint32_t* offsets = nullptr;   // [buckets + 1] exclusive prefix of bucket sizes
-    uint32_t* task_off = nullptr;  // [buckets + 1] exclusive prefix of per-bucket partial-sum slots (one per segment a bucket touches)
+    uint32_t* task_off = nullptr;  // [buckets + 1] exclusive prefix of per-bucket partial-sum slots (one per segment a bucket touches,
+                                   // or -- MSM_WALK_PARTS -- one per part of the bucket)
+    PartTask* tasks = nullptr;     // MSM_WALK_PARTS: [task_off[buckets]] one descriptor per slot, longest parts first
     uint32_t* heavy = nullptr;     // [0] = number of buckets with more than HEAVY_PARTS partials, then their ids
     uint32_t max_tasks = 0;        // host-side upper bound on task_off[buckets] (partial slots)
-    uint32_t max_segments = 0;     // host-side upper bound on ceil(entries the bucket pass walks / Lmax)
+    uint32_t max_segments = 0;     // host-side upper bound on the bucket pass's tasks: ceil(entries it walks / Lmax) segments, or
+                                   // -- MSM_WALK_PARTS -- entries / Lmax + buckets parts (the real count is read on the device)
     uint64_t max_sorted = 0;       // host-side upper bound on offsets[buckets]: entries + padding of the batched-affine plan
 };
+// walk: what the caller would like; MSM_WALK_PARTS is granted to merged plans without batched-affine levels (out->plan.walk says)
 template <class C> int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Arena& arena, hipStream_t st, ScalarSort* out,
-                                    int shard_n = 1, int shard_r = 0);
+                                    int shard_n = 1, int shard_r = 0, int walk = MSM_WALK_SEGMENT);
 // Short scalars (the 128-bit coefficients of the ceremony library): a per-window plan over 128 scalar bits plus the signed-digit
 // carry, and the per-window sort from its second step on over digit planes the caller made (W planes of n u16 digits of
 // scalar + plan.K, as digits_kernel writes them; device memory) -- histogram, slot layout, scatter
@@ -285,6 +298,19 @@ int sort_digit_planes(const MsmPlan& plan, const uint16_t* planes, uint64_t n, A
 // All device pointers; block_sums: M / 2048 + 1 words of scratch.
 int msm_slot_layout(const uint32_t* counts, uint32_t M, int R, uint32_t lseg, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off,
                     uint32_t* heavy, uint32_t* block_sums, hipStream_t st);
+
+// The same tail for MSM_WALK_PARTS (partwalk.hip, the part-walk library): counts[M] -> offsets[M + 1], nparts[M] = ceil(count / lmax),
+// task_off[M + 1], the heavy list as above, and tasks[task_off[M]]: one descriptor per slot, ordered by length, longest first (a counting
+// sort over the <= lmax lengths: LDS histograms per workgroup, one scan, no global atomics).  8 <= lmax <= PART_MAX_L;
+// scratch: msm_parts_layout_scratch(M, lmax) words of device memory.
+static constexpr uint32_t PART_MAX_L = 4096;    // lengths the layout's histogram holds
+static constexpr uint32_t PART_TILE = 1024;     // buckets per workgroup of the layout kernels
+inline size_t msm_parts_layout_scratch(uint32_t M, uint32_t lmax) {
+    const size_t cells = (size_t)lmax * ((M + PART_TILE - 1) / PART_TILE);   // the [length][workgroup] matrix
+    return 2 * (cells + 1) + (std::max<size_t>(M, cells) + 2047) / 2048 + 1;  // counts, their prefix, the scan's block sums
+}
+int msm_parts_layout(const uint32_t* counts, uint32_t M, uint32_t lmax, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off, uint32_t* heavy,
+                     PartTask* tasks, uint32_t* scratch, hipStream_t st);
 
 // Pippenger over one base array using a ScalarSort, in two stream-separable halves:
 //   msm_bucket_pass  the throughput-bound bucket accumulation.  Sorted index p addresses bases[p + shift] when
@@ -301,7 +327,7 @@ struct MsmBuffers {
 };
 template <class F> int msm_bucket_pass(const Affine<F>* d_bases, int64_t shift, uint64_t base_count, const ScalarSort& ss, Arena& arena,
                                        hipStream_t st, MsmBuffers<F>* out, EventTimer* bucket_timer);
-// the bucket passes of n <= 4 MSMs over one bucket layout (B, groups, segment length) as ONE launch: one tail instead of n
+// the bucket passes of n <= 4 MSMs over one bucket layout (B, groups, segment length, walk) as ONE launch: one tail instead of n
 template <class F>
 struct PassJob {
     const Affine<F>* bases;

@@ -24,7 +24,10 @@
 //                           mixed additions (8M+2S, no inversion; Y3 under one reduction) in 30-bit lazy arithmetic
 //                           (fp30.hpp), the running sum's four coordinates parked in LDS (AccParked, round 4),
 //                           flushing one partial sum per (bucket, segment) it touches.  ONE launch walks up to four MSMs
-//                           (PassBatch, round 5: the G1 MSMs of a proof that are ready together -- one tail instead of four)
+//                           (PassBatch, round 5: the G1 MSMs of a proof that are ready together -- one tail instead of four).
+//                           The prover's merged-window sorts use the BUCKET-PART walk instead (MsmPlan::walk, part_walk.hpp; its
+//                           kernels live in partwalk.hip, a library of their own): one lane (pair) per part of ONE bucket, at most
+//                           Lmax entries, tasks ordered by length -- no boundary test and no flush in the loop, one store at the end
 //   5b. heavy_reduce_kernel cooperative combine of the FEW buckets with MANY partial sums (> 16)
 //   5c. bucket_combine_kernel (round 5)  every other bucket's partial sums added up by one lane per BUCKET, so that ...
 //   6. bucket_reduce_kernel / window_reduce_kernel   ... sum_b (b+1) S_b by chunked running sums reads ONE sum per bucket: a chain
@@ -52,10 +55,13 @@
 #include "msm_common.hpp"
 #include "fp30.hpp"
 #include "acc_store.hpp"
+#include "scan.hpp"
+#include "pass_batch.hpp"
 #include "batch_affine.hpp"
 #include "window_tables.hpp"
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 namespace g16 {
 
@@ -287,65 +293,7 @@ static __global__ __launch_bounds__(SORT_M_THREADS) void bucket_scatter_merged_k
 //    (block sums -> scan of block sums -> write), 2048 values per workgroup.  Used twice: bucket counts -> bucket
 //    offsets, and per-bucket partial-slot counts -> slot offsets.
 // ---------------------------------------------------------------------------------------------
-static constexpr int SCAN_THREADS = 256;
-static constexpr int SCAN_PER_THREAD = 8;
-static constexpr int SCAN_TILE = SCAN_THREADS * SCAN_PER_THREAD;
-
-// exclusive scan of one value per thread across the workgroup; returns the workgroup total through *total
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* sh, uint32_t* total) {
-    const uint32_t tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < SCAN_THREADS; d <<= 1) {
-        const uint32_t add = tid >= d ? sh[tid - d] : 0u;
-        __syncthreads();
-        sh[tid] += add;
-        __syncthreads();
-    }
-    const uint32_t incl = sh[tid];
-    *total = sh[SCAN_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-// `pad` (a power of two minus one, or 0): every value is rounded up to a multiple of pad + 1 before it is summed -- bucket
-// regions of the batched-affine plan start and end on multiples of 2^R entries
-static __global__ __launch_bounds__(SCAN_THREADS) void scan_block_sums_kernel(const uint32_t* __restrict__ vals, uint32_t M, uint32_t pad,
-                                                                       uint32_t* __restrict__ block_sums) {
-    __shared__ uint32_t sa[SCAN_THREADS];
-    const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
-    uint32_t sum = 0, tot;
-    G16_UNROLL for (int j = 0; j < SCAN_PER_THREAD; ++j) sum += (base + j < M) ? ((vals[base + j] + pad) & ~pad) : 0u;
-    (void)block_exclusive(sum, sa, &tot);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
-}
-
-static __global__ __launch_bounds__(SCAN_THREADS) void scan_block_offsets_kernel(uint32_t* __restrict__ block_sums, uint32_t nblocks, uint32_t M,
-                                                                          uint32_t* __restrict__ prefix) {
-    __shared__ uint32_t sa[SCAN_THREADS];
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nblocks; base += SCAN_THREADS) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t a = i < nblocks ? block_sums[i] : 0u;
-        uint32_t tot;
-        const uint32_t ea = block_exclusive(a, sa, &tot);
-        if (i < nblocks) block_sums[i] = carry + ea;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) prefix[M] = carry;
-}
-
-static __global__ __launch_bounds__(SCAN_THREADS) void scan_write_kernel(const uint32_t* __restrict__ vals, uint32_t M, uint32_t pad,
-                                                                  const uint32_t* __restrict__ block_base, uint32_t* __restrict__ prefix) {
-    __shared__ uint32_t sa[SCAN_THREADS];
-    const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
-    uint32_t cv[SCAN_PER_THREAD], sum = 0, tot;
-    G16_UNROLL for (int j = 0; j < SCAN_PER_THREAD; ++j) { cv[j] = (base + j < M) ? ((vals[base + j] + pad) & ~pad) : 0u; sum += cv[j]; }
-    uint32_t a = block_base[blockIdx.x] + block_exclusive(sum, sa, &tot);
-    G16_UNROLL for (int j = 0; j < SCAN_PER_THREAD; ++j) {
-        if (base + j < M) { prefix[base + j] = a; a += cv[j]; }
-    }
-}
+// (scan.hpp: SCAN_THREADS, SCAN_TILE, block_exclusive and the three kernels, shared with the part-walk library)
 
 // partial-sum slots of bucket b = number of length-L segments of the sorted list its entries touch
 // (batched-affine plan: the bucket pass walks the level-R list, whose bucket regions are offsets >> R)
@@ -574,8 +522,9 @@ static __global__ __launch_bounds__(SORT_THREADS) void bucket_scatter_kernel(con
 // ---------------------------------------------------------------------------------------------
 // 5. bucket accumulation (THE hot kernel), 30-bit lazy arithmetic (fp30.hpp); F30 = Fp30<P> (G1) or Fp2p30<P> (G2, lane pair).
 // Work unit = a SEGMENT of Lseg consecutive entries of the bucket-sorted list, not a bucket: every lane walks exactly
-// Lseg entries, so lanes of a wave finish together whatever the bucket-size distribution (one lane per bucket left ~18 %
-// of lane time idle at a mean bucket load of 128, ~35 % at 16).  When the walk crosses a bucket boundary the running sum
+// Lseg entries, so lanes of a wave finish together whatever the bucket-size distribution (one lane per whole bucket, in bucket
+// order, left ~18 % of lane time idle at a mean bucket load of 128, ~35 % at 16: what idled the lanes was the missing order by
+// length, which the bucket-part walk has).  When the walk crosses a bucket boundary the running sum
 // is flushed -- raw lazy limbs, no conversion -- into that bucket's slot for this segment (slot offsets from the scan),
 // so a bucket ends up with one partial sum per segment it touches; the reduction kernels add them up.
 // `bases` hold canonical x*R', y*R' packed in 32-bit words (convert_bases30_kernel).
@@ -634,18 +583,7 @@ __device__ __forceinline__ Acc30<F30> gather_acc(const St& st, bool inf) {
 // re-filled dynamically -- and a launch's tail cannot be filled by the next launch of the same stream.  The G1 MSMs of a proof that are
 // ready together (l, a, b_g1 share the witness sort; h joins when its sort is done in time) therefore go as ONE launch: one tail
 // instead of three or four (a rank's share of an 8-way sharded 2^22 proof: 1.3-1.4 ms per pass of 1.1 ms of work, round 5).
-static constexpr int PASS_BATCH = 4;
-template <class F30>
-struct PassBatch {
-    const Affine<typename F30::Std>* bases[PASS_BATCH];
-    int64_t shift[PASS_BATCH];
-    uint64_t base_count[PASS_BATCH];
-    const uint32_t* sorted[PASS_BATCH];
-    const uint32_t* offsets[PASS_BATCH];
-    const uint32_t* slot_off[PASS_BATCH];
-    AccRaw<typename F30::Raw>* partials[PASS_BATCH];
-};
-
+// (pass_batch.hpp: PASS_BATCH and PassBatch, shared with the part-walk library)
 template <class F30, bool DIRECT>
 __global__ __launch_bounds__(ACC_THREADS, F30::ACC_MIN_WAVES) void bucket_accumulate30_kernel(
     PassBatch<F30> batch, uint32_t M, uint32_t off_shift, uint32_t lseg, uint32_t merged) {
@@ -1135,17 +1073,28 @@ int msm_slot_layout(const uint32_t* counts, uint32_t M, int R, uint32_t lseg, ui
     G16_TRY(prefix_scan_u32(nparts, task_off, M, 0u, block_sums, st));
     return G16_OK;
 }
+
+int msm_prover_walk() {
+    if (const char* e = getenv("G16_MSM_WALK")) {   // A/B: force either walk
+        if (!strcmp(e, "segment")) return MSM_WALK_SEGMENT;
+        if (!strcmp(e, "parts")) return MSM_WALK_PARTS;
+    }
+    return MSM_WALK_PARTS;
+}
 #endif
 
 template <class C>
 int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Arena& arena, hipStream_t st, ScalarSort* out, int shard_n,
-                 int shard_r) {
+                 int shard_r, int walk) {
     typedef typename C::Fr Fr;
     if (n >= ((uint64_t)1 << 31)) return G16_ERR_BAD_LENGTH;
     uint32_t modw[Fr::N];
     for (int i = 0; i < Fr::N; ++i) modw[i] = Fr::Params::mod(i);
     MsmPlan plan;
     G16_TRY(make_msm_plan(n, Fr::Params::BITS, modw, Fr::N, merged_c, &plan, shard_n, shard_r));
+    // the bucket-part walk: merged plans whose pass walks the sorted list itself (and lengths its layout's histogram holds)
+    const bool parts = walk == MSM_WALK_PARTS && plan.merged && plan.affine_levels == 0 && plan.Lmax <= PART_MAX_L;
+    plan.walk = parts ? MSM_WALK_PARTS : MSM_WALK_SEGMENT;
     out->plan = plan;
     out->n = n;
     const uint32_t M = plan.buckets();
@@ -1189,6 +1138,14 @@ int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Aren
     const uint64_t walked = R ? (max_sorted >> R) : nw;
     out->max_segments = (uint32_t)((walked + plan.Lmax - 1) / plan.Lmax);
     out->max_tasks = out->max_segments + M;   // a bucket gets one slot per segment it touches: <= segments + buckets in total
+    uint32_t* part_scratch = nullptr;
+    if (parts) {
+        // sum_b ceil(n_b / Lmax) <= entries / Lmax + buckets; one task per slot, and the grid of the pass covers that bound
+        out->max_tasks = (uint32_t)(nw / plan.Lmax) + M;
+        out->max_segments = out->max_tasks;
+        G16_TRY(arena.alloc_n((size_t)out->max_tasks ? out->max_tasks : 1, &out->tasks));
+        G16_TRY(arena.alloc_n(msm_parts_layout_scratch(M, plan.Lmax), &part_scratch));
+    }
     G16_HIP_TRY(hipMemsetAsync(counts, 0, ((size_t)2 * M + 1) * sizeof(uint32_t), st));
     PlanDev pd;
     pd.c = plan.c; pd.W = plan.W; pd.B = plan.B;
@@ -1284,7 +1241,8 @@ int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Aren
         }
         G16_LAUNCH_CHECK();
     }
-    G16_TRY(msm_slot_layout(counts, M, R, plan.Lmax, out->offsets, nparts, out->task_off, out->heavy, block_sums, st));
+    if (parts) G16_TRY(msm_parts_layout(counts, M, plan.Lmax, out->offsets, nparts, out->task_off, out->heavy, out->tasks, part_scratch, st));
+    else G16_TRY(msm_slot_layout(counts, M, R, plan.Lmax, out->offsets, nparts, out->task_off, out->heavy, block_sums, st));
     if (n && !two_level) {
         if (plan.merged)
             hipLaunchKernelGGL(bucket_scatter_merged_kernel, dim3(gx, Q), dim3(SORT_M_THREADS), lds, st, planes, ent_tag, class_off, nb, Bs,
@@ -1469,20 +1427,25 @@ int msm_bucket_pass_batch(const PassJob<F>* jobs, int n, Arena& arena, hipStream
     const MsmPlan& plan = jobs[0].ss->plan;
     for (int i = 0; i < n; ++i) {
         const MsmPlan& q = jobs[i].ss->plan;
-        if (q.B != plan.B || q.groups != plan.groups || q.Lmax != plan.Lmax || q.merged != plan.merged) return G16_ERR_INTERNAL;
+        if (q.B != plan.B || q.groups != plan.groups || q.Lmax != plan.Lmax || q.merged != plan.merged || q.walk != plan.walk) return G16_ERR_INTERNAL;
+        if (q.walk == MSM_WALK_PARTS && (!jobs[i].ss->tasks || q.affine_levels)) return G16_ERR_INTERNAL;
         if (q.affine_levels && jobs[i].ss->max_sorted) return G16_ERR_INTERNAL;   // that plan walks level lists: msm_bucket_pass
     }
     PassBatch<F30> b;
+    PartTaskBatch tb;
     uint32_t max_segments = 0;
     for (int i = 0; i < n; ++i) G16_TRY(alloc_msm_buffers<F>(*jobs[i].ss, arena, jobs[i].out));
     for (int i = 0; i < PASS_BATCH; ++i) {
         const PassJob<F>& j = jobs[i < n ? i : 0];
         b.bases[i] = j.bases; b.shift[i] = j.shift; b.base_count[i] = j.base_count; b.sorted[i] = j.ss->sorted;
         b.offsets[i] = j.ss->offsets; b.slot_off[i] = j.ss->task_off; b.partials[i] = static_cast<Raw*>(j.out->partials);
+        tb.tasks[i] = j.ss->tasks;
         if (i < n) max_segments = std::max(max_segments, j.ss->max_segments);
     }
     if (bucket_timer) G16_TRY(bucket_timer->start(st));
-    if (max_segments) {
+    if (max_segments && plan.walk == MSM_WALK_PARTS) {   // max_segments bounds the parts here; the kernel lives in the part-walk library
+        G16_TRY((msm_parts_pass_launch<F30>(b, tb, n, max_segments, plan.buckets(), plan.merged, pass_lds_pad<F30>(), st)));
+    } else if (max_segments) {
         const uint64_t lanes = (uint64_t)max_segments * F30::LANES_PER_TASK;
         const dim3 grid((unsigned)((lanes + ACC_THREADS - 1) / ACC_THREADS), (unsigned)n);
         hipLaunchKernelGGL((bucket_accumulate30_kernel<F30, false>), grid, dim3(ACC_THREADS), pass_lds_pad<F30>(), st, b, plan.buckets(), 0u,
@@ -1687,7 +1650,7 @@ int build_window_tables(const Affine<F>* d_src, uint64_t n, int c, int W, Affine
 #define G16_INSTANTIATE_MSM(C)                                                                                               \
     template int convert_bases<typename C::Fq>(Affine<typename C::Fq>*, uint64_t, hipStream_t);                             \
     template int convert_bases<typename C::Fq2>(Affine<typename C::Fq2>*, uint64_t, hipStream_t);                           \
-    template int sort_scalars<C>(const typename C::Fr*, uint64_t, int, Arena&, hipStream_t, ScalarSort*, int, int);                   \
+    template int sort_scalars<C>(const typename C::Fr*, uint64_t, int, Arena&, hipStream_t, ScalarSort*, int, int, int);                  \
     template int build_window_tables<typename C::Fq>(const Affine<typename C::Fq>*, uint64_t, int, int, Affine<typename C::Fq>*, hipStream_t, void*);    \
     template int build_window_tables<typename C::Fq2>(const Affine<typename C::Fq2>*, uint64_t, int, int, Affine<typename C::Fq2>*, hipStream_t, void*); \
     template size_t window_table_park_bytes<typename C::Fq>(uint64_t, int);                                                 \

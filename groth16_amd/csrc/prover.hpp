@@ -37,7 +37,7 @@ struct Prover {
         ctx->reset_arena();
         const Fr* d_z = reinterpret_cast<const Fr*>(z_dev);
         ScalarSort ss;
-        G16_TRY((sort_scalars<C>(d_z + 1 + pk->a_start, pk->a_count, pk->c_z, ctx->arena, ctx->stream2, &ss, pk->shard_n, pk->shard_r)));
+        G16_TRY((sort_scalars<C>(d_z + 1 + pk->a_start, pk->a_count, pk->c_z, ctx->arena, ctx->stream2, &ss, pk->shard_n, pk->shard_r, msm_prover_walk())));
         G16_HIP_TRY(hipEventRecord(ctx->ev_z, ctx->stream2));
         ctx->prep.valid = true;
         ctx->prep.pk = pkh;
@@ -139,7 +139,7 @@ struct Prover {
         } else {
             G16_HIP_TRY(hipStreamWaitEvent(s2, ctx->ev_z, 0));
             G16_TRY(ctx->t_prep_z.start(s2));
-            G16_TRY((sort_scalars<C>(d_z + 1 + pk->a_start, pk->a_count, pk->c_z, ctx->arena, s2, &sort_z, pk->shard_n, pk->shard_r)));
+            G16_TRY((sort_scalars<C>(d_z + 1 + pk->a_start, pk->a_count, pk->c_z, ctx->arena, s2, &sort_z, pk->shard_n, pk->shard_r, msm_prover_walk())));
             G16_TRY(ctx->t_prep_z.stop(s2));
             G16_HIP_TRY(hipEventRecord(ctx->ev_z, s2));   // (re-recorded: now also covers the witness sort)
         }
@@ -147,7 +147,7 @@ struct Prover {
         // ---- stream 3: h's digit/sort pass, underneath the first bucket pass (stream 2 stays free for the reductions)
         G16_HIP_TRY(hipStreamWaitEvent(s3, ctx->ev_wm, 0));
         G16_TRY(ctx->t_prep_h.start(s3));
-        G16_TRY((sort_scalars<C>(d_h + pk->h_start, pk->h_count, pk->c_h, ctx->arena, s3, &sort_h, pk->shard_n, pk->shard_r)));
+        G16_TRY((sort_scalars<C>(d_h + pk->h_start, pk->h_count, pk->c_h, ctx->arena, s3, &sort_h, pk->shard_n, pk->shard_r, msm_prover_walk())));
         G16_TRY(ctx->t_prep_h.stop(s3));
         G16_HIP_TRY(hipEventRecord(ctx->ev_h, s3));
 
@@ -231,7 +231,7 @@ struct Prover {
         int pk_of[4], npj = 0;
         double weight[5] = {0, 0, 0, 0, 0};   // a batch's time is shared out by the points of its members (one W: entries ~ points)
         auto plans_match = [](const MsmPlan& x, const MsmPlan& y) {
-            return x.B == y.B && x.groups == y.groups && x.Lmax == y.Lmax && x.merged == y.merged && x.affine_levels == 0 && y.affine_levels == 0;
+            return x.B == y.B && x.groups == y.groups && x.Lmax == y.Lmax && x.merged == y.merged && x.walk == y.walk && x.affine_levels == 0 && y.affine_levels == 0;
         };
         const bool batch_ok = sort_z.plan.affine_levels == 0 || sort_z.max_sorted == 0;
         // (sharded proof: h waits in the same launch -- the launch then waits ~0.4 ms for h's sort, which only gets going when the G2
@@ -289,7 +289,7 @@ struct Prover {
             const int64_t shift = (int64_t)pk->a_start - (int64_t)(nin - 1) - (int64_t)pk->l_start;
             queue_pass(1, pk->l, shift, pk->l_count, sort_z, &buf_l);
         } else {
-            G16_TRY((sort_scalars<C>(d_z + nin + pk->l_start, pk->l_count, pk->c_z, ctx->arena, s1, &sort_l, pk->shard_n, pk->shard_r)));
+            G16_TRY((sort_scalars<C>(d_z + nin + pk->l_start, pk->l_count, pk->c_z, ctx->arena, s1, &sort_l, pk->shard_n, pk->shard_r, msm_prover_walk())));
             last_end = nullptr;   // the sort sits between the passes: this one gets its own begin mark
             queue_pass(1, pk->l, 0, pk->l_count, sort_l, &buf_l);
             G16_TRY(run_batch());

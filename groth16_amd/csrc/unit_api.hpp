@@ -3,6 +3,7 @@
 #pragma once
 #include "api_types.hpp"
 #include "prover.hpp"
+#include "part_walk.hpp"
 
 namespace {
 
@@ -196,8 +197,11 @@ struct UnitApi {
     // did is checked afterwards (G16_ERR_INTERNAL).  ss.max_tasks = task_off[M] + 8: the 8 records behind the last slot are the guards.
     // Refused (G16_ERR_BAD_ARG): whatever would let the kernel read outside what was uploaded.  A point index outside [0, base_count)
     // after `shift` is NOT refused: skipping it is the kernel's to do.
+    // parts (g16_dev_msm_parts_lab): the same with the bucket-part walk -- plan.walk = MSM_WALK_PARTS, lseg is the longest part, the
+    // layout and the task list come from msm_parts_layout, a bucket's slots are its parts; per-window plans run it here too.
     template <class F>
-    static int msm_pass_lab(g16_ctx* ctx, int merged, int c, int groups, int G, int lseg, int rows, g16_pass_lab_job* jobs, int n_jobs) {
+    static int msm_pass_lab(g16_ctx* ctx, int merged, int c, int groups, int G, int lseg, int rows, g16_pass_lab_job* jobs, int n_jobs,
+                            bool parts = false) {
         typedef Affine<F> A;
         typedef XYZZ<F> X;
         typedef Fp30<typename Fq::Params> B30;
@@ -218,6 +222,7 @@ struct UnitApi {
             plan.B = 1u << (c - 1);
             plan.G = (uint32_t)G;
             plan.Lmax = (uint32_t)lseg;
+            plan.walk = parts ? MSM_WALK_PARTS : MSM_WALK_SEGMENT;
             plan.chunk = 1024;
             for (int k = 0; k < 10; ++k) plan.K[k] = 0;
         }
@@ -237,8 +242,9 @@ struct UnitApi {
             if (merged)
                 for (uint64_t e = 0; e < job.n_sorted; ++e)
                     if (((job.sorted[e] >> 26) & 31u) >= (uint32_t)rows) return G16_ERR_BAD_ARG;
-            // a bucket gets one slot per segment it touches: <= segments + buckets in total
-            if (job.record_cap < (job.n_sorted + (uint64_t)lseg - 1) / (uint64_t)lseg + M + GUARDS) return G16_ERR_BAD_LENGTH;
+            // a bucket gets one slot per segment it touches: <= segments + buckets in total; one per part: <= entries / lseg + buckets
+            const uint64_t slots = (parts ? job.n_sorted / (uint64_t)lseg : (job.n_sorted + (uint64_t)lseg - 1) / (uint64_t)lseg) + M;
+            if (job.record_cap < slots + GUARDS) return G16_ERR_BAD_LENGTH;
         }
         hipStream_t st = ctx->stream;
         DrainOnError drain(ctx);
@@ -267,7 +273,13 @@ struct UnitApi {
             if (job.n_sorted)
                 G16_HIP_TRY(hipMemcpyAsync(ss[j].sorted, job.sorted, (size_t)job.n_sorted * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             G16_HIP_TRY(hipMemsetAsync(ss[j].heavy, 0, ((size_t)M + 1) * sizeof(uint32_t), st));
-            G16_TRY(msm_slot_layout(d_counts[j], M, 0, plan.Lmax, ss[j].offsets, d_nparts, ss[j].task_off, ss[j].heavy, d_block, st));
+            if (parts) {
+                G16_TRY(ctx->arena.alloc_n((size_t)(job.n_sorted / (uint64_t)lseg) + M, &ss[j].tasks));
+                uint32_t* scratch = nullptr;
+                G16_TRY(ctx->arena.alloc_n(msm_parts_layout_scratch(M, plan.Lmax), &scratch));
+                G16_TRY(msm_parts_layout(d_counts[j], M, plan.Lmax, ss[j].offsets, d_nparts, ss[j].task_off, ss[j].heavy, ss[j].tasks, scratch, st));
+            } else
+                G16_TRY(msm_slot_layout(d_counts[j], M, 0, plan.Lmax, ss[j].offsets, d_nparts, ss[j].task_off, ss[j].heavy, d_block, st));
             G16_HIP_TRY(hipMemcpyAsync(h_task.data() + (size_t)j * (M + 1), ss[j].task_off, ((size_t)M + 1) * sizeof(uint32_t),
                                        hipMemcpyDeviceToHost, st));
         }
@@ -279,7 +291,9 @@ struct UnitApi {
             ss[j].max_sorted = jobs[j].n_sorted;
             ss[j].max_tasks = tasks + GUARDS;
             // one task past the last segment: real plans size the grid by an upper bound too, and that task must return at once
-            ss[j].max_segments = jobs[j].n_sorted ? (uint32_t)((jobs[j].n_sorted + plan.Lmax - 1) / plan.Lmax) + 1u : 0u;
+            // (parts: one task past the last descriptor)
+            if (parts) ss[j].max_segments = jobs[j].n_sorted ? tasks + 1u : 0u;
+            else ss[j].max_segments = jobs[j].n_sorted ? (uint32_t)((jobs[j].n_sorted + plan.Lmax - 1) / plan.Lmax) + 1u : 0u;
             jobs[j].n_records = tasks;
         }
         // the allocations msm_bucket_pass_batch is about to make (alloc_msm_buffers, job by job), filled, then handed back

@@ -639,6 +639,18 @@ typedef struct {
 } g16_pass_lab_job;
 int g16_dev_msm_pass_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, int lseg, int rows, g16_pass_lab_job* jobs, int n_jobs);
 
+/* ---- the parts lab (test hook): the bucket-part walk in place ----
+ * The pass lab with the walk the prover's merged-window sorts use: a bucket of n entries is cut into ceil(n / lmax) parts, part p covers
+ * the entries [p n / np, (p + 1) n / np) of the bucket (integer division), slot task_off[b] + p holds part p's sum, and a lane walks one
+ * part -- the task list is ordered by length, longest first -- and stores its sum once.  Same arguments, same jobs, same outputs and
+ * the same refusals as g16_dev_msm_pass_lab, with lmax (8 .. 4096) in place of lseg: task_off is the exclusive prefix of
+ * ceil(counts / lmax), heavy lists the buckets with more than 16 parts, record_cap >= n_sorted / lmax + M + 8.
+ * g16_host_msm_parts_lab is the host twin for G1: one job, the same layout rule and the same per-task walk (part_walk.hpp) compiled for
+ * the host, tasks in slot order; it fills records (n_records of them, no guards: record_cap >= n_sorted / lmax + M), offsets, task_off,
+ * heavy and out_affine, and reads the job through exactly sized copies, so that a sanitizer build sees an index out of range. */
+int g16_dev_msm_parts_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, int lmax, int rows, g16_pass_lab_job* jobs, int n_jobs);
+int g16_host_msm_parts_lab(int curve, int merged, int c, int groups, int lmax, int rows, g16_pass_lab_job* job);
+
 /* ---- the sort lab (test hook): signed digits and the sort layout in place ----
  * Uploads n <= 2^16 scalars (Fr, Montgomery limbs) and calls sort_scalars as the prover does: merged_c = 0 for a per-window plan (window
  * size from the cost model or G16_MSM_WINDOW), 9 .. 20 for a merged plan, shard_n > 1 for rank shard_r's bucket-space share of a merged
