@@ -292,6 +292,9 @@ template <class C> int sort_scalars(const typename C::Fr* d_scalars, uint64_t n,
 static constexpr int COEFF128_SWORDS = 7;   // 32-bit words of rho + K a digits kernel stages: six (the sixth is 0 for c <= 16) + a guard
 int coeffs128_plan(uint64_t n, MsmPlan* plan);
 int sort_digit_planes(const MsmPlan& plan, const uint16_t* planes, uint64_t n, Arena& arena, hipStream_t st, ScalarSort* out);
+// Exclusive prefix sum of `count` u32 values on the device in three launches (msm.hip step 3), prefix[count] = the total.  padmask (a
+// power of two minus one, or 0): every value is rounded up to a multiple of padmask + 1 first.  block_sums: count / 2048 + 1 words of scratch.
+int prefix_scan_u32(const uint32_t* vals, uint32_t* prefix, uint32_t count, uint32_t padmask, uint32_t* block_sums, hipStream_t st);
 // The tail of sort_scalars on its own (the pass lab runs it on caller-made counts): counts[M] -> offsets[M + 1] (every count rounded up
 // to a multiple of 2^R), nparts[M] = segments of length lseg each bucket touches, task_off[M + 1] = their exclusive prefix, and the heavy
 // list (heavy[0], zeroed by the caller, counts the buckets with more than HEAVY_PARTS partial sums; their ids follow in any order).
@@ -299,7 +302,7 @@ int sort_digit_planes(const MsmPlan& plan, const uint16_t* planes, uint64_t n, A
 int msm_slot_layout(const uint32_t* counts, uint32_t M, int R, uint32_t lseg, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off,
                     uint32_t* heavy, uint32_t* block_sums, hipStream_t st);
 
-// The same tail for MSM_WALK_PARTS (partwalk.hip, the part-walk library): counts[M] -> offsets[M + 1], nparts[M] = ceil(count / lmax),
+// The same tail for MSM_WALK_PARTS (partwalk.hip): counts[M] -> offsets[M + 1], nparts[M] = ceil(count / lmax),
 // task_off[M + 1], the heavy list as above, and tasks[task_off[M]]: one descriptor per slot, ordered by length, longest first (a counting
 // sort over the <= lmax lengths: LDS histograms per workgroup, one scan, no global atomics).  8 <= lmax <= PART_MAX_L;
 // scratch: msm_parts_layout_scratch(M, lmax) words of device memory.

@@ -26,7 +26,7 @@
 //                           flushing one partial sum per (bucket, segment) it touches.  ONE launch walks up to four MSMs
 //                           (PassBatch, round 5: the G1 MSMs of a proof that are ready together -- one tail instead of four).
 //                           The prover's merged-window sorts use the BUCKET-PART walk instead (MsmPlan::walk, part_walk.hpp; its
-//                           kernels live in partwalk.hip, a library of their own): one lane (pair) per part of ONE bucket, at most
+//                           kernels live in partwalk.hip, an object of their own): one lane (pair) per part of ONE bucket, at most
 //                           Lmax entries, tasks ordered by length -- no boundary test and no flush in the loop, one store at the end
 //   5b. heavy_reduce_kernel cooperative combine of the FEW buckets with MANY partial sums (> 16)
 //   5c. bucket_combine_kernel (round 5)  every other bucket's partial sums added up by one lane per BUCKET, so that ...
@@ -55,7 +55,6 @@
 #include "msm_common.hpp"
 #include "fp30.hpp"
 #include "acc_store.hpp"
-#include "scan.hpp"
 #include "pass_batch.hpp"
 #include "batch_affine.hpp"
 #include "window_tables.hpp"
@@ -290,10 +289,68 @@ static __global__ __launch_bounds__(SORT_M_THREADS) void bucket_scatter_merged_k
 
 // ---------------------------------------------------------------------------------------------
 // 3. scans over the M = W*B buckets: an exclusive prefix sum of a u32 array in three small coalesced launches
-//    (block sums -> scan of block sums -> write), 2048 values per workgroup.  Used twice: bucket counts -> bucket
-//    offsets, and per-bucket partial-slot counts -> slot offsets.
+//    (block sums -> scan of block sums -> write), 2048 values per workgroup.  Used for bucket counts -> bucket offsets,
+//    per-bucket partial-slot counts -> slot offsets, and the part layout's length matrix (prefix_scan_u32, the one launcher).
 // ---------------------------------------------------------------------------------------------
-// (scan.hpp: SCAN_THREADS, SCAN_TILE, block_exclusive and the three kernels, shared with the part-walk library)
+static constexpr int SCAN_THREADS = 256;
+static constexpr int SCAN_PER_THREAD = 8;
+static constexpr int SCAN_TILE = SCAN_THREADS * SCAN_PER_THREAD;
+
+// exclusive scan of one value per thread across the workgroup; returns the workgroup total through *total
+__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* sh, uint32_t* total) {
+    const uint32_t tid = threadIdx.x;
+    sh[tid] = v;
+    __syncthreads();
+    for (uint32_t d = 1; d < SCAN_THREADS; d <<= 1) {
+        const uint32_t add = tid >= d ? sh[tid - d] : 0u;
+        __syncthreads();
+        sh[tid] += add;
+        __syncthreads();
+    }
+    const uint32_t incl = sh[tid];
+    *total = sh[SCAN_THREADS - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+// `pad` (a power of two minus one, or 0): every value is rounded up to a multiple of pad + 1 before it is summed -- bucket
+// regions of the batched-affine plan start and end on multiples of 2^R entries
+static __global__ __launch_bounds__(SCAN_THREADS) void scan_block_sums_kernel(const uint32_t* __restrict__ vals, uint32_t M, uint32_t pad,
+                                                                       uint32_t* __restrict__ block_sums) {
+    __shared__ uint32_t sa[SCAN_THREADS];
+    const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
+    uint32_t sum = 0, tot;
+    G16_UNROLL for (int j = 0; j < SCAN_PER_THREAD; ++j) sum += (base + j < M) ? ((vals[base + j] + pad) & ~pad) : 0u;
+    (void)block_exclusive(sum, sa, &tot);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
+}
+
+static __global__ __launch_bounds__(SCAN_THREADS) void scan_block_offsets_kernel(uint32_t* __restrict__ block_sums, uint32_t nblocks, uint32_t M,
+                                                                          uint32_t* __restrict__ prefix) {
+    __shared__ uint32_t sa[SCAN_THREADS];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nblocks; base += SCAN_THREADS) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t a = i < nblocks ? block_sums[i] : 0u;
+        uint32_t tot;
+        const uint32_t ea = block_exclusive(a, sa, &tot);
+        if (i < nblocks) block_sums[i] = carry + ea;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) prefix[M] = carry;
+}
+
+static __global__ __launch_bounds__(SCAN_THREADS) void scan_write_kernel(const uint32_t* __restrict__ vals, uint32_t M, uint32_t pad,
+                                                                  const uint32_t* __restrict__ block_base, uint32_t* __restrict__ prefix) {
+    __shared__ uint32_t sa[SCAN_THREADS];
+    const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
+    uint32_t cv[SCAN_PER_THREAD], sum = 0, tot;
+    G16_UNROLL for (int j = 0; j < SCAN_PER_THREAD; ++j) { cv[j] = (base + j < M) ? ((vals[base + j] + pad) & ~pad) : 0u; sum += cv[j]; }
+    uint32_t a = block_base[blockIdx.x] + block_exclusive(sum, sa, &tot);
+    G16_UNROLL for (int j = 0; j < SCAN_PER_THREAD; ++j) {
+        if (base + j < M) { prefix[base + j] = a; a += cv[j]; }
+    }
+}
 
 // partial-sum slots of bucket b = number of length-L segments of the sorted list its entries touch
 // (batched-affine plan: the bucket pass walks the level-R list, whose bucket regions are offsets >> R)
@@ -583,7 +640,7 @@ __device__ __forceinline__ Acc30<F30> gather_acc(const St& st, bool inf) {
 // re-filled dynamically -- and a launch's tail cannot be filled by the next launch of the same stream.  The G1 MSMs of a proof that are
 // ready together (l, a, b_g1 share the witness sort; h joins when its sort is done in time) therefore go as ONE launch: one tail
 // instead of three or four (a rank's share of an 8-way sharded 2^22 proof: 1.3-1.4 ms per pass of 1.1 ms of work, round 5).
-// (pass_batch.hpp: PASS_BATCH and PassBatch, shared with the part-walk library)
+// (pass_batch.hpp: PASS_BATCH and PassBatch, shared with partwalk.hip)
 template <class F30, bool DIRECT>
 __global__ __launch_bounds__(ACC_THREADS, F30::ACC_MIN_WAVES) void bucket_accumulate30_kernel(
     PassBatch<F30> batch, uint32_t M, uint32_t off_shift, uint32_t lseg, uint32_t merged) {
@@ -1046,12 +1103,8 @@ int make_msm_plan(uint64_t n, int scalar_bits, const uint32_t* modulus_words, in
     return G16_OK;
 }
 
-#endif  // G16_MSM_PART == 0
-
-static int ilog2(uint32_t v) { int l = 0; while ((1u << l) < v) ++l; return l; }
-
-// exclusive prefix sum of `count` values (3. above); block_sums: scratch of ceil(count / SCAN_TILE) words
-static int prefix_scan_u32(const uint32_t* vals, uint32_t* prefix, uint32_t count, uint32_t padmask, uint32_t* block_sums, hipStream_t st) {
+// exclusive prefix sum of `count` values (3. above; internal.hpp); block_sums: scratch of ceil(count / SCAN_TILE) words
+int prefix_scan_u32(const uint32_t* vals, uint32_t* prefix, uint32_t count, uint32_t padmask, uint32_t* block_sums, hipStream_t st) {
     const uint32_t nblocks = (count + SCAN_TILE - 1) / SCAN_TILE;
     hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, st, vals, count, padmask, block_sums);
     G16_LAUNCH_CHECK();
@@ -1062,7 +1115,6 @@ static int prefix_scan_u32(const uint32_t* vals, uint32_t* prefix, uint32_t coun
     return G16_OK;
 }
 
-#if G16_MSM_PART == 0
 // The tail of sort_scalars, which the pass lab (unit_api.hpp) runs on caller-made counts: bucket counts -> offsets (every count
 // rounded up to a multiple of 2^R), offsets -> partial-sum slots per bucket and the heavy list, slots -> task_off.
 int msm_slot_layout(const uint32_t* counts, uint32_t M, int R, uint32_t lseg, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off,
@@ -1081,7 +1133,9 @@ int msm_prover_walk() {
     }
     return MSM_WALK_PARTS;
 }
-#endif
+#endif  // G16_MSM_PART == 0
+
+static int ilog2(uint32_t v) { int l = 0; while ((1u << l) < v) ++l; return l; }
 
 template <class C>
 int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Arena& arena, hipStream_t st, ScalarSort* out, int shard_n,
@@ -1443,7 +1497,7 @@ int msm_bucket_pass_batch(const PassJob<F>* jobs, int n, Arena& arena, hipStream
         if (i < n) max_segments = std::max(max_segments, j.ss->max_segments);
     }
     if (bucket_timer) G16_TRY(bucket_timer->start(st));
-    if (max_segments && plan.walk == MSM_WALK_PARTS) {   // max_segments bounds the parts here; the kernel lives in the part-walk library
+    if (max_segments && plan.walk == MSM_WALK_PARTS) {   // max_segments bounds the parts here; the kernel lives in partwalk.hip
         G16_TRY((msm_parts_pass_launch<F30>(b, tb, n, max_segments, plan.buckets(), plan.merged, pass_lds_pad<F30>(), st)));
     } else if (max_segments) {
         const uint64_t lanes = (uint64_t)max_segments * F30::LANES_PER_TASK;

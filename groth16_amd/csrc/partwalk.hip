@@ -1,20 +1,13 @@
-// The part-walk library (libg16_partwalk.so, beside the product library, which links against it): the kernels of the bucket-part
-// walk of the bucket pass (MsmPlan::walk == MSM_WALK_PARTS, part_walk.hpp) and their launchers -- the layout (msm_parts_layout) and the
-// pass (msm_parts_pass_launch).  A translation unit and a code object of their own: the product library's kernels are what they were,
-// instantiation for instantiation.  Nothing here calls back into the product library (errors come back as plain status codes).
+// The kernels of the bucket-part walk of the bucket pass (MsmPlan::walk == MSM_WALK_PARTS, part_walk.hpp) and their launchers -- the
+// layout (msm_parts_layout) and the pass (msm_parts_pass_launch).  A translation unit and a code object of their own inside the product
+// library, so that msm.hip's two objects build as they did without them; the scans are msm.hip's (prefix_scan_u32).
 #include "internal.hpp"
 #include "fp30.hpp"
 #include "acc_store.hpp"
 #include "part_walk.hpp"
-#include "scan.hpp"
 #include "pass_batch.hpp"
 
 namespace g16 {
-
-#define PW_LAUNCH_CHECK()                                    \
-    do {                                                     \
-        if (hipGetLastError() != hipSuccess) return G16_ERR_HIP; \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // The bucket-part layout (MSM_WALK_PARTS, part_walk.hpp): slots per bucket = ceil(count / Lmax), and one task descriptor per
@@ -102,19 +95,6 @@ static __global__ __launch_bounds__(PART_THREADS) void part_place_kernel(const u
     }
 }
 
-
-// exclusive prefix sum of `count` values, prefix[count] = the total (scan.hpp); block_sums: ceil(count / SCAN_TILE) words
-static int pw_scan_u32(const uint32_t* vals, uint32_t* prefix, uint32_t count, uint32_t* block_sums, hipStream_t st) {
-    const uint32_t nblocks = (count + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, st, vals, count, 0u, block_sums);
-    PW_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_block_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, block_sums, nblocks, count, prefix);
-    PW_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_write_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, st, vals, count, 0u, block_sums, prefix);
-    PW_LAUNCH_CHECK();
-    return G16_OK;
-}
-
 int msm_parts_layout(const uint32_t* counts, uint32_t M, uint32_t lmax, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off, uint32_t* heavy,
                      PartTask* tasks, uint32_t* scratch, hipStream_t st) {
     if (lmax < 8 || lmax > PART_MAX_L || M == 0 || !scratch) return G16_ERR_INTERNAL;
@@ -122,15 +102,15 @@ int msm_parts_layout(const uint32_t* counts, uint32_t M, uint32_t lmax, uint32_t
     const uint64_t cells = (uint64_t)lmax * nblk;
     if (cells >= ((uint64_t)1 << 31)) return G16_ERR_INTERNAL;
     uint32_t *len_counts = scratch, *len_off = scratch + cells + 1, *block_sums = scratch + 2 * (cells + 1);   // msm_parts_layout_scratch
-    G16_TRY(pw_scan_u32(counts, offsets, M, block_sums, st));
+    G16_TRY(prefix_scan_u32(counts, offsets, M, 0u, block_sums, st));
     hipLaunchKernelGGL(part_count_kernel, dim3(nblk), dim3(PART_THREADS), (size_t)lmax * sizeof(uint32_t), st, offsets, M, lmax, nparts, heavy,
                        len_counts);
-    PW_LAUNCH_CHECK();
-    G16_TRY(pw_scan_u32(nparts, task_off, M, block_sums, st));
-    G16_TRY(pw_scan_u32(len_counts, len_off, (uint32_t)cells, block_sums, st));
+    G16_LAUNCH_CHECK();
+    G16_TRY(prefix_scan_u32(nparts, task_off, M, 0u, block_sums, st));
+    G16_TRY(prefix_scan_u32(len_counts, len_off, (uint32_t)cells, 0u, block_sums, st));
     hipLaunchKernelGGL(part_place_kernel, dim3(nblk), dim3(PART_THREADS), ((size_t)lmax + 1 + 3 * PART_WIDE_CAP) * sizeof(uint32_t), st, offsets,
                        nparts, task_off, M, lmax, len_off, tasks);
-    PW_LAUNCH_CHECK();
+    G16_LAUNCH_CHECK();
     return G16_OK;
 }
 
@@ -179,7 +159,7 @@ int msm_parts_pass_launch(const PassBatch<F30>& batch, const PartTaskBatch& task
     const uint64_t lanes = (uint64_t)max_tasks * F30::LANES_PER_TASK;
     const dim3 grid((unsigned)((lanes + ACC_THREADS - 1) / ACC_THREADS), (unsigned)n);
     hipLaunchKernelGGL((bucket_parts30_kernel<F30>), grid, dim3(ACC_THREADS), lds_pad, st, batch, tasks, M, merged ? 1u : 0u);
-    PW_LAUNCH_CHECK();
+    G16_LAUNCH_CHECK();
     return G16_OK;
 }
 

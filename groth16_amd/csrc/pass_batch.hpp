@@ -1,4 +1,4 @@
-// The argument block of a batched bucket pass (msm.hip step 5), shared by bucket_accumulate30_kernel and the part-walk library's
+// The argument block of a batched bucket pass (msm.hip step 5), shared by bucket_accumulate30_kernel (msm.hip) and the part walk's
 // bucket_parts30_kernel (partwalk.hip).
 #pragma once
 #include "curve.hpp"

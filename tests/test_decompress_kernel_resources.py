@@ -2,13 +2,12 @@
 power, the base and one product's temporaries; the exponentiation is out of line, so scratch holds little more than the operands
 passed to it.  The figures are the ones the build gives (DESIGN.md 4.6 records them): scratch rounded up to the next KB as a
 ceiling, the waves per SIMD as a floor."""
-import os
-import sys
+import operator
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_inventory as inv
+
 # (kernel, curve): (scratch ceiling in bytes, waves-per-SIMD floor); read: BLS12-381 G1 224 B / 4, G2 912 B / 4,
 # BN254 G1 48 B / 6, G2 480 B / 4
 BUDGET = {
@@ -21,27 +20,18 @@ BUDGET = {
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_occupancy
-
-    import groth16_amd
-
-    return kernel_occupancy.kernels(groth16_amd.lib().path)
+    return inv.kernels()
 
 
 @pytest.mark.parametrize("kernel,curve", sorted(BUDGET))
 def test_decompress_kernel_budget(kernels, kernel, curve):
-    hit = [k for n, k in kernels.items() if kernel in n and curve in n]
-    assert len(hit) == 1, hit
-    (k,) = hit
     scratch, waves = BUDGET[(kernel, curve)]
-    assert k["max_flat_wg"] == 64, k
-    assert k["lds"] == 0, k
-    assert k["scratch"] <= scratch <= 16 * 1024, k
-    assert k["waves_per_simd"] >= waves >= 2, k
+    assert scratch <= 16 * 1024 and waves >= 2
+    inv.check_budget(inv.one(kernels, kernel, curve), wg=64, scratch=scratch, lds=0, waves=waves, lds_cmp=operator.eq)
 
 
 def test_combine_kernel_and_names(kernels):
-    (k,) = [k for n, k in kernels.items() if "decompress_combine_kernel" in n]
+    k = inv.one(kernels, "decompress_combine_kernel")
     assert k["scratch"] == 0 and k["lds"] == 0, k
     others = ("subgroup_", "verify_agg_", "verify_batch_kernel", "pairing_", "verify_window_table_kernel")
     mine = [n for n in kernels if "decompress_" in n]

@@ -4,30 +4,17 @@ The bucket passes and the NTT kernels sit right at resource cliffs the compiler 
 a kernel from two waves per SIMD to one (round 2: 10.1 -> 12.5 ms per G1 bucket pass), and an unrolled block past LLVM's pragma-
 unroll cap leaves the butterfly registers in scratch memory (NTT 6.3 -> 11.4 ms).  Both regressions were silent -- every parity
 test stayed green -- so the budgets are asserted here."""
-import os
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_inventory as inv
+from kernel_inventory import pick
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_occupancy
-
-    import groth16_amd
-
-    ks = kernel_occupancy.kernels(groth16_amd.lib().path)
+    ks = inv.kernels()
     assert len(ks) > 40, "could not read the code objects of the built library"
     return ks
-
-
-def pick(kernels, *subs):
-    hit = {n: k for n, k in kernels.items() if all(s in n for s in subs)}
-    assert hit, f"no kernel matches {subs}"
-    return hit
 
 
 @pytest.mark.parametrize("curve,limbs", [("Bls12_381FqP", 13), ("Bn254FqP", 9)])

@@ -2,13 +2,12 @@
 root: a lane range-checks two or four coordinates, converts them and evaluates the curve equation once, so it stays inside the
 budget the decompression kernels meet -- scratch <= 1 KB, >= 4 waves per SIMD -- and the figures pinned here are the ones the build
 gives (DESIGN.md 4.7 records them).  The compressed decode and the membership tests are NOT instantiated a second time."""
-import os
-import sys
+import operator
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_inventory as inv
+
 CEILING_SCRATCH, FLOOR_WAVES = 1024, 4
 # (kernel, curve): (scratch in bytes, waves per SIMD) as built: BLS12-381 G1 224 B / 4, G2 976 B / 4, BN254 G1 0 B / 8, G2 368 B / 7
 BUILT = {
@@ -21,27 +20,18 @@ BUILT = {
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_occupancy
-
-    import groth16_amd
-
-    return kernel_occupancy.kernels(groth16_amd.lib().path)
+    return inv.kernels()
 
 
 @pytest.mark.parametrize("kernel,curve", sorted(BUILT))
 def test_decode_kernel_budget(kernels, kernel, curve):
-    hit = [k for n, k in kernels.items() if kernel in n and curve in n]
-    assert len(hit) == 1, hit
-    (k,) = hit
     scratch, waves = BUILT[(kernel, curve)]
-    assert k["max_flat_wg"] == 64, k
-    assert k["lds"] == 0, k
-    assert k["scratch"] <= scratch <= CEILING_SCRATCH, k
-    assert k["waves_per_simd"] >= waves >= FLOOR_WAVES, k
+    assert scratch <= CEILING_SCRATCH and waves >= FLOOR_WAVES
+    inv.check_budget(inv.one(kernels, kernel, curve), wg=64, scratch=scratch, lds=0, waves=waves, lds_cmp=operator.eq)
 
 
 def test_fold_kernel_and_names(kernels):
-    (k,) = [k for n, k in kernels.items() if "keyload_fold_kernel" in n]
+    k = inv.one(kernels, "keyload_fold_kernel")
     assert k["scratch"] == 0 and k["lds"] == 0 and k["max_flat_wg"] == 256 and k["waves_per_simd"] == 8, k
     mine = sorted(n for n in kernels if "keyload_" in n)
     assert len(mine) == 5, mine   # two decode kernels per curve and the fold

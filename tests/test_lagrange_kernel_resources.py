@@ -2,15 +2,13 @@
 first build as ceilings / floors.  lagrange_twiddle_mul_kernel is phase 1's windowed task behind a twiddle read from
 the power table: the registers of batch_scalar_mul_kernel, two waves per SIMD, no scratch in any instantiation.
 lagrange_addsub_kernel holds two affine points, one inversion and the two chords.  lagrange_bitrev_kernel copies.  The library holds
-nothing else; the other libraries' inventories are pinned by their own resource tests."""
+nothing else; every library's inventory is tests/kernel_inventory.py's."""
 import os
 import re
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_inventory as inv
 
 # kernel name prefix: (vector registers incl. accumulation registers, scratch bytes, LDS bytes, waves per SIMD, workgroup) as built
 BUILT = {
@@ -31,41 +29,24 @@ BUILT = {
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_occupancy
-
-    import groth16_amd
-
-    path = os.path.join(os.path.dirname(groth16_amd.lib().path), "libg16_lagrange.so")
-    assert os.path.exists(path), path
-    return kernel_occupancy.kernels(path)
-
-
-def _one(kernels, prefix):
-    hit = [k for n, k in kernels.items() if n.replace(" ", "").startswith(prefix.replace(" ", ""))]
-    assert len(hit) == 1, (prefix, sorted(kernels))
-    return hit[0]
+    return inv.kernels("libg16_lagrange.so")
 
 
 @pytest.mark.parametrize("kernel", sorted(BUILT))
 def test_lagrange_kernel_budget(kernels, kernel):
-    k = _one(kernels, kernel)
     regs, scratch, lds, waves, wg = BUILT[kernel]
-    assert k["max_flat_wg"] == wg, k
-    assert k["vgpr"] + k["agpr"] <= regs, k
-    assert k["scratch"] <= scratch, k
-    assert k["lds"] <= lds, k
-    assert k["waves_per_simd"] >= waves, k
+    inv.check_budget(inv.one(kernels, prefix=kernel), wg, regs, scratch, lds, waves)
 
 
 def test_names_and_counts(kernels):
     assert len(kernels) == len(BUILT), sorted(kernels)   # the code object holds the three kernels' twelve instantiations and nothing else
     for prefix in BUILT:
-        _one(kernels, prefix)
+        inv.one(kernels, prefix=prefix)
 
 
 def test_stage_kernels_use_no_scratch_at_two_waves(kernels):
     for prefix in BUILT:
-        k = _one(kernels, prefix)
+        k = inv.one(kernels, prefix=prefix)
         assert k["scratch"] == 0 and k["waves_per_simd"] >= 2, (prefix, k)
 
 
@@ -76,5 +57,5 @@ def test_header_matches_exports():
     lag = groth16_amd.lib().lag
     for name in binding.LAGRANGE_EXPORTS:
         assert hasattr(lag, name), name
-    hdr = open(os.path.join(ROOT, "include", "g16_lagrange.h")).read()
+    hdr = open(os.path.join(inv.ROOT, "include", "g16_lagrange.h")).read()
     assert set(re.findall(r"\b(g16_[a-z0-9_]+)\s*\(", hdr)) == set(binding.LAGRANGE_EXPORTS)

@@ -104,6 +104,15 @@ def test_host_twin_refusals(lib, cfg):
     assert host(lib, (curve, g2, merged, lmax), base)[0] == G16_OK
 
 
+def test_layout_launcher_refuses_a_short_lmax(lib):
+    """msm_parts_layout (partwalk.hip, an object of the product library) turns down lmax < 8 with G16_ERR_INTERNAL before it touches the device"""
+    import ctypes
+
+    fn = ctypes.CDLL(lib.path)["_ZN3g1616msm_parts_layoutEPKjjjPjS2_S2_S2_PNS_8PartTaskES2_P12ihipStream_t"]
+    scratch = (ctypes.c_uint32 * 4)()
+    assert fn(None, ctypes.c_uint32(qc.M), ctypes.c_uint32(7), None, None, None, None, None, scratch, None) == 7   # G16_ERR_INTERNAL
+
+
 def test_job_dump_for_the_replay_program(lib, tmp_path):
     """the file tests/parts_walk_replay.cpp reads: one record per (G1 configuration, job), the job and this build's outputs"""
     items = []

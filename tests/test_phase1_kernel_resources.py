@@ -1,16 +1,13 @@
 """CPU tier: the kernels of phase 1, read from the built companion library (libg16_phase1.so), held to the figures of the first build
  as ceilings / floors.  batch_scalar_mul_kernel keeps the accumulator and the live values of one addition in registers
 and the table in HBM: two waves per SIMD, no scratch in any instantiation.  phase1_powers_kernel calls the out-of-line exponentiation
-once per lane, hence its small stack.  The library holds nothing else; the other two libraries' inventories are pinned by
-test_ceremony_kernel_resources.py."""
+once per lane, hence its small stack.  The library holds nothing else; every library's inventory is tests/kernel_inventory.py's."""
 import os
 import re
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_inventory as inv
 
 # kernel name prefix: (vector registers incl. accumulation registers, scratch bytes, LDS bytes, waves per SIMD, workgroup) as built
 BUILT = {
@@ -25,42 +22,25 @@ BUILT = {
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_occupancy
-
-    import groth16_amd
-
-    path = os.path.join(os.path.dirname(groth16_amd.lib().path), "libg16_phase1.so")
-    assert os.path.exists(path), path
-    return kernel_occupancy.kernels(path)
-
-
-def _one(kernels, prefix):
-    hit = [k for n, k in kernels.items() if n.replace(" ", "").startswith(prefix.replace(" ", ""))]
-    assert len(hit) == 1, (prefix, sorted(kernels))
-    return hit[0]
+    return inv.kernels("libg16_phase1.so")
 
 
 @pytest.mark.parametrize("kernel", sorted(BUILT))
 def test_phase1_kernel_budget(kernels, kernel):
-    k = _one(kernels, kernel)
     regs, scratch, lds, waves, wg = BUILT[kernel]
-    assert k["max_flat_wg"] == wg, k
-    assert k["vgpr"] + k["agpr"] <= regs, k
-    assert k["scratch"] <= scratch, k
-    assert k["lds"] <= lds, k
-    assert k["waves_per_simd"] >= waves, k
+    inv.check_budget(inv.one(kernels, prefix=kernel), wg, regs, scratch, lds, waves)
 
 
 def test_names_and_counts(kernels):
     assert len(kernels) == len(BUILT), sorted(kernels)   # the code object holds the two kernels' six instantiations and nothing else
     for prefix in BUILT:
-        _one(kernels, prefix)
+        inv.one(kernels, prefix=prefix)
 
 
 def test_scalar_mul_kernels_use_no_scratch_at_two_waves(kernels):
     for prefix in BUILT:
         if prefix.startswith("batch_scalar_mul_kernel"):
-            k = _one(kernels, prefix)
+            k = inv.one(kernels, prefix=prefix)
             assert k["scratch"] == 0 and k["waves_per_simd"] >= 2, (prefix, k)
 
 
@@ -71,5 +51,5 @@ def test_header_matches_exports():
     ph1 = groth16_amd.lib().ph1
     for name in binding.PHASE1_EXPORTS:
         assert hasattr(ph1, name), name
-    hdr = open(os.path.join(ROOT, "include", "g16_phase1.h")).read()
+    hdr = open(os.path.join(inv.ROOT, "include", "g16_phase1.h")).read()
     assert set(re.findall(r"\b(g16_[a-z0-9_]+)\s*\(", hdr)) == set(binding.PHASE1_EXPORTS)

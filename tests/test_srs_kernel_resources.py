@@ -2,15 +2,13 @@
 per lane in 64-lane groups and uses no LDS.  The two that multiply by a full-size scalar (the butterfly and the column sum) are the
 heavy ones -- a complete addition, a doubling and the scalar's words live at once, and the words are indexed at run time -- so they
 sit at one or two waves per SIMD with kilobytes of scratch; the figures pinned here are the ones the build gives (DESIGN.md 4.8
-records them) and are ceilings / floors, not targets met.  The fixed-base kernels the SRS generator borrows, and every kernel the
-other resource tests name, are instantiated exactly as often as before."""
-import os
-import sys
+records them) and are ceilings / floors, not targets met.  How often the fixed-base kernels the SRS generator borrows, and every
+other kernel, are instantiated is tests/kernel_inventory.py's to say."""
+import operator
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_inventory as inv
 
 G1_BLS, G2_BLS, G1_BN, G2_BN = "Fp<Bls12_381FqP>", "Fp2<Bls12_381FqP>", "Fp<Bn254FqP>", "Fp2<Bn254FqP>"
 # (kernel, coordinate field): (vector registers incl. accumulation registers, scratch bytes, waves per SIMD) as built
@@ -30,37 +28,17 @@ BUILT = {
     ("srs_diff_kernel", G1_BLS): (134, 928, 3), ("srs_diff_kernel", G1_BN): (112, 208, 4),
     ("srs_scale_kernel", G1_BLS): (122, 976, 4), ("srs_scale_kernel", G1_BN): (188, 208, 2),
 }
-# instantiations per name the other resource tests search for, counted in the library as it was before this translation unit existed
-BEFORE = {'fixed_base_mul_kernel': 4, 'fixed_base_table_kernel': 4, 'keyload_': 5, 'decompress_': 5, 'subgroup_': 5, 'verify_mixed_': 12,
-          'verify_agg_': 8, 'verify_batch_kernel': 2, 'pairing_': 4, 'bucket_accumulate30_kernel': 8, 'ntt30_': 6, 'digits_kernel': 2,
-          'build_window_tables_kernel': 4, 'spmv3_kernel': 2, 'spmv_circom_kernel': 2, 'circom_h_kernel': 2, 'quotient_kernel': 2,
-          'r1cs_check_kernel': 2, 'r1cs_row_values_kernel': 2, 'sub_count_kernel': 1, 'sub_partition_kernel': 1, 'final_sort_kernel': 1,
-          'bitrev_scale_kernel': 2, 'class_count_kernel': 2, 'class_partition_kernel': 2, 'bucket_count_merged_kernel': 1,
-          'bucket_scatter_merged_kernel': 1, 'bucket_wg_scan_kernel': 1, 'dwm_column_kernel': 20, 'bucket_reduce_kernel<': 4,
-          'window_reduce_kernel<': 4, 'heavy_reduce_kernel<': 4, 'bucket_combine_kernel<': 4, 'bucket_slots_kernel': 1,
-          'scan_block_sums_kernel': 1, 'scan_block_offsets_kernel': 1, 'scan_write_kernel': 1, 'verify_window_table_kernel': 2}
-TOTAL_BEFORE = 163
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_occupancy
-
-    import groth16_amd
-
-    return kernel_occupancy.kernels(groth16_amd.lib().path)
+    return inv.kernels()
 
 
 @pytest.mark.parametrize("kernel,field", sorted(BUILT))
 def test_srs_kernel_budget(kernels, kernel, field):
-    hit = [k for n, k in kernels.items() if n.startswith(kernel + "<" + field)]
-    assert len(hit) == 1, (kernel, field, [n for n in kernels if kernel in n])
-    (k,) = hit
     regs, scratch, waves = BUILT[(kernel, field)]
-    assert k["max_flat_wg"] == 64 and k["lds"] == 0, k
-    assert k["vgpr"] + k["agpr"] <= regs, k
-    assert k["scratch"] <= scratch, k
-    assert k["waves_per_simd"] >= waves, k
+    inv.check_budget(inv.one(kernels, prefix=kernel + "<" + field), 64, regs, scratch, 0, waves, lds_cmp=operator.eq)
 
 
 def test_srs_kernel_names_and_counts(kernels):
@@ -75,7 +53,6 @@ def test_srs_kernel_names_and_counts(kernels):
 
 
 def test_existing_instantiations_unchanged(kernels):
-    """the SRS generator borrows fixed_base_mul_kernel / fixed_base_table_kernel as they are; nothing else gained or lost a kernel"""
-    for sub, count in BEFORE.items():
-        assert len([n for n in kernels if sub in n]) == count, sub
-    assert len([n for n in kernels if "srs_" not in n]) == TOTAL_BEFORE
+    """the SRS generator borrows fixed_base_mul_kernel / fixed_base_table_kernel as they are: four instantiations each, as the inventory says"""
+    for sub in ("fixed_base_mul_kernel", "fixed_base_table_kernel"):
+        assert len(inv.pick(kernels, sub)) == 4 == inv.INVENTORY[inv.MAIN][sub], sub

@@ -2,13 +2,12 @@
 accumulator and Fq / Fq2 products only, so they stay far below the pairing kernels' scratch and above their two waves per SIMD.
 The figures are the ones the build gives (DESIGN.md 4.6 records them): scratch rounded up to the next KB as a ceiling, the waves
 per SIMD as a floor."""
-import os
-import sys
+import operator
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_inventory as inv
+
 # (kernel, curve): (scratch ceiling in bytes, waves-per-SIMD floor); read: BLS12-381 G1 816 B / 4, G2 3552 B / 4,
 # BN254 G1 0 B / 8 (on-curve test only), G2 2032 B / 4
 BUDGET = {
@@ -21,27 +20,18 @@ BUDGET = {
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_occupancy
-
-    import groth16_amd
-
-    return kernel_occupancy.kernels(groth16_amd.lib().path)
+    return inv.kernels()
 
 
 @pytest.mark.parametrize("kernel,curve", sorted(BUDGET))
 def test_membership_kernel_budget(kernels, kernel, curve):
-    hit = [k for n, k in kernels.items() if kernel in n and curve in n]
-    assert len(hit) == 1, hit
-    (k,) = hit
     scratch, waves = BUDGET[(kernel, curve)]
-    assert k["max_flat_wg"] == 64, k
-    assert k["lds"] == 0, k
-    assert k["scratch"] <= scratch <= 16 * 1024, k
-    assert k["waves_per_simd"] >= waves >= 2, k
+    assert scratch <= 16 * 1024 and waves >= 2
+    inv.check_budget(inv.one(kernels, kernel, curve), wg=64, scratch=scratch, lds=0, waves=waves, lds_cmp=operator.eq)
 
 
 def test_combine_kernel_and_names(kernels):
-    (k,) = [k for n, k in kernels.items() if "subgroup_combine_kernel" in n]
+    k = inv.one(kernels, "subgroup_combine_kernel")
     assert k["scratch"] == 0 and k["lds"] == 0, k
     others = ("verify_agg_", "verify_batch_kernel", "pairing_", "verify_window_table_kernel", "bucket_accumulate30_kernel", "ntt30_",
               "digits_kernel", "build_window_tables_kernel", "spmv3_kernel")

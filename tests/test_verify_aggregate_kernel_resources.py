@@ -1,49 +1,31 @@
 """CPU tier: budgets of the aggregate verifier's kernels (verify_aggregate.hip), read from the built library.  The per-proof
 stage keeps what tests/test_verify_kernel_resources.py demands of verify_batch_kernel: scratch <= 16 KB per lane, two waves per
 SIMD, 64-lane workgroups (the wave reduction moves values across the lanes of ONE wave)."""
-import os
-import sys
+import operator
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_inventory as inv
+
 CURVES = ["Bls12_381FqP", "Bn254FqP"]
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_occupancy
-
-    import groth16_amd
-
-    return kernel_occupancy.kernels(groth16_amd.lib().path)
-
-
-def pick(kernels, *subs):
-    hit = {n: k for n, k in kernels.items() if all(s in n for s in subs)}
-    assert hit, f"no kernel matches {subs}"
-    return hit
+    return inv.kernels()
 
 
 @pytest.mark.parametrize("curve", CURVES)
 @pytest.mark.parametrize("kernel", ["verify_agg_miller_kernel", "verify_agg_reduce_kernel"])
 def test_pairing_stage_budget(kernels, kernel, curve):
-    (k,) = pick(kernels, kernel, curve).values()
-    assert k["waves_per_simd"] >= 2, k
-    assert k["lds"] == 0, k
-    assert k["scratch"] <= 16 * 1024, k
-    assert k["max_flat_wg"] == 64, k
+    inv.check_budget(inv.one(kernels, kernel, curve), wg=64, scratch=16 * 1024, lds=0, waves=2, lds_cmp=operator.eq)
 
 
 @pytest.mark.parametrize("curve", CURVES)
 def test_scalar_stage_budget(kernels, curve):
     """Fr sums: registers only, one Fr per lane of LDS for the workgroup's tree"""
     for sub, lanes in (("verify_agg_scalar_kernel", 256), ("verify_agg_scalar_reduce_kernel", 64)):
-        (k,) = pick(kernels, sub, curve).values()
-        assert k["scratch"] == 0, k
-        assert k["lds"] == 32 * lanes, k
-        assert k["waves_per_simd"] >= 4, k
+        inv.check_budget(inv.one(kernels, sub, curve), scratch=0, lds=32 * lanes, waves=4, lds_cmp=operator.eq)
 
 
 def test_names_stay_out_of_the_other_budgets(kernels):

@@ -2,13 +2,12 @@
 that run Miller loops or multiply Fq12 values across a wave are held to what tests/test_verify_aggregate_kernel_resources.py
 demands of their single-key counterparts: two waves per SIMD, scratch <= 16 KB per lane, 64-lane workgroups (the wave reductions
 move values across the lanes of ONE wave)."""
-import os
-import sys
+import operator
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_inventory as inv
+
 CURVES = ["Bls12_381", "Bn254"]
 MILLER = ["verify_mixed_miller_kernel", "verify_mixed_key_kernel", "verify_mixed_delta_kernel", "verify_mixed_reduce_kernel"]
 ALL = MILLER + ["verify_mixed_scalar_kernel", "verify_mixed_csum_kernel"]
@@ -16,40 +15,20 @@ ALL = MILLER + ["verify_mixed_scalar_kernel", "verify_mixed_csum_kernel"]
 
 @pytest.fixture(scope="module")
 def kernels():
-    import kernel_occupancy
-
-    import groth16_amd
-
-    return kernel_occupancy.kernels(groth16_amd.lib().path)
-
-
-def pick(kernels, *subs):
-    hit = {n: k for n, k in kernels.items() if all(s in n for s in subs)}
-    assert len(hit) == 1, f"{len(hit)} kernels match {subs}"
-    return next(iter(hit.values()))
+    return inv.kernels()
 
 
 @pytest.mark.parametrize("curve", CURVES)
 @pytest.mark.parametrize("kernel", MILLER)
 def test_pairing_stage_budget(kernels, kernel, curve):
-    k = pick(kernels, kernel, curve)
-    assert k["waves_per_simd"] >= 2, k
-    assert k["lds"] == 0, k
-    assert k["scratch"] <= 16 * 1024, k
-    assert k["max_flat_wg"] == 64, k
+    inv.check_budget(inv.one(kernels, kernel, curve), wg=64, scratch=16 * 1024, lds=0, waves=2, lds_cmp=operator.eq)
 
 
 @pytest.mark.parametrize("curve", CURVES)
 def test_scalar_and_sum_stage_budget(kernels, curve):
     """Fr sums: registers only, one Fr per lane of LDS for the workgroup's tree; the per-key sum of the records: one wave"""
-    k = pick(kernels, "verify_mixed_scalar_kernel", curve)
-    assert k["scratch"] == 0, k
-    assert k["lds"] == 32 * 256, k
-    assert k["waves_per_simd"] >= 4, k
-    k = pick(kernels, "verify_mixed_csum_kernel", curve)
-    assert k["max_flat_wg"] == 64, k
-    assert k["waves_per_simd"] >= 2, k
-    assert k["scratch"] <= 16 * 1024, k
+    inv.check_budget(inv.one(kernels, "verify_mixed_scalar_kernel", curve), scratch=0, lds=32 * 256, waves=4, lds_cmp=operator.eq)
+    inv.check_budget(inv.one(kernels, "verify_mixed_csum_kernel", curve), wg=64, scratch=16 * 1024, waves=2)
 
 
 def test_names_stay_out_of_the_other_budgets(kernels):

@@ -35,8 +35,15 @@ def code_objects(path, arch="gfx950"):
 
 
 def kernels(path):
-    out = {}
+    """demangled name -> figures, over all code objects of the library (two `static` kernels of one name in two objects look like one)"""
+    return {name: k for obj in kernels_per_object(path) for name, k in obj.items()}
+
+
+def kernels_per_object(path):
+    """one {demangled name -> figures} per gfx950 code object of the library, in file order"""
+    res = []
     for blob in code_objects(path):
+        out = {}
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(blob)
             f.flush()
@@ -50,14 +57,16 @@ def kernels(path):
             out[sym] = dict(vgpr=int(get("vgpr_count") or 0), agpr=int(get("agpr_count") or 0), sgpr=int(get("sgpr_count") or 0),
                             scratch=int(get("private_segment_fixed_size") or 0), lds=int(get("group_segment_fixed_size") or 0),
                             max_flat_wg=int(get("max_flat_workgroup_size") or 0))
-    names = list(out)
-    dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
-    res = {}
-    for sym, d in zip(names, dem):
-        k = out[sym]
-        regs = (k["vgpr"] + 7) // 8 * 8   # .vgpr_count is the unified total (arch VGPRs + AGPRs)
-        k["waves_per_simd"] = min(8, 512 // regs) if regs else 8
-        res[re.sub(r"g16::", "", re.sub(r"\(.*", "", d)).replace("void ", "")] = k
+        names = list(out)
+        dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
+        obj = {}
+        for sym, d in zip(names, dem):
+            k = out[sym]
+            regs = (k["vgpr"] + 7) // 8 * 8   # .vgpr_count is the unified total (arch VGPRs + AGPRs)
+            k["waves_per_simd"] = min(8, 512 // regs) if regs else 8
+            d = d.replace("(anonymous namespace)::", "")   # the labs' kernels: named like the rest, not cut at that parenthesis
+            obj[re.sub(r"g16::", "", re.sub(r"\(.*", "", d)).replace("void ", "")] = k
+        res.append(obj)
     return res
 
 
