@@ -246,6 +246,7 @@ EXPORTS = [
     "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
     "g16_dev_fp30_op", "g16_host_fp30_op", "g16_dev_msm_reduce_lab", "g16_dev_window_table_lab", "g16_dev_pairing_op", "g16_host_pairing_op",
+    "g16_dev_std_op", "g16_host_std_op",
     "g16_dev_msm_pass_lab", "g16_dev_msm_sort_lab", "g16_dev_msm_parts_lab", "g16_host_msm_parts_lab",
     "g16_dev_pvk_tables", "g16_dev_prepare_inputs", "g16_host_pvk_tables", "g16_host_prepare_inputs",
     "g16_check_subgroups", "g16_check_proof_subgroups", "g16_verify_aggregate_checked", "g16_host_check_subgroups",
@@ -479,6 +480,8 @@ class Lib:
         c.g16_host_fp30_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_dev_pairing_op.argtypes = [C.c_void_p, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_pairing_op.argtypes = [C.c_int, C.c_int, u32p, C.c_uint64, u32p]
+        c.g16_dev_std_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
+        c.g16_host_std_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_dev_msm_reduce_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u32p, u32p, C.c_uint64, u32p, u64p]
         c.g16_dev_window_table_lab.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, C.c_int, C.c_int, u64p]
         c.g16_dev_msm_pass_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PassLabJobC),

@@ -496,7 +496,11 @@ int g16_deserialize_points(int curve, int g2, int compressed, const uint8_t* in,
                            uint64_t* points_out);
 
 /* ---- host-side arithmetic self-test hooks (CPU; used by the `not gpu` tests) ----
- * The same field / group code the kernels use, compiled for the host.  They ship IN the product library on purpose: the CPU tier --
+ * The same field / group code the kernels use, compiled for the host -- with one exception: the Montgomery product.  On the host
+ * Fp::operator* runs a 64-bit-limb body (Fp::mul_host64), on the device the 32-bit operand-scanning body (Fp::mul_cios32); +, -,
+ * to_canonical and the group formulas are one text for both.  These hooks therefore run the host's product; the device's is tested
+ * by the standard-form lab below (g16_host_std_op forms 14 / 15 / 18 on the CPU, g16_dev_std_op on the GPU).
+ * They ship IN the product library on purpose: the CPU tier --
  * the only tier that runs where the library is built, a container without a GPU -- checks the 30-bit lazy arithmetic, its overflow
  * and bound proofs, the window-table tasks and the bucket-method model (g16_host_selftest, g16_host_msm_model[_shard]) on exactly the
  * code objects the kernels are generated from.  None of them is on a proof's path; none touches a GPU.
@@ -594,6 +598,27 @@ int g16_dev_window_table_lab(g16_ctx* ctx, int g2, const uint64_t* points, uint6
  * G16_ERR_BAD_ARG for an unknown form, a null pointer, n == 0 or n > 2^22. */
 int g16_dev_pairing_op(g16_ctx* ctx, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
 int g16_host_pairing_op(int curve, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
+
+/* ---- the standard-form lab (test hooks): ONE operation of csrc/field.hpp and csrc/curve.hpp on the ABI's own words ----
+ * g16_dev_std_op runs one tuple per lane, in workgroups of 64, on the ctx's (first) GPU and its curve, g16_host_std_op the same code
+ * compiled for the host.  kind: 0 Fr, 1 Fq, 2 Fq2, 3 G1, 4 G2.  A slot is one base-field element in the ABI's form: the Fp<P>'s 32-bit
+ * words (8 for Fr and for BN254's Fq, 12 for BLS12-381's Fq), Montgomery, canonical (below p); Fq2 is 2 slots (c0 c1).  operands: n
+ * tuples of `in` slots; out: n tuples of `out` slots.  form (in -> out slots):
+ *   Fp    0 a + b (2->1)  1 a - b  2 neg (1)  3 dbl (1)  4 a * b through operator* (2; out of line for BLS12-381's Fq)  5 sqr (1)
+ *         6 inverse (1; of zero: zero)  7 to_canonical (1 -> plain words)  8 from_canonical (plain words below p -> 1)
+ *         9 flags (a b -> word 0 is_zero(a), word 1 is_one(a), word 2 a == b)
+ *         14 a * b, 15 sqr, 18 from_canonical through Fp::mul_cios32 BY NAME: the device's 32-bit product on the host too.  On the
+ *         device 4 / 5 / 8 run that body as well; on the host they run the 64-bit body (mul_host64) the host glue runs per proof
+ *   Fp2   0 a + b (4->2)  1 a - b  2 neg (2)  3 dbl (2)  4 a * b (Karatsuba; 4->2)  5 sqr (complex squaring; 2)  6 inverse (2; of zero: zero)
+ *   group (C = 1 slot per coordinate for G1, 2 for G2; an affine point is x y, the identity all zero; a raw XYZZ record is x y zz zzz,
+ *         the identity any record with zz = 0)
+ *         0 from_affine(P) then add_affine(Q) (4 C -> 4 C)  1 add of two raw records (8 C -> 4 C)  2 dbl of a raw record (4 C)
+ *         3 dbl_affine (2 C -> 4 C)  4 neg of a raw record (4 C)  5 mul_bits: a raw record | words 0..7 of a slot the scalar | word 0 of
+ *         a slot the bit count, <= 256 (clamped) (4 C + 2 -> 4 C)  6 to_affine of a raw record (4 C -> 2 C)
+ *         XYZZ results come back raw (x y zz zzz as the formula left them), not normalised.
+ * Nothing is checked about the operands.  G16_ERR_BAD_ARG for an unknown kind or form, a null pointer, n == 0 or n > 2^22. */
+int g16_dev_std_op(g16_ctx* ctx, int kind, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
+int g16_host_std_op(int curve, int kind, int form, const uint32_t* operands, uint64_t n, uint32_t* out);
 
 /* ---- the reduction lab (test hook): the MSM reductions alone, on caller-made partial sums ----
  * Fills a plan (merged: 0 per-window fold, 1 merged fold; `groups` groups of 2^(c-1) buckets, 2 <= c <= 16; G = 8, 16 or 32 buckets

@@ -36,8 +36,8 @@ INVENTORY = {
         "verify_mixed_reduce_kernel": 2, "verify_mixed_scalar_kernel": 2, "subgroup_combine_kernel": 1, "subgroup_g1_kernel": 2,
         "subgroup_g2_kernel": 2, "decompress_combine_kernel": 1, "decompress_g1_kernel": 2, "decompress_g2_kernel": 2,
         "keyload_decode_g1_kernel": 2, "keyload_decode_g2_kernel": 2, "keyload_fold_kernel": 1,
-        # the labs (test hooks): devtest.hip, towerlab.hip, preplab.hip
-        "devlab_op<": 162, "devlab_tower_op<": 2, "devlab_prepare_inputs<": 2,
+        # the labs (test hooks): devtest.hip, towerlab.hip, preplab.hip, stdlab.hip
+        "devlab_op<": 162, "devlab_tower_op<": 2, "devlab_prepare_inputs<": 2, "devlab_std_op<": 10,
     },
     "libg16_ceremony.so": {"ceremony_digits128_kernel": 1, "ceremony_first_bad_kernel": 1},
     "libg16_phase1.so": {"batch_scalar_mul_kernel": 4, "phase1_powers_kernel": 2},
