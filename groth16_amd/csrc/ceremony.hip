@@ -8,7 +8,7 @@
 // array survives with probability <= 2^-128: the difference of the two sides is a non-zero linear form in the rho_i).  The sums are
 // MSMs with SHORT scalars, so the pipeline is the prover's with a new front:
 //   upload X once -> membership (verify_subgroup.hip's kernels, on that copy) -> ceremony_first_bad_kernel
-//   -> ceremony_digits128_kernel + sort_digit_planes (msm.hip: the per-window histogram / scatter) under coeffs128_plan: a plan over
+//   -> ceremony_digits128_kernel + sort_digit_planes (msm_sort.hip: the per-window histogram / scatter) under coeffs128_plan: a plan over
 //      128 bits, half the windows of Fr
 //   -> convert_bases in place -> msm_bucket_pass_batch: lo and hi are the SAME sort read with shift 0 and shift 1, and every array of
 //      one call shares that sort (a shorter array skips the entries beyond its end: the pass's base_count test)

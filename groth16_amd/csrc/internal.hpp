@@ -207,7 +207,7 @@ template <class C> void dwm_destroy(DistWm<C>* d);
 template <class C> int dwm_stage(const DeviceCircuit<C>* ck, const DistWm<C>* dw, int stage, const typename C::Fr* d_z,
                                  typename C::Fr* const work[3], typename C::Fr* const recv[3], typename C::Fr* h_local, hipStream_t st);
 
-// ---- MSM (msm.hip) ----------------------------------------------------------------------------
+// ---- MSM (msm.hip's header maps the steps); first the plan (msm_plan.hip) -----------------------------------------------------
 struct MsmPlan {
     int c = 0;          // window bits
     int W = 0;          // windows
@@ -268,6 +268,7 @@ int msm_plan_windows(int c, int scalar_bits, const uint32_t* modulus_words, int 
 // 8 until round 5: a bucket-space shard's top-window buckets hold ~2x the mean (224 entries = 8 - 9 segments of 32), thousands of them
 // just over the threshold, and the cooperative kernel -- a 128-lane tree per bucket -- took 0.5 - 0.9 ms per MSM in the tail of the proof.
 static constexpr uint32_t HEAVY_PARTS = 16;
+// -- the sort (msm_sort.hip)
 // digit extraction + bucket sort of one scalar array, shared by every MSM over those scalars
 struct ScalarSort {
     MsmPlan plan;
@@ -290,7 +291,7 @@ template <class C> int sort_scalars(const typename C::Fr* d_scalars, uint64_t n,
 // carry, and the per-window sort from its second step on over digit planes the caller made (W planes of n u16 digits of
 // scalar + plan.K, as digits_kernel writes them; device memory) -- histogram, slot layout, scatter
 static constexpr int COEFF128_SWORDS = 7;   // 32-bit words of rho + K a digits kernel stages: six (the sixth is 0 for c <= 16) + a guard
-int coeffs128_plan(uint64_t n, MsmPlan* plan);
+int coeffs128_plan(uint64_t n, MsmPlan* plan);   // (msm_plan.hip)
 int sort_digit_planes(const MsmPlan& plan, const uint16_t* planes, uint64_t n, Arena& arena, hipStream_t st, ScalarSort* out);
 // Exclusive prefix sum of `count` u32 values on the device in three launches (msm.hip step 3), prefix[count] = the total.  padmask (a
 // power of two minus one, or 0): every value is rounded up to a multiple of padmask + 1 first.  block_sums: count / 2048 + 1 words of scratch.
@@ -302,7 +303,7 @@ int prefix_scan_u32(const uint32_t* vals, uint32_t* prefix, uint32_t count, uint
 int msm_slot_layout(const uint32_t* counts, uint32_t M, int R, uint32_t lseg, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off,
                     uint32_t* heavy, uint32_t* block_sums, hipStream_t st);
 
-// The same tail for MSM_WALK_PARTS (partwalk.hip): counts[M] -> offsets[M + 1], nparts[M] = ceil(count / lmax),
+// The same tail for MSM_WALK_PARTS: counts[M] -> offsets[M + 1], nparts[M] = ceil(count / lmax),
 // task_off[M + 1], the heavy list as above, and tasks[task_off[M]]: one descriptor per slot, ordered by length, longest first (a counting
 // sort over the <= lmax lengths: LDS histograms per workgroup, one scan, no global atomics).  8 <= lmax <= PART_MAX_L;
 // scratch: msm_parts_layout_scratch(M, lmax) words of device memory.
@@ -315,6 +316,7 @@ inline size_t msm_parts_layout_scratch(uint32_t M, uint32_t lmax) {
 int msm_parts_layout(const uint32_t* counts, uint32_t M, uint32_t lmax, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off, uint32_t* heavy,
                      PartTask* tasks, uint32_t* scratch, hipStream_t st);
 
+// -- the pass, the reductions, the fold, the window tables (msm.hip, one object per curve)
 // Pippenger over one base array using a ScalarSort, in two stream-separable halves:
 //   msm_bucket_pass  the throughput-bound bucket accumulation.  Sorted index p addresses bases[p + shift] when
 //                    0 <= p + shift < base_count (other entries are skipped: lets l_query reuse the sort made for a/b);

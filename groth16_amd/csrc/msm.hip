@@ -4,9 +4,10 @@
 // (/root/reference/src/prover.rs:66, 74 and 262 via calculate_coeff :92,105,113).
 // The reference runs one serial bucket scan per window, windows in parallel (<= 17-way); the
 // result of an MSM is a canonical group element, so the GPU is free to organise the work
-// differently:
+// differently.  Steps 1-4 (the sort) are in msm_sort.hip, built once for both curves; 5-7 (the pass, the reductions, the fold) and
+// the window-table builder are here, built once per curve; the host planner (MsmPlan) is msm_plan.hip:
 //
-//   1. digits_kernel        scalars (Montgomery Fr) -> canonical (prover.rs:63-65 into_bigint)
+//   1. digits_kernel       scalars (Montgomery Fr) -> canonical (prover.rs:63-65 into_bigint)
 //                           -> biased signed digits, written as W coalesced u16 "digit planes"
 //   2. bucket_count_kernel  per (point-chunk, window) workgroup: LDS-resident bucket histogram
 //                           (2^(c-1) counters, <= 128 KiB of the 160 KiB LDS) flushed with one
@@ -16,7 +17,7 @@
 //                           slice and LDS atomics hand out the slots: a counting sort of
 //                           (point index | sign) by (window, bucket) -- order inside a bucket is
 //                           irrelevant because group addition commutes
-//      (1, 2, 4 as written serve ad-hoc bases -- g16_msm_g1 / _g2; proving-key MSMs use the merged-window variants below:
+//      (1, 2, 4 as written serve ad-hoc bases -- g16_msm_g1 / _g2; proving-key MSMs use the merged-window variants:
 //       class_count / class_partition, then sub_count / sub_partition / final_sort (4m) -- no global atomics, workgroups that fit on
 //       a compute unit beside the bucket passes; bucket_count_merged / bucket_wg_scan / bucket_scatter_merged serve padded regions)
 //   5. bucket_accumulate30_kernel  THE hot kernel: one lane (G1) / lane pair (G2) per 64-entry SEGMENT of the
@@ -25,9 +26,10 @@
 //                           (fp30.hpp), the running sum's four coordinates parked in LDS (AccParked, round 4),
 //                           flushing one partial sum per (bucket, segment) it touches.  ONE launch walks up to four MSMs
 //                           (PassBatch, round 5: the G1 MSMs of a proof that are ready together -- one tail instead of four).
-//                           The prover's merged-window sorts use the BUCKET-PART walk instead (MsmPlan::walk, part_walk.hpp; its
-//                           kernels live in partwalk.hip, an object of their own): one lane (pair) per part of ONE bucket, at most
-//                           Lmax entries, tasks ordered by length -- no boundary test and no flush in the loop, one store at the end
+//                           The prover's merged-window sorts use the BUCKET-PART walk instead (MsmPlan::walk, part_walk.hpp:
+//                           bucket_parts30_kernel here, its task list from the sort's part_count / part_place kernels): one lane (pair)
+//                           per part of ONE bucket, at most Lmax entries, tasks ordered by length -- no boundary test and no flush in
+//                           the loop, one store at the end
 //   5b. heavy_reduce_kernel cooperative combine of the FEW buckets with MANY partial sums (> 16)
 //   5c. bucket_combine_kernel (round 5)  every other bucket's partial sums added up by one lane per BUCKET, so that ...
 //   6. bucket_reduce_kernel / window_reduce_kernel   ... sum_b (b+1) S_b by chunked running sums reads ONE sum per bucket: a chain
@@ -46,13 +48,12 @@
 // windows share one set of 2^(c-1) buckets: sum_i s_i P_i = sum_b (b+1) sum_{(i,j): |d_ij|-1 = b} +-T[j][i].  The bucket
 // count no longer grows with the number of windows, so c rises from 16 to 20 and the bucket pass folds n*13 instead
 // of n*16 points (BLS12-381 and BN254 scalars); the 2^19 buckets are cut into 64 sort classes of 2^13 for the LDS histogram
-// (*_merged_kernel below) and into 16 groups of 2^15 for the reductions, which treat a group like a window.  Costs 13x the key's
+// (msm_sort.hip) and into 16 groups of 2^15 for the reductions, which treat a group like a window.  Costs 13x the key's
 // memory (31 GB at 2^22 constraints on BLS12-381 -- HBM capacity is what this GPU has to spare) and a one-off table build at load time.
 // Roofline: step 5 reads ~N*W*(sizeof(Affine)+4) bytes (6.9 GB measured per MSM at 2^22, G1, merged windows) but spends ~10
 // field products (3 169 v_mad_u64_u32) per 100 bytes, i.e. it is integer-VALU bound, not HBM bound; the
 // bytes/s it sustains is reported against the 8 TB/s roofline by bench.py regardless.
 #include "internal.hpp"
-#include "msm_common.hpp"
 #include "fp30.hpp"
 #include "acc_store.hpp"
 #include "pass_batch.hpp"
@@ -60,521 +61,11 @@
 #include "window_tables.hpp"
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 
 namespace g16 {
 
-static constexpr int SORT_THREADS = 1024;
 static constexpr int RED_THREADS = 64;
 static constexpr int WIN_THREADS = 256;  // lanes of the per-window reduction
-#ifndef G16_REDUCE_G
-#define G16_REDUCE_G 8
-#endif
-static constexpr uint32_t REDUCE_G = G16_REDUCE_G;   // buckets per lane in the bucket reduction
-
-struct PlanDev {
-    int c, W;
-    uint32_t B;
-    uint32_t K[10];
-    // bucket-space shard (MsmPlan::shard_n): keep the keys with key mod shard_n == shard_r, re-index them as key / shard_n.
-    // shard_magic = ceil(2^32 / shard_n): umulhi(key, magic) == key / shard_n exactly for key < 2^20, shard_n <= 64
-    // (key * (magic * shard_n - 2^32) < 2^20 * 64 < 2^32).  shard_n == 1: no filter.
-    uint32_t shard_n, shard_r, shard_magic;
-};
-
-// false: the key belongs to another rank's residue class; true: *key is now the rank's local bucket index
-__device__ __forceinline__ bool shard_local_key(const PlanDev& plan, uint32_t* key) {
-    if (plan.shard_n <= 1) return true;
-    const uint32_t q = __umulhi(*key, plan.shard_magic);
-    if (*key - q * plan.shard_n != plan.shard_r) return false;
-    *key = q;
-    return true;
-}
-
-// ---------------------------------------------------------------------------------------------
-// 1. digit planes
-// ---------------------------------------------------------------------------------------------
-template <class Fr>
-__global__ __launch_bounds__(256) void digits_kernel(const Fr* __restrict__ scalars, uint64_t n, PlanDev plan,
-                                                     uint16_t* __restrict__ planes) {
-    __shared__ uint32_t sw[MSM_SWORDS][256];
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    uint32_t s[Fr::N];
-    scalars[i].to_canonical(s);
-    uint64_t carry = 0;
-    G16_UNROLL for (int k = 0; k < 10; ++k) {
-        carry += (uint64_t)(k < Fr::N ? s[k] : 0u) + plan.K[k];
-        sw[k][threadIdx.x] = (uint32_t)carry;
-        carry >>= 32;
-    }
-    sw[10][threadIdx.x] = 0;
-    // each thread reads back only its own column: no barrier needed
-    for (int w = 0; w < plan.W; ++w) {
-        const int bit = w * plan.c, word = bit >> 5, sh = bit & 31;
-        const uint64_t two = (uint64_t)sw[word][threadIdx.x] | ((uint64_t)sw[word + 1][threadIdx.x] << 32);
-        planes[(uint64_t)w * n + i] = (uint16_t)((uint32_t)(two >> sh) & ((1u << plan.c) - 1u));
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// 2. histogram   grid = (chunks, W)
-// ---------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(SORT_THREADS) void bucket_count_kernel(const uint16_t* __restrict__ planes, uint64_t n, uint32_t chunk,
-                                                                    int c, uint32_t B, uint32_t* __restrict__ counts) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t* hist = reinterpret_cast<uint32_t*>(smem);
-    const int w = blockIdx.y;
-    for (uint32_t b = threadIdx.x; b < B; b += SORT_THREADS) hist[b] = 0;
-    __syncthreads();
-    const uint64_t lo = (uint64_t)blockIdx.x * chunk, hi = min(n, lo + chunk);
-    const uint16_t* plane = planes + (uint64_t)w * n;
-    for (uint64_t p = lo + threadIdx.x; p < hi; p += SORT_THREADS) {
-        uint32_t bucket, neg;
-        if (digit_to_bucket(plane[p], c, &bucket, &neg)) atomicAdd(&hist[bucket], 1u);
-    }
-    __syncthreads();
-    uint32_t* out = counts + (uint64_t)w * B;
-    for (uint32_t b = threadIdx.x; b < B; b += SORT_THREADS) {
-        const uint32_t v = hist[b];
-        if (v) atomicAdd(&out[b], v);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// 1m/2m/4m. merged-window variants: every (point, window) digit is an entry of ONE bucket set of 2^(c-1) buckets, cut
-// into Q sort classes of 2^blog <= 2^13 buckets (what the LDS histogram holds: SORT_CLASS_LOG below).  Two levels:
-//   class_count_kernel / class_partition_kernel   entries -> Q contiguous class regions (block-local LDS cursors on top
-//                           of scanned per-(class, block) counts); an entry is a u16 key (bucket in class | sign << 15)
-//                           and a u32 tag (point | window << 26)
-//   sub_count_kernel / sub_partition_kernel / final_sort_kernel (4m below)   class region -> sub-class regions -> the sorted list,
-//                           its last write coalesced.   Sorted entry = point | window << 26 | sign << 31.
-//   bucket_count_merged_kernel / bucket_wg_scan_kernel / bucket_scatter_merged_kernel   padded bucket regions only
-//                           (G16_MSM_AFFINE_LEVELS > 0): per class an LDS counting sort over the class region, its histograms
-//                           exchanged through a [class][workgroup][bucket] matrix instead of global atomics.
-// ---------------------------------------------------------------------------------------------
-static constexpr int CLASS_THREADS = 256;
-static constexpr int MAX_CLASSES = 64;
-// The merged counting sort works on SORT CLASSES of 2^13 buckets (round 5; 2^15 before) with 256-lane workgroups: a 32 KB histogram and
-// four waves (<= 32 registers each) fit on a compute unit BESIDE eight bucket-pass workgroups (8 x 13 KB of LDS, 2 x 190 / 2 x 239 of a
-// SIMD's 512 registers), so h's sort -- which cannot start before the witness map ends, i.e. when the passes begin -- runs underneath the
-// passes instead of waiting for a kernel boundary: with 128 KB histograms its count and scatter kernels each sat out a whole 23 ms
-// pass and the h pass then waited 2.3 ms for the scatter (kernel trace of round 5).  The sorted list does not depend on the class
-// size (classes are contiguous bucket ranges); the reductions keep their own grouping (MsmPlan::B, groups).
-static constexpr uint32_t SORT_CLASS_LOG = 13;
-static constexpr int SORT_M_THREADS = 256;
-
-// the thread's scalar, biased, as little-endian words in its column of sw
-template <class Fr>
-__device__ __forceinline__ void biased_scalar(const Fr& sc, const PlanDev& plan, uint32_t (*sw)[CLASS_THREADS]) {
-    uint32_t s[Fr::N];
-    sc.to_canonical(s);
-    uint64_t carry = 0;
-    G16_UNROLL for (int k = 0; k < 10; ++k) {
-        carry += (uint64_t)(k < Fr::N ? s[k] : 0u) + plan.K[k];
-        sw[k][threadIdx.x] = (uint32_t)carry;
-        carry >>= 32;
-    }
-    sw[10][threadIdx.x] = 0;
-}
-__device__ __forceinline__ uint32_t window_of(const uint32_t (*sw)[CLASS_THREADS], int w, int c) {
-    const int bit = w * c, word = bit >> 5, sh = bit & 31;
-    const uint64_t two = (uint64_t)sw[word][threadIdx.x] | ((uint64_t)sw[word + 1][threadIdx.x] << 32);
-    return (uint32_t)(two >> sh) & ((1u << c) - 1u);
-}
-
-// block_counts[q * gridDim.x + block] = entries of class q among this block's 256 points
-template <class Fr>
-__global__ __launch_bounds__(CLASS_THREADS) void class_count_kernel(const Fr* __restrict__ scalars, uint64_t n, PlanDev plan, uint32_t blog,
-                                                                    uint32_t Q, uint32_t* __restrict__ block_counts) {
-    __shared__ uint32_t sw[MSM_SWORDS][CLASS_THREADS];
-    __shared__ uint32_t cnt[MAX_CLASSES];
-    if (threadIdx.x < MAX_CLASSES) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * CLASS_THREADS + threadIdx.x;
-    if (i < n) {
-        biased_scalar(scalars[i], plan, sw);
-        for (int w = 0; w < plan.W; ++w) {
-            uint32_t key, neg;
-            if (digit_to_bucket(window_of(sw, w, plan.c), plan.c, &key, &neg) && shard_local_key(plan, &key)) atomicAdd(&cnt[key >> blog], 1u);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < Q) block_counts[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x] = cnt[threadIdx.x];
-}
-
-template <class Fr>
-__global__ __launch_bounds__(CLASS_THREADS) void class_partition_kernel(const Fr* __restrict__ scalars, uint64_t n, PlanDev plan, uint32_t blog,
-                                                                        uint32_t Q, const uint32_t* __restrict__ block_off,
-                                                                        uint16_t* __restrict__ ent_key, uint32_t* __restrict__ ent_tag) {
-    __shared__ uint32_t sw[MSM_SWORDS][CLASS_THREADS];
-    __shared__ uint32_t cur[MAX_CLASSES];
-    if (threadIdx.x < Q) cur[threadIdx.x] = block_off[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x];
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * CLASS_THREADS + threadIdx.x;
-    if (i >= n) return;
-    biased_scalar(scalars[i], plan, sw);
-    for (int w = 0; w < plan.W; ++w) {
-        uint32_t key, neg;
-        if (digit_to_bucket(window_of(sw, w, plan.c), plan.c, &key, &neg) && shard_local_key(plan, &key)) {
-            const uint32_t pos = atomicAdd(&cur[key >> blog], 1u);
-            ent_key[pos] = (uint16_t)((key & ((1u << blog) - 1u)) | (neg << 15));
-            ent_tag[pos] = (uint32_t)i | ((uint32_t)w << 26);
-        }
-    }
-}
-
-// grid = (G, Q): workgroup (x, q) owns the tiles x, x + G, x + 2G, ... (SORT_M_THREADS entries each) of class region q.
-// NO global atomics (round 5).  The first version flushed every workgroup's histogram with one global atomic per non-empty bucket and
-// reserved scatter slices with one RETURNING global atomic per non-empty bucket: 2048 workgroups x ~18 000 buckets = 37 M device-scope
-// atomics per kernel at 2^22 -- on this GPU those are performed at the memory side (eight XCDs, eight L2s) -- 0.9 ms for the count and
-// 2.5 ms for the scatter of a 54.5 M-entry sort whose compulsory traffic is ~1.3 GB.  Now each workgroup STORES its histogram as one
-// row of a [class][workgroup][bucket] matrix (coalesced), a small kernel turns the columns into exclusive prefixes over the
-// workgroups (one thread per bucket, coalesced across threads) and totals, and the scatter reads its row back: its slice of bucket b
-// starts at offsets[b] + prefix[workgroup][b].  The scatter no longer re-counts its tiles either.
-static __global__ __launch_bounds__(SORT_M_THREADS) void bucket_count_merged_kernel(const uint16_t* __restrict__ ent_key,
-                                                                           const uint32_t* __restrict__ class_off, uint32_t nb, uint32_t B,
-                                                                           uint32_t* __restrict__ wg_counts) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t* hist = reinterpret_cast<uint32_t*>(smem);
-    const uint32_t q = blockIdx.y;
-    const uint32_t lo = class_off[(uint64_t)q * nb], hi = class_off[(uint64_t)(q + 1) * nb];
-    for (uint32_t b = threadIdx.x; b < B; b += SORT_M_THREADS) hist[b] = 0;
-    __syncthreads();
-    for (uint64_t p = (uint64_t)lo + blockIdx.x * SORT_M_THREADS + threadIdx.x; p < hi; p += (uint64_t)gridDim.x * SORT_M_THREADS)
-        atomicAdd(&hist[ent_key[p] & 0x7fffu], 1u);
-    __syncthreads();
-    uint32_t* out = wg_counts + ((uint64_t)q * gridDim.x + blockIdx.x) * B;   // a workgroup without tiles stores its row of zeros
-    for (uint32_t b = threadIdx.x; b < B; b += SORT_M_THREADS) out[b] = hist[b];
-}
-
-// one thread per (class, bucket): wg_counts[q][x][b] <- sum of the rows x' < x (in place), counts[q * B + b] <- the column's total
-static __global__ __launch_bounds__(256) void bucket_wg_scan_kernel(uint32_t* __restrict__ wg_counts, uint32_t G, uint32_t B, uint32_t M,
-                                                                    uint32_t* __restrict__ counts) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= M) return;
-    const uint32_t q = i / B, b = i - q * B;
-    uint32_t* col = wg_counts + (uint64_t)q * G * B + b;
-    uint32_t run = 0;
-    for (uint32_t x = 0; x < G; ++x) {
-        const uint32_t v = col[(uint64_t)x * B];
-        col[(uint64_t)x * B] = run;
-        run += v;
-    }
-    counts[i] = run;
-}
-
-static __global__ __launch_bounds__(SORT_M_THREADS) void bucket_scatter_merged_kernel(const uint16_t* __restrict__ ent_key,
-                                                                             const uint32_t* __restrict__ ent_tag,
-                                                                             const uint32_t* __restrict__ class_off, uint32_t nb, uint32_t B,
-                                                                             const uint32_t* __restrict__ offsets,
-                                                                             const uint32_t* __restrict__ wg_counts, uint32_t* __restrict__ sorted) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t* hist = reinterpret_cast<uint32_t*>(smem);
-    const uint32_t q = blockIdx.y;
-    const uint32_t lo = class_off[(uint64_t)q * nb], hi = class_off[(uint64_t)(q + 1) * nb];
-    if ((uint64_t)lo + (uint64_t)blockIdx.x * SORT_M_THREADS >= hi) return;
-    // hist[b] = this workgroup's write cursor in bucket b: the bucket's offset + what the workgroups before this one put there
-    const uint64_t qb = (uint64_t)q * B;
-    const uint32_t* mine = wg_counts + ((uint64_t)q * gridDim.x + blockIdx.x) * B;
-    for (uint32_t b = threadIdx.x; b < B; b += SORT_M_THREADS) hist[b] = offsets[qb + b] + mine[b];
-    __syncthreads();
-    const uint64_t first = (uint64_t)lo + blockIdx.x * SORT_M_THREADS + threadIdx.x, step = (uint64_t)gridDim.x * SORT_M_THREADS;
-    for (uint64_t p = first; p < hi; p += step) {
-        const uint32_t d = ent_key[p];
-        const uint32_t pos = atomicAdd(&hist[d & 0x7fffu], 1u);
-        sorted[pos] = ent_tag[p] | ((d >> 15) << 31);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// 3. scans over the M = W*B buckets: an exclusive prefix sum of a u32 array in three small coalesced launches
-//    (block sums -> scan of block sums -> write), 2048 values per workgroup.  Used for bucket counts -> bucket offsets,
-//    per-bucket partial-slot counts -> slot offsets, and the part layout's length matrix (prefix_scan_u32, the one launcher).
-// ---------------------------------------------------------------------------------------------
-static constexpr int SCAN_THREADS = 256;
-static constexpr int SCAN_PER_THREAD = 8;
-static constexpr int SCAN_TILE = SCAN_THREADS * SCAN_PER_THREAD;
-
-// exclusive scan of one value per thread across the workgroup; returns the workgroup total through *total
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* sh, uint32_t* total) {
-    const uint32_t tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < SCAN_THREADS; d <<= 1) {
-        const uint32_t add = tid >= d ? sh[tid - d] : 0u;
-        __syncthreads();
-        sh[tid] += add;
-        __syncthreads();
-    }
-    const uint32_t incl = sh[tid];
-    *total = sh[SCAN_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-// `pad` (a power of two minus one, or 0): every value is rounded up to a multiple of pad + 1 before it is summed -- bucket
-// regions of the batched-affine plan start and end on multiples of 2^R entries
-static __global__ __launch_bounds__(SCAN_THREADS) void scan_block_sums_kernel(const uint32_t* __restrict__ vals, uint32_t M, uint32_t pad,
-                                                                       uint32_t* __restrict__ block_sums) {
-    __shared__ uint32_t sa[SCAN_THREADS];
-    const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
-    uint32_t sum = 0, tot;
-    G16_UNROLL for (int j = 0; j < SCAN_PER_THREAD; ++j) sum += (base + j < M) ? ((vals[base + j] + pad) & ~pad) : 0u;
-    (void)block_exclusive(sum, sa, &tot);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
-}
-
-static __global__ __launch_bounds__(SCAN_THREADS) void scan_block_offsets_kernel(uint32_t* __restrict__ block_sums, uint32_t nblocks, uint32_t M,
-                                                                          uint32_t* __restrict__ prefix) {
-    __shared__ uint32_t sa[SCAN_THREADS];
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nblocks; base += SCAN_THREADS) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t a = i < nblocks ? block_sums[i] : 0u;
-        uint32_t tot;
-        const uint32_t ea = block_exclusive(a, sa, &tot);
-        if (i < nblocks) block_sums[i] = carry + ea;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) prefix[M] = carry;
-}
-
-static __global__ __launch_bounds__(SCAN_THREADS) void scan_write_kernel(const uint32_t* __restrict__ vals, uint32_t M, uint32_t pad,
-                                                                  const uint32_t* __restrict__ block_base, uint32_t* __restrict__ prefix) {
-    __shared__ uint32_t sa[SCAN_THREADS];
-    const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
-    uint32_t cv[SCAN_PER_THREAD], sum = 0, tot;
-    G16_UNROLL for (int j = 0; j < SCAN_PER_THREAD; ++j) { cv[j] = (base + j < M) ? ((vals[base + j] + pad) & ~pad) : 0u; sum += cv[j]; }
-    uint32_t a = block_base[blockIdx.x] + block_exclusive(sum, sa, &tot);
-    G16_UNROLL for (int j = 0; j < SCAN_PER_THREAD; ++j) {
-        if (base + j < M) { prefix[base + j] = a; a += cv[j]; }
-    }
-}
-
-// partial-sum slots of bucket b = number of length-L segments of the sorted list its entries touch
-// (batched-affine plan: the bucket pass walks the level-R list, whose bucket regions are offsets >> R)
-static __global__ void bucket_slots_kernel(const uint32_t* __restrict__ offsets, uint32_t M, uint32_t off_shift, uint32_t lseg,
-                                    uint32_t* __restrict__ nparts, uint32_t* __restrict__ heavy /* [0] = count, then bucket ids */) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= M) return;
-    const uint32_t lo = offsets[b] >> off_shift, hi = offsets[b + 1] >> off_shift;
-    const uint32_t np = hi > lo ? ((hi - 1) / lseg - lo / lseg + 1u) : 0u;
-    nparts[b] = np;
-    if (np > HEAVY_PARTS) heavy[1 + atomicAdd(&heavy[0], 1u)] = b;
-}
-
-// ---------------------------------------------------------------------------------------------
-// 4m. merged plan without padded bucket regions (affine_levels == 0): second partition level + LDS-resident final level.
-// The scatter above puts every word at a random position of a 3.4 MB class region -- a memory sector dirtied for 4 useful bytes,
-// 1.2 ms for 54.5 M entries, and the partial-line traffic slows the witness map's first sweep beside it.  Instead:
-//   sub_count_kernel / sub_partition_kernel   class region -> S sub-class regions of 2^sublog consecutive buckets (2^6 at 2^22, c = 20:
-//                           ~6.7 K entries each).  A workgroup stages a tile of SUB_TILE entries in LDS, ordered by sub-class, and
-//                           streams it out: every destination gets a run of consecutive words from consecutive lanes.  Cursors come
-//                           from a [class][sub-class][workgroup] count matrix and one prefix scan, as on the class level.
-//   final_sort_kernel       one workgroup per sub-class: LDS histogram of its <= 128 buckets -> counts[], scan, entries placed by
-//                           bucket in LDS, the slice of `sorted` streamed out coalesced.  With unpadded regions a bucket's offset is
-//                           the sub-class region's start + the scanned histogram, so this level needs neither `offsets` nor a count
-//                           pass of its own.  A sub-class with more than FINAL_CAP entries (repeated scalars; the top window's short
-//                           digit range doubles the load of the first 2^15 buckets) is detected from its region's bounds and scattered
-//                           directly through the same LDS cursors: 2^sublog open runs per workgroup instead of 2^13.
-// No global atomics.  <= 64 registers, <= 48 KB of LDS per 256-lane workgroup: the kernels run beside the G2 bucket pass like the
-// ones they replace (tests/test_sort_kernel_resources.py).
-// ---------------------------------------------------------------------------------------------
-static constexpr uint32_t MAX_SUBS = 256;        // sub-classes per class
-static constexpr uint32_t MAX_SUB_LOG = 7;       // buckets per sub-class <= 128
-static constexpr uint32_t SUB_TILE = 4096;       // entries staged per step of the sub-class partition: runs of ~32 per destination
-static constexpr uint32_t SUB_PER_LANE = SUB_TILE / SORT_M_THREADS;
-static constexpr uint32_t SUB_BATCH = 4;         // loads in flight per lane in the partition's loops
-static constexpr uint32_t FINAL_CAP = 10240;     // entries of a sub-class the final level holds in LDS (40 KB of sorted words)
-static constexpr uint32_t FINAL_BATCH = 4;       // loads in flight per lane in the final level's loops
-static_assert(SORT_M_THREADS == SCAN_THREADS && MAX_SUBS <= SCAN_THREADS && SUB_TILE <= 65536, "block_exclusive scans one value per lane");
-
-// One step of an LDS counter per valid lane, returning the value before the step.  A wave whose valid lanes all hit ONE counter
-// (a repeated scalar: every entry of the region in one bucket) takes its slots with a single atomic instead of 64 serialised ones.
-// Every lane of the wave must call it.
-__device__ __forceinline__ uint32_t lds_take(uint32_t* ctr, uint32_t idx, bool valid) {
-    const uint64_t act = __ballot(valid);
-    if (act == 0) return 0;
-    const int first = __ffsll((unsigned long long)act) - 1;
-    const uint32_t idx0 = (uint32_t)__shfl((int)idx, first);
-    if (__ballot(valid && idx == idx0) == act) {
-        const uint32_t lane = threadIdx.x & 63u;
-        uint32_t base = 0;
-        if ((int)lane == first) base = atomicAdd(&ctr[idx0], (uint32_t)__popcll(act));
-        base = (uint32_t)__shfl((int)base, first);
-        return base + (uint32_t)__popcll(act & (((uint64_t)1 << lane) - 1u));
-    }
-    return valid ? atomicAdd(&ctr[idx], 1u) : 0u;
-}
-
-// grid = (G, Q): workgroup (x, q) owns the tiles x, x + G, ... (SUB_TILE entries each) of class region q.
-// sub_counts[(q * S + s) * G + x] = its entries of sub-class s -- the order in which the exclusive scan of the matrix yields its cursors
-static __global__ __launch_bounds__(SORT_M_THREADS) void sub_count_kernel(const uint16_t* __restrict__ ent_key,
-                                                                          const uint32_t* __restrict__ class_off, uint32_t nb, uint32_t S,
-                                                                          uint32_t sublog, uint32_t* __restrict__ sub_counts) {
-    __shared__ uint32_t cnt[MAX_SUBS];
-    const uint32_t q = blockIdx.y;
-    const uint64_t lo = class_off[(uint64_t)q * nb], hi = class_off[(uint64_t)(q + 1) * nb];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint64_t tlo = lo + (uint64_t)blockIdx.x * SUB_TILE; tlo < hi; tlo += (uint64_t)gridDim.x * SUB_TILE) {
-        uint32_t k[SUB_PER_LANE];
-        G16_UNROLL for (uint32_t j = 0; j < SUB_PER_LANE; ++j) {
-            const uint64_t p = tlo + j * SORT_M_THREADS + threadIdx.x;
-            k[j] = p < hi ? (uint32_t)ent_key[p] : 0xffffffffu;
-        }
-        G16_UNROLL for (uint32_t j = 0; j < SUB_PER_LANE; ++j) (void)lds_take(cnt, (k[j] & 0x7fffu) >> sublog, k[j] != 0xffffffffu);
-    }
-    __syncthreads();
-    if (threadIdx.x < S) sub_counts[((uint64_t)q * S + threadIdx.x) * gridDim.x + blockIdx.x] = cnt[threadIdx.x];
-}
-
-static __global__ __launch_bounds__(SORT_M_THREADS) void sub_partition_kernel(const uint16_t* __restrict__ ent_key,
-                                                                              const uint32_t* __restrict__ ent_tag,
-                                                                              const uint32_t* __restrict__ class_off, uint32_t nb, uint32_t S,
-                                                                              uint32_t sublog, const uint32_t* __restrict__ sub_off,
-                                                                              uint16_t* __restrict__ out_key, uint32_t* __restrict__ out_tag) {
-    __shared__ uint32_t cnt[MAX_SUBS], start[MAX_SUBS], cur[MAX_SUBS], gcur[MAX_SUBS], sa[SCAN_THREADS];
-    __shared__ uint32_t stag[SUB_TILE];
-    __shared__ uint16_t skey[SUB_TILE];
-    const uint32_t q = blockIdx.y;
-    const uint64_t lo = class_off[(uint64_t)q * nb], hi = class_off[(uint64_t)(q + 1) * nb];
-    if (lo + (uint64_t)blockIdx.x * SUB_TILE >= hi) return;
-    gcur[threadIdx.x] = threadIdx.x < S ? sub_off[((uint64_t)q * S + threadIdx.x) * gridDim.x + blockIdx.x] : 0u;
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint64_t tlo = lo + (uint64_t)blockIdx.x * SUB_TILE; tlo < hi; tlo += (uint64_t)gridDim.x * SUB_TILE) {
-        const uint32_t tn = (uint32_t)min((uint64_t)SUB_TILE, hi - tlo);
-        // two rolled loops, SUB_BATCH loads in flight per lane: count the tile, scan, then take the staging slots from the scanned
-        // cursors (the keys come from the cache the second time; ranks kept in registers would cost sixteen of them)
-        _Pragma("unroll 1") for (uint32_t i0 = 0; i0 < tn; i0 += SUB_BATCH * SORT_M_THREADS) {
-            uint32_t k[SUB_BATCH];
-            G16_UNROLL for (uint32_t j = 0; j < SUB_BATCH; ++j) {
-                const uint32_t i = i0 + j * SORT_M_THREADS + threadIdx.x;
-                k[j] = i < tn ? (uint32_t)ent_key[tlo + i] : 0xffffffffu;
-            }
-            G16_UNROLL for (uint32_t j = 0; j < SUB_BATCH; ++j) (void)lds_take(cnt, (k[j] & 0x7fffu) >> sublog, k[j] != 0xffffffffu);
-        }
-        __syncthreads();
-        uint32_t tot;
-        const uint32_t mine = cnt[threadIdx.x], ex = block_exclusive(mine, sa, &tot);
-        start[threadIdx.x] = ex;
-        cur[threadIdx.x] = ex;
-        __syncthreads();
-        _Pragma("unroll 1") for (uint32_t i0 = 0; i0 < tn; i0 += SUB_BATCH * SORT_M_THREADS) {
-            uint32_t k[SUB_BATCH], t[SUB_BATCH];
-            G16_UNROLL for (uint32_t j = 0; j < SUB_BATCH; ++j) {
-                const uint32_t i = i0 + j * SORT_M_THREADS + threadIdx.x;
-                k[j] = i < tn ? (uint32_t)ent_key[tlo + i] : 0xffffffffu;
-                t[j] = i < tn ? ent_tag[tlo + i] : 0u;
-            }
-            G16_UNROLL for (uint32_t j = 0; j < SUB_BATCH; ++j) {
-                const bool valid = k[j] != 0xffffffffu;
-                const uint32_t pos = lds_take(cur, (k[j] & 0x7fffu) >> sublog, valid);
-                if (valid) {
-                    skey[pos] = (uint16_t)k[j];
-                    stag[pos] = t[j];
-                }
-            }
-        }
-        __syncthreads();
-        // staged position i belongs to sub-class s at rank i - start[s]: consecutive lanes, consecutive words of s's region
-        _Pragma("unroll 1") for (uint32_t i = threadIdx.x; i < tn; i += SORT_M_THREADS) {
-            const uint32_t key = skey[i], s = (key & 0x7fffu) >> sublog;
-            const uint32_t g = gcur[s] + (i - start[s]);
-            out_key[g] = (uint16_t)key;
-            out_tag[g] = stag[i];
-        }
-        __syncthreads();
-        gcur[threadIdx.x] += mine;
-        cnt[threadIdx.x] = 0;
-        __syncthreads();
-    }
-}
-
-// grid = Q * S: workgroup u owns sub-class u = buckets [u << sublog, (u + 1) << sublog), entries [sub_off[u * G], sub_off[(u + 1) * G])
-static __global__ __launch_bounds__(SORT_M_THREADS) void final_sort_kernel(const uint16_t* __restrict__ ent_key,
-                                                                           const uint32_t* __restrict__ ent_tag,
-                                                                           const uint32_t* __restrict__ sub_off, uint32_t G, uint32_t sublog,
-                                                                           uint32_t* __restrict__ counts, uint32_t* __restrict__ sorted) {
-    __shared__ uint32_t cnt[1u << MAX_SUB_LOG], cur[1u << MAX_SUB_LOG], sa[SCAN_THREADS];
-    __shared__ uint32_t out[FINAL_CAP];
-    const uint32_t u = blockIdx.x, NB = 1u << sublog;
-    const uint64_t lo = sub_off[(uint64_t)u * G], hi = sub_off[(uint64_t)(u + 1) * G];
-    if (threadIdx.x < NB) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint64_t base = lo; base < hi; base += 2 * FINAL_BATCH * SORT_M_THREADS) {
-        uint32_t k[2 * FINAL_BATCH];
-        G16_UNROLL for (uint32_t j = 0; j < 2 * FINAL_BATCH; ++j) {
-            const uint64_t p = base + j * SORT_M_THREADS + threadIdx.x;
-            k[j] = p < hi ? (uint32_t)ent_key[p] : 0xffffffffu;
-        }
-        G16_UNROLL for (uint32_t j = 0; j < 2 * FINAL_BATCH; ++j) (void)lds_take(cnt, k[j] & (NB - 1u), k[j] != 0xffffffffu);
-    }
-    __syncthreads();
-    const uint32_t mine = threadIdx.x < NB ? cnt[threadIdx.x] : 0u;
-    if (threadIdx.x < NB) counts[((uint64_t)u << sublog) + threadIdx.x] = mine;
-    uint32_t tot;
-    const uint32_t ex = block_exclusive(mine, sa, &tot);
-    if (threadIdx.x < NB) cur[threadIdx.x] = ex;
-    __syncthreads();
-    const bool resident = hi - lo <= FINAL_CAP;   // workgroup-uniform
-    for (uint64_t base = lo; base < hi; base += FINAL_BATCH * SORT_M_THREADS) {
-        uint32_t k[FINAL_BATCH], t[FINAL_BATCH];
-        G16_UNROLL for (uint32_t j = 0; j < FINAL_BATCH; ++j) {
-            const uint64_t p = base + j * SORT_M_THREADS + threadIdx.x;
-            k[j] = p < hi ? (uint32_t)ent_key[p] : 0xffffffffu;
-            t[j] = p < hi ? ent_tag[p] : 0u;
-        }
-        G16_UNROLL for (uint32_t j = 0; j < FINAL_BATCH; ++j) {
-            const bool valid = k[j] != 0xffffffffu;
-            const uint32_t pos = lds_take(cur, k[j] & (NB - 1u), valid), word = t[j] | ((k[j] >> 15) << 31);
-            if (valid) {
-                if (resident) out[pos] = word;
-                else sorted[lo + pos] = word;
-            }
-        }
-    }
-    if (!resident) return;
-    __syncthreads();
-    const uint32_t N = (uint32_t)(hi - lo);
-    for (uint32_t i = threadIdx.x; i < N; i += SORT_M_THREADS) sorted[lo + i] = out[i];
-}
-
-// ---------------------------------------------------------------------------------------------
-// 4. scatter   grid = (chunks, W)
-// ---------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(SORT_THREADS) void bucket_scatter_kernel(const uint16_t* __restrict__ planes, uint64_t n, uint32_t chunk,
-                                                                      int c, uint32_t B, const uint32_t* __restrict__ offsets,
-                                                                      uint32_t* __restrict__ cursor, uint32_t* __restrict__ sorted) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t* hist = reinterpret_cast<uint32_t*>(smem);
-    const int w = blockIdx.y;
-    for (uint32_t b = threadIdx.x; b < B; b += SORT_THREADS) hist[b] = 0;
-    __syncthreads();
-    const uint64_t lo = (uint64_t)blockIdx.x * chunk, hi = min(n, lo + chunk);
-    const uint16_t* plane = planes + (uint64_t)w * n;
-    for (uint64_t p = lo + threadIdx.x; p < hi; p += SORT_THREADS) {
-        uint32_t bucket, neg;
-        if (digit_to_bucket(plane[p], c, &bucket, &neg)) atomicAdd(&hist[bucket], 1u);
-    }
-    __syncthreads();
-    // reserve a slice of every non-empty bucket; hist[b] becomes this block's write cursor
-    const uint64_t wb = (uint64_t)w * B;
-    for (uint32_t b = threadIdx.x; b < B; b += SORT_THREADS) {
-        const uint32_t v = hist[b];
-        if (v) hist[b] = offsets[wb + b] + atomicAdd(&cursor[wb + b], v);
-    }
-    __syncthreads();
-    for (uint64_t p = lo + threadIdx.x; p < hi; p += SORT_THREADS) {
-        uint32_t bucket, neg;
-        if (digit_to_bucket(plane[p], c, &bucket, &neg)) {
-            const uint32_t pos = atomicAdd(&hist[bucket], 1u);
-            sorted[pos] = (uint32_t)p | (neg << 31);
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // 5. bucket accumulation (THE hot kernel), 30-bit lazy arithmetic (fp30.hpp); F30 = Fp30<P> (G1) or Fp2p30<P> (G2, lane pair).
@@ -640,7 +131,7 @@ __device__ __forceinline__ Acc30<F30> gather_acc(const St& st, bool inf) {
 // re-filled dynamically -- and a launch's tail cannot be filled by the next launch of the same stream.  The G1 MSMs of a proof that are
 // ready together (l, a, b_g1 share the witness sort; h joins when its sort is done in time) therefore go as ONE launch: one tail
 // instead of three or four (a rank's share of an 8-way sharded 2^22 proof: 1.3-1.4 ms per pass of 1.1 ms of work, round 5).
-// (pass_batch.hpp: PASS_BATCH and PassBatch, shared with partwalk.hip)
+// (pass_batch.hpp: PASS_BATCH and PassBatch, shared with bucket_parts30_kernel below)
 template <class F30, bool DIRECT>
 __global__ __launch_bounds__(ACC_THREADS, F30::ACC_MIN_WAVES) void bucket_accumulate30_kernel(
     PassBatch<F30> batch, uint32_t M, uint32_t off_shift, uint32_t lseg, uint32_t merged) {
@@ -717,6 +208,42 @@ __global__ __launch_bounds__(ACC_THREADS, F30::ACC_MIN_WAVES) void bucket_accumu
         if constexpr (!F30::ACC_PREFETCH) advance();
     }
     flush(&partials[slot_off[b] + (t - b_first / lseg)]);
+}
+
+// the largest v of the wave, in a scalar register
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    G16_UNROLL for (int d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// The bucket pass over PARTS (part_walk.hpp; the segment walk: bucket_accumulate30_kernel above).  Lane (pair) i of MSM blockIdx.y reads
+// descriptor i -- the list is ordered by length, so the wave's tasks have one trip count, or two where it straddles two length classes --
+// walks its entries with the segment walk's software pipeline (walk_bucket_part) and stores its sum once, into its slot.  No search for
+// the first bucket, no boundary test, no flush and no slot arithmetic in the loop; the first entry's set and the final store are uniform
+// across the wave.  The grid covers a host upper bound on the slots; slot_off[M] is the real count.  Same launch bounds, same parked
+// accumulator and the same LDS as the segment walk's kernel: three waves per SIMD for G1, two for the lane pair.
+template <class F30>
+__global__ __launch_bounds__(ACC_THREADS, F30::ACC_MIN_WAVES) void bucket_parts30_kernel(PassBatch<F30> batch, PartTaskBatch lists, uint32_t M,
+                                                                                         uint32_t merged) {
+    const Affine<typename F30::Std>* __restrict__ bases = batch.bases[blockIdx.y];
+    const int64_t shift = batch.shift[blockIdx.y];
+    const uint64_t base_count = batch.base_count[blockIdx.y];
+    const uint32_t* __restrict__ sorted = batch.sorted[blockIdx.y];
+    const uint32_t* __restrict__ slot_off = batch.slot_off[blockIdx.y];
+    AccRaw<typename F30::Raw>* __restrict__ partials = batch.partials[blockIdx.y];
+    const PartTask* __restrict__ tasks = lists.tasks[blockIdx.y];
+    const uint32_t t = (blockIdx.x * ACC_THREADS + threadIdx.x) / F30::LANES_PER_TASK;   // lanes of one task are adjacent
+    const uint32_t ntasks = slot_off[M];
+    PartTask task{0u, 0u, 0u};
+    if (t < ntasks) task = tasks[t];
+    const uint32_t trip = wave_max_u32(task.len);
+    if (t >= ntasks) return;
+    __shared__ __attribute__((aligned(16))) uint32_t acc_lds[4 * F30::PREFIX_LIMBS * ACC_THREADS];
+    AccParked<F30, LdsAccStore<F30>> acc;
+    acc.s.quad = acc_lds + 4 * threadIdx.x;
+    acc.s.tail = acc_lds + 4 * LdsAccStore<F30>::QUADS * ACC_THREADS + threadIdx.x;
+    acc.inf = true;
+    walk_bucket_part<F30>(task, trip, sorted, bases, shift, base_count, merged != 0, acc, &partials[task.slot]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -931,450 +458,6 @@ __global__ __launch_bounds__(WIN_THREADS, 2) void window_reduce_kernel(ReduceBat
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// This file is compiled twice (G16_MSM_PART = 0: BLS12-381 + the curve-independent host helpers, 1: BN254) so that the
-// two sets of template instantiations build in parallel.
-#ifndef G16_MSM_PART
-#define G16_MSM_PART 0
-#endif
-#if G16_MSM_PART == 0
-int msm_window_override() {
-    const char* e = getenv("G16_MSM_WINDOW");
-    return e ? atoi(e) : 0;
-}
-
-// W for a given c: smallest W with (modulus - 1) + K < 2^(cW)
-static int plan_windows(int c, int scalar_bits, const uint32_t* modulus_words, int mod_nwords, uint32_t* Kout) {
-    int W = (scalar_bits + 1 + c - 1) / c;
-    for (;; ++W) {
-        if (c * W > 320) return -1;
-        uint32_t K[MSM_SWORDS] = {0};
-        for (int w = 0; w < W; ++w) {
-            const int bit = w * c + c - 1;
-            K[bit >> 5] |= 1u << (bit & 31);
-        }
-        uint32_t sum[MSM_SWORDS];
-        uint64_t carry = 0;
-        for (int k = 0; k < MSM_SWORDS; ++k) {
-            carry += (uint64_t)K[k] + (k < mod_nwords ? modulus_words[k] : 0u);
-            sum[k] = (uint32_t)carry;
-            carry >>= 32;
-        }
-        bool ok = true;  // sum = modulus + K > (modulus - 1) + K ; require sum < 2^(cW)  (conservative by one)
-        for (int bit = MSM_SWORDS * 32 - 1; bit >= c * W; --bit)
-            if ((sum[bit >> 5] >> (bit & 31)) & 1) { ok = false; break; }
-        if (ok) {
-            if (Kout) for (int k = 0; k < 10; ++k) Kout[k] = K[k];
-            return W;
-        }
-    }
-}
-
-int msm_plan_windows(int c, int scalar_bits, const uint32_t* modulus_words, int mod_nwords) {
-    return plan_windows(c, scalar_bits, modulus_words, mod_nwords, nullptr);
-}
-
-// seconds, MI355X measurements of round 1: the bucket pass folds entries at ~4.5 G mixed adds/s; the bucket reduction is
-// buckets/G lanes of (2G + ~24) dependent full additions, latency-bound (~12 us each) until the lanes exceed two waves
-// per SIMD; per-group bookkeeping ~4 us
-static double plan_cost(uint64_t n, int W, double buckets, int groups) {
-    const double acc = (double)n * W / 4.5e9;
-    const double lanes = buckets / REDUCE_G;
-    const double red = (2.0 * REDUCE_G + 24.0) * 12e-6 * (lanes > 131072.0 ? lanes / 131072.0 : 1.0);
-    return acc + red + 4e-6 * groups;
-}
-
-int merged_window_bits(uint64_t n, int scalar_bits, const uint32_t* modulus_words, int mod_nwords) {
-    const char* e = getenv("G16_MSM_PRECOMP");
-    if (e && atoi(e) == 0) return 0;
-    if (n == 0 || n > MSM_MERGED_MAX_N) return 0;
-    const char* f = getenv("G16_MSM_PRECOMP_WINDOW");
-    int c = f ? atoi(f) : 0;
-    if (c <= 0) {
-        double best = 1e300;
-        for (int cc = MSM_MERGED_MIN_C; cc <= MSM_MERGED_MAX_C; ++cc) {
-            const int W = plan_windows(cc, scalar_bits, modulus_words, mod_nwords, nullptr);
-            if (W < 0 || W > 32) continue;
-            const double buckets = (double)(1u << (cc - 1));
-            const int groups = cc > 16 ? 1 << (cc - 16) : 1;
-            // the class filter of the merged counting sort re-reads the digit planes once per class
-            const double t = plan_cost(n, W, buckets, groups) + (double)n * W * groups * 3.0 / 1.5e12;
-            if (t < best) { best = t; c = cc; }
-        }
-    }
-    if (c < MSM_MERGED_MIN_C) c = MSM_MERGED_MIN_C;
-    if (c > MSM_MERGED_MAX_C) c = MSM_MERGED_MAX_C;
-    const int W = plan_windows(c, scalar_bits, modulus_words, mod_nwords, nullptr);
-    return (W < 0 || W > 32) ? 0 : c;
-}
-
-int make_msm_plan(uint64_t n, int scalar_bits, const uint32_t* modulus_words, int mod_nwords, int merged_c, MsmPlan* plan, int shard_n,
-                  int shard_r) {
-    if (shard_n < 1 || shard_n > 64 || shard_r < 0 || shard_r >= shard_n || (shard_n > 1 && merged_c <= 0)) return G16_ERR_INTERNAL;
-    int c = merged_c;
-    if (c <= 0) {
-        c = msm_window_override();
-        if (c <= 0) {
-            double best = 1e300;
-            for (int cc = 4; cc <= 16; ++cc) {
-                const int W = plan_windows(cc, scalar_bits, modulus_words, mod_nwords, nullptr);
-                if (W < 0) continue;
-                const double t = plan_cost(n, W, (double)W * (1u << (cc - 1)), W);
-                if (t < best) { best = t; c = cc; }
-            }
-        }
-        if (c < 3) c = 3;
-        if (c > 16) c = 16;
-    } else if (c < MSM_MERGED_MIN_C || c > MSM_MERGED_MAX_C || n > MSM_MERGED_MAX_N) {
-        return G16_ERR_INTERNAL;
-    }
-    const int W = plan_windows(c, scalar_bits, modulus_words, mod_nwords, plan->K);
-    if (W < 0 || (merged_c > 0 && W > 32)) return G16_ERR_INTERNAL;
-    plan->c = c;
-    plan->W = W;
-    plan->merged = merged_c > 0;
-    plan->shard_n = shard_n;
-    plan->shard_r = shard_r;
-    if (plan->merged) {
-        // classes of B <= 2^15 buckets (what the LDS histogram holds) over the rank's buckets: all 2^(c-1) of them, or -- bucket-space
-        // shard -- the ceil(2^(c-1) / shard_n) local ones (bucket shard_n k + shard_r has local index k)
-        const uint32_t all = 1u << (c - 1), local = (all + (uint32_t)shard_n - 1) / (uint32_t)shard_n;
-        uint32_t B = 1;
-        while (B < local && B < (1u << 15)) B <<= 1;
-        plan->B = B;
-        plan->groups = (int)((local + B - 1) / B);
-    } else {
-        plan->B = 1u << (c - 1);
-        plan->groups = W;
-    }
-    // buckets per lane of the bucket reduction: 8.  16 halves the window level's tree sums but doubles the bucket level's chain;
-    // measured at 2^22 on one box (round 3, tools/ab_reduce_g.sh): 8: 77.50 / 78.11 ms, 16: 78.27 / 77.81 ms, 32: 80.56 ms -- no
-    // gain, so 8 stays.  G16_MSM_REDUCE_G forces 4 / 8 / 16 / 32 (tests, A/B).
-    plan->G = REDUCE_G;
-    if (const char* e = getenv("G16_MSM_REDUCE_G")) {
-        const int v = atoi(e);
-        if (v == 4 || v == 8 || v == 16 || v == 32) plan->G = (uint32_t)v;
-    }
-    const uint64_t all_entries = n * (uint64_t)W / (uint64_t)shard_n;   // EXPECTED entries of this rank (uniform digits); buffers
-                                                                          // are sized for the worst case in sort_scalars
-    // batched-affine levels: they pay when buckets are long (each level halves a bucket's entries at ~0.6 of the XYZZ cost
-    // per addition, but a lane needs >= ~16 pairs to amortise its inversion and the chip >= ~2 k waves to stay busy)
-    plan->affine_levels = 0;
-    {
-        const uint64_t mean_load = all_entries / plan->buckets();
-        // Measured (profiles/r02_affine_v1_kernel_stats.csv, 2^22, BLS12-381): the levels LOSE on this GPU -- level 0 gathers
-        // every operand twice and spills a prefix product per pair (~750 B of mostly random HBM traffic per addition against
-        // ~137 B for the XYZZ walk), 8.0 ms for the 27 M additions that cost the XYZZ pass 6.3 ms -- so the default is 0 and the
-        // path stays as a measured, tested experiment.
-        (void)mean_load;
-        int R = 0;
-        if (const char* e = getenv("G16_MSM_AFFINE_LEVELS")) {   // 0 disables, 1..4 forces (tests run it at tiny sizes)
-            const int v = atoi(e);
-            if (v >= 0 && v <= 4) R = v;
-        }
-        if (all_entries + (uint64_t)plan->buckets() * ((1u << R) - 1u) >= ((uint64_t)1 << 32)) R = 0;
-        if (shard_n > 1) R = 0;   // (an experiment that is off by default: not carried into the bucket-space shard)
-        plan->affine_levels = R;
-    }
-    const uint64_t entries = (all_entries >> plan->affine_levels) + (plan->affine_levels ? plan->buckets() : 0);   // what the bucket pass walks
-    // Segment length of the bucket pass (entries one lane walks; the kernels take any integer >= 8): 64 entries per lane,
-    // shorter for small inputs so that the pass still has >= ~4 segments per lane slot of the chip (256 CUs x 4 SIMDs x 2 waves x 64
-    // lanes).  Measured at 2^22 (profiles/r03_ab_segment_length.txt, one box): 60 and 64 tie, 70 / 84 +0.8 %, 104 +1.2 %, 139 +3 %;
-    // for an 8-way shard 16 and 19 tie, 28 +2 %, 56 (ONE full round of the chip) +6 %.  Lanes do not take equal time (a lane that
-    // crosses more bucket boundaries flushes more partial sums), workgroups are re-dispatched one by one as others retire, so many
-    // short segments balance better than few long ones, and "fill whole rounds of the chip" -- tried in round 3 -- does not pay.
-    uint32_t l = 64;
-    while (l > 16 && entries / l < 4ull * 131072ull) l >>= 1;
-    // ... but never much shorter than the mean bucket load: a bucket of ~mean entries then touches at most ~5 segments and
-    // stays below the heavy-bucket threshold (otherwise EVERY bucket would go through the cooperative combine)
-    const uint64_t mean = entries / plan->buckets() + 1;
-    while (l < 128 && (uint64_t)l * 4 < mean) l <<= 1;
-    if (const char* e = getenv("G16_MSM_SEGMENT")) {   // experiments: force the segment length (8 .. 4096)
-        const int v = atoi(e);
-        if (v >= 8 && v <= 4096) l = (uint32_t)v;
-    }
-    plan->Lmax = l;
-    // histogram / scatter chunking: ~2048 workgroups in total, chunk a multiple of 1024 points
-    uint64_t nchunks = 2048 / (uint64_t)plan->groups;
-    if (nchunks < 1) nchunks = 1;
-    uint64_t chunk = (n + nchunks - 1) / nchunks;
-    chunk = (chunk + 1023) / 1024 * 1024;
-    if (chunk < 1024) chunk = 1024;
-    plan->chunk = (uint32_t)chunk;
-    return G16_OK;
-}
-
-// exclusive prefix sum of `count` values (3. above; internal.hpp); block_sums: scratch of ceil(count / SCAN_TILE) words
-int prefix_scan_u32(const uint32_t* vals, uint32_t* prefix, uint32_t count, uint32_t padmask, uint32_t* block_sums, hipStream_t st) {
-    const uint32_t nblocks = (count + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, st, vals, count, padmask, block_sums);
-    G16_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_block_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, block_sums, nblocks, count, prefix);
-    G16_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_write_kernel, dim3(nblocks), dim3(SCAN_THREADS), 0, st, vals, count, padmask, block_sums, prefix);
-    G16_LAUNCH_CHECK();
-    return G16_OK;
-}
-
-// The tail of sort_scalars, which the pass lab (unit_api.hpp) runs on caller-made counts: bucket counts -> offsets (every count
-// rounded up to a multiple of 2^R), offsets -> partial-sum slots per bucket and the heavy list, slots -> task_off.
-int msm_slot_layout(const uint32_t* counts, uint32_t M, int R, uint32_t lseg, uint32_t* offsets, uint32_t* nparts, uint32_t* task_off,
-                    uint32_t* heavy, uint32_t* block_sums, hipStream_t st) {
-    G16_TRY(prefix_scan_u32(counts, offsets, M, (1u << R) - 1u, block_sums, st));
-    hipLaunchKernelGGL(bucket_slots_kernel, dim3((M + 255) / 256), dim3(256), 0, st, offsets, M, (uint32_t)R, lseg, nparts, heavy);
-    G16_LAUNCH_CHECK();
-    G16_TRY(prefix_scan_u32(nparts, task_off, M, 0u, block_sums, st));
-    return G16_OK;
-}
-
-int msm_prover_walk() {
-    if (const char* e = getenv("G16_MSM_WALK")) {   // A/B: force either walk
-        if (!strcmp(e, "segment")) return MSM_WALK_SEGMENT;
-        if (!strcmp(e, "parts")) return MSM_WALK_PARTS;
-    }
-    return MSM_WALK_PARTS;
-}
-#endif  // G16_MSM_PART == 0
-
-static int ilog2(uint32_t v) { int l = 0; while ((1u << l) < v) ++l; return l; }
-
-template <class C>
-int sort_scalars(const typename C::Fr* d_scalars, uint64_t n, int merged_c, Arena& arena, hipStream_t st, ScalarSort* out, int shard_n,
-                 int shard_r, int walk) {
-    typedef typename C::Fr Fr;
-    if (n >= ((uint64_t)1 << 31)) return G16_ERR_BAD_LENGTH;
-    uint32_t modw[Fr::N];
-    for (int i = 0; i < Fr::N; ++i) modw[i] = Fr::Params::mod(i);
-    MsmPlan plan;
-    G16_TRY(make_msm_plan(n, Fr::Params::BITS, modw, Fr::N, merged_c, &plan, shard_n, shard_r));
-    // the bucket-part walk: merged plans whose pass walks the sorted list itself (and lengths its layout's histogram holds)
-    const bool parts = walk == MSM_WALK_PARTS && plan.merged && plan.affine_levels == 0 && plan.Lmax <= PART_MAX_L;
-    plan.walk = parts ? MSM_WALK_PARTS : MSM_WALK_SEGMENT;
-    out->plan = plan;
-    out->n = n;
-    const uint32_t M = plan.buckets();
-    const uint64_t nw = n * (uint64_t)plan.W;
-    if (nw >= ((uint64_t)1 << 32)) return G16_ERR_BAD_LENGTH;
-    uint16_t* planes = nullptr;     // per-window plan: digit planes; merged plan: entry keys, class-partitioned
-    uint32_t* ent_tag = nullptr;    // merged plan: entry tags (point | window << 26), class-partitioned
-    uint32_t *class_cnt = nullptr, *class_off = nullptr;
-    uint32_t *counts = nullptr, *cursor = nullptr, *nparts = nullptr, *block_sums = nullptr;
-    // merged plan: sort classes of Bs = 2^13 buckets (or the whole bucket set when it is smaller)
-    uint32_t sort_class_log = SORT_CLASS_LOG;
-    if (const char* e = getenv("G16_SORT_CLASS_LOG")) {   // A/B: 15 = histograms of 128 KB (no room beside the bucket passes)
-        const int v = atoi(e);
-        if (v >= 8 && v <= 15) sort_class_log = (uint32_t)v;
-    }
-    const uint32_t slog = plan.merged ? std::min<uint32_t>(sort_class_log, (uint32_t)ilog2(plan.B)) : 0u;
-    const uint32_t Bs = plan.merged ? 1u << slog : plan.B;
-    const uint32_t nb = (uint32_t)((n + CLASS_THREADS - 1) / CLASS_THREADS), Q = plan.merged ? M >> slog : (uint32_t)plan.groups;
-    G16_TRY(arena.alloc_n(nw ? nw : 1, &planes));
-    if (plan.merged) {
-        if (Q > MAX_CLASSES) return G16_ERR_INTERNAL;
-        G16_TRY(arena.alloc_n(nw ? nw : 1, &ent_tag));
-        G16_TRY(arena.alloc_n((size_t)Q * nb + 1, &class_cnt));
-        G16_TRY(arena.alloc_n((size_t)Q * nb + 1, &class_off));
-    }
-    G16_TRY(arena.alloc_n((size_t)3 * M + 1, &counts));  // counts | scatter cursors | heavy count + list
-    cursor = counts + M;
-    out->heavy = counts + 2 * (size_t)M;
-    G16_TRY(arena.alloc_n((size_t)M + 1, &out->offsets));
-    G16_TRY(arena.alloc_n((size_t)M + 1, &out->task_off));
-    G16_TRY(arena.alloc_n((size_t)M, &nparts));
-    // batched-affine plan: every bucket region is padded to a multiple of 2^R entries; the padding slots keep the hole
-    // word the list is pre-filled with, and the bucket pass walks the level-R list (1 / 2^R of the slots)
-    const int R = plan.affine_levels;
-    const uint32_t pad = (1u << R) - 1u;
-    const uint64_t max_sorted = nw + (uint64_t)M * pad;
-    if (max_sorted >= ((uint64_t)1 << 32)) return G16_ERR_BAD_LENGTH;
-    out->max_sorted = max_sorted;
-    G16_TRY(arena.alloc_n(max_sorted ? max_sorted : 1, &out->sorted));
-    if (R) G16_HIP_TRY(hipMemsetAsync(out->sorted, 0xff, max_sorted * sizeof(uint32_t), st));   // SORT_HOLE
-    const uint64_t walked = R ? (max_sorted >> R) : nw;
-    out->max_segments = (uint32_t)((walked + plan.Lmax - 1) / plan.Lmax);
-    out->max_tasks = out->max_segments + M;   // a bucket gets one slot per segment it touches: <= segments + buckets in total
-    uint32_t* part_scratch = nullptr;
-    if (parts) {
-        // sum_b ceil(n_b / Lmax) <= entries / Lmax + buckets; one task per slot, and the grid of the pass covers that bound
-        out->max_tasks = (uint32_t)(nw / plan.Lmax) + M;
-        out->max_segments = out->max_tasks;
-        G16_TRY(arena.alloc_n((size_t)out->max_tasks ? out->max_tasks : 1, &out->tasks));
-        G16_TRY(arena.alloc_n(msm_parts_layout_scratch(M, plan.Lmax), &part_scratch));
-    }
-    G16_HIP_TRY(hipMemsetAsync(counts, 0, ((size_t)2 * M + 1) * sizeof(uint32_t), st));
-    PlanDev pd;
-    pd.c = plan.c; pd.W = plan.W; pd.B = plan.B;
-    for (int k = 0; k < 10; ++k) pd.K[k] = plan.K[k];
-    pd.shard_n = (uint32_t)plan.shard_n;
-    pd.shard_r = (uint32_t)plan.shard_r;
-    pd.shard_magic = plan.shard_n > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)plan.shard_n - 1) / (uint64_t)plan.shard_n) : 0u;
-    const size_t lds = (size_t)Bs * sizeof(uint32_t);
-    static PerDeviceOnce attr_once;
-    std::atomic<bool>& attr_set = attr_once.flag();
-    if (!attr_set) {
-        G16_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bucket_count_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        128 * 1024));
-        G16_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bucket_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        128 * 1024));
-        G16_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bucket_count_merged_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        G16_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bucket_scatter_merged_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        attr_set = true;
-    }
-    const unsigned nchunks = (unsigned)((n + plan.chunk - 1) / plan.chunk);
-    const uint32_t blog = plan.merged ? slog : (uint32_t)ilog2(plan.B);
-    // merged plan, unpadded bucket regions: second partition level + LDS-resident final level (4m above).  Sub-classes of 2^sublog
-    // buckets, the largest size whose EXPECTED load leaves a quarter of the final level's LDS list free (2^6 at 2^22, c = 20); what
-    // exceeds the list anyway is scattered directly by the same kernel.  Padded regions (G16_MSM_AFFINE_LEVELS > 0) keep the
-    // histogram-matrix scatter, which places entries by `offsets`.
-    const bool two_level = plan.merged && R == 0;
-    uint32_t sublog = 0, S = 1;
-    unsigned gx2 = 1;
-    if (two_level) {
-        const uint64_t mean_x4 = 4 * (nw / (uint64_t)plan.shard_n) / M + 1;   // 4 x the mean bucket load
-        const uint32_t lo_log = slog > 8 ? slog - 8 : 0u;                     // S <= MAX_SUBS
-        sublog = std::min<uint32_t>(slog, MAX_SUB_LOG);
-        while (sublog > lo_log && (mean_x4 << sublog) > 3 * (uint64_t)FINAL_CAP) --sublog;
-        if (sublog > MAX_SUB_LOG) return G16_ERR_INTERNAL;
-        S = Bs >> sublog;
-        // ~4096 workgroups of 256 lanes over the class regions, a tile of SUB_TILE entries at a time
-        gx2 = std::max(1u, std::min(std::min(4096u / Q, 256u), (unsigned)((nw + SUB_TILE - 1) / SUB_TILE)));
-    }
-    const uint32_t sub_cells = two_level ? Q * S * gx2 : 0u;
-    const uint32_t max_scan = std::max(std::max(M, plan.merged ? Q * nb : 0u), sub_cells);
-    G16_TRY(arena.alloc_n((size_t)(max_scan + SCAN_TILE - 1) / SCAN_TILE, &block_sums));
-    auto prefix_scan = [&](const uint32_t* vals, uint32_t* prefix, uint32_t count) -> int {
-        return prefix_scan_u32(vals, prefix, count, 0u, block_sums, st);
-    };
-    // merged plan: ~4096 workgroups of 256 lanes over the class regions (a class region may hold anything between nothing and all
-    // entries), at most 256 per class: every workgroup zeroes, stores and re-reads a histogram row whatever it counts
-    unsigned gx = std::max(1u, std::min(std::min(4096u / Q, 256u), (unsigned)((nw + SORT_M_THREADS - 1) / SORT_M_THREADS)));
-    if (const char* e = getenv("G16_SORT_GX")) {   // experiments: workgroups per class of the histogram-matrix scatter (padded regions)
-        const int v = atoi(e);
-        if (v >= 1 && v <= 4096) gx = (unsigned)v;
-    }
-    uint32_t* wg_counts = nullptr;   // merged plan, padded regions: [class][workgroup][bucket] histograms, then their prefixes over the workgroups
-    if (plan.merged && !two_level) G16_TRY(arena.alloc_n((size_t)Q * gx * Bs, &wg_counts));
-    uint16_t* sub_key = nullptr;     // two-level plan: entry keys and tags, sub-class-partitioned
-    uint32_t *sub_tag = nullptr, *sub_cnt = nullptr, *sub_off = nullptr;
-    if (two_level) {
-        G16_TRY(arena.alloc_n(nw ? nw : 1, &sub_key));
-        G16_TRY(arena.alloc_n(nw ? nw : 1, &sub_tag));
-        G16_TRY(arena.alloc_n((size_t)sub_cells + 1, &sub_cnt));
-        G16_TRY(arena.alloc_n((size_t)sub_cells + 1, &sub_off));
-    }
-    if (n) {
-        if (plan.merged) {
-            hipLaunchKernelGGL((class_count_kernel<Fr>), dim3(nb), dim3(CLASS_THREADS), 0, st, d_scalars, n, pd, blog, Q, class_cnt);
-            G16_LAUNCH_CHECK();
-            G16_TRY(prefix_scan(class_cnt, class_off, Q * nb));
-            hipLaunchKernelGGL((class_partition_kernel<Fr>), dim3(nb), dim3(CLASS_THREADS), 0, st, d_scalars, n, pd, blog, Q, class_off, planes,
-                               ent_tag);
-            G16_LAUNCH_CHECK();
-            if (two_level) {
-                hipLaunchKernelGGL(sub_count_kernel, dim3(gx2, Q), dim3(SORT_M_THREADS), 0, st, planes, class_off, nb, S, sublog, sub_cnt);
-                G16_LAUNCH_CHECK();
-                G16_TRY(prefix_scan(sub_cnt, sub_off, sub_cells));
-                hipLaunchKernelGGL(sub_partition_kernel, dim3(gx2, Q), dim3(SORT_M_THREADS), 0, st, planes, ent_tag, class_off, nb, S, sublog,
-                                   sub_off, sub_key, sub_tag);
-                G16_LAUNCH_CHECK();
-                // writes counts[] AND the sorted list: what follows only derives offsets, slots and the heavy list from the counts
-                hipLaunchKernelGGL(final_sort_kernel, dim3(Q * S), dim3(SORT_M_THREADS), 0, st, sub_key, sub_tag, sub_off, gx2, sublog, counts,
-                                   out->sorted);
-            } else {
-                hipLaunchKernelGGL(bucket_count_merged_kernel, dim3(gx, Q), dim3(SORT_M_THREADS), lds, st, planes, class_off, nb, Bs,
-                                   wg_counts);
-                G16_LAUNCH_CHECK();
-                hipLaunchKernelGGL(bucket_wg_scan_kernel, dim3((M + 255) / 256), dim3(256), 0, st, wg_counts, gx, Bs, M, counts);
-            }
-        } else {
-            hipLaunchKernelGGL((digits_kernel<Fr>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, n, pd, planes);
-            G16_LAUNCH_CHECK();
-            hipLaunchKernelGGL(bucket_count_kernel, dim3(nchunks, plan.W), dim3(SORT_THREADS), lds, st, planes, n, plan.chunk, plan.c, plan.B,
-                               counts);
-        }
-        G16_LAUNCH_CHECK();
-    }
-    if (parts) G16_TRY(msm_parts_layout(counts, M, plan.Lmax, out->offsets, nparts, out->task_off, out->heavy, out->tasks, part_scratch, st));
-    else G16_TRY(msm_slot_layout(counts, M, R, plan.Lmax, out->offsets, nparts, out->task_off, out->heavy, block_sums, st));
-    if (n && !two_level) {
-        if (plan.merged)
-            hipLaunchKernelGGL(bucket_scatter_merged_kernel, dim3(gx, Q), dim3(SORT_M_THREADS), lds, st, planes, ent_tag, class_off, nb, Bs,
-                               out->offsets, wg_counts, out->sorted);
-        else
-            hipLaunchKernelGGL(bucket_scatter_kernel, dim3(nchunks, plan.W), dim3(SORT_THREADS), lds, st, planes, n, plan.chunk, plan.c, plan.B,
-                               out->offsets, cursor, out->sorted);
-        G16_LAUNCH_CHECK();
-    }
-    return G16_OK;
-}
-
-#if G16_MSM_PART == 0
-// ---------------------------------------------------------------------------------------------
-// Sorting SHORT scalars (the ceremony library's 128-bit coefficients).  coeffs128_plan: a per-window plan over 128 scalar bits with
-// the "modulus" 2^128, so the smallest W with (2^128 - 1) + K < 2^(cW) -- the carry out of bit 127 and the top window's range -- is
-// the plan's business; about half the windows, digit planes, histograms and per-window reductions of an Fr plan.
-// sort_digit_planes: the per-window path from its second step on, over digit planes the caller made with a kernel of its own
-// (W planes of n u16 digits of scalar + K, as digits_kernel writes them): histogram, slot layout, scatter -- unchanged kernels.
-// ---------------------------------------------------------------------------------------------
-int coeffs128_plan(uint64_t n, MsmPlan* plan) {
-    if (n >= ((uint64_t)1 << 31)) return G16_ERR_BAD_LENGTH;
-    const uint32_t two128[5] = {0u, 0u, 0u, 0u, 1u};   // coefficients are < 2^128
-    G16_TRY(make_msm_plan(n, 128, two128, 5, 0, plan));
-    plan->affine_levels = 0;   // (the G16_MSM_AFFINE_LEVELS experiment pads bucket regions: not carried into this sort)
-    // rho + K < 2^(cW) <= 2^160 must fit COEFF128_SWORDS - 1 words, and the last window's second word must be the guard at most
-    if (plan->merged || plan->c > 16 || plan->c * plan->W > 32 * (COEFF128_SWORDS - 2)) return G16_ERR_INTERNAL;
-    for (int k = COEFF128_SWORDS - 2; k < 10; ++k)
-        if (plan->K[k]) return G16_ERR_INTERNAL;
-    return G16_OK;
-}
-
-int sort_digit_planes(const MsmPlan& plan, const uint16_t* planes, uint64_t n, Arena& arena, hipStream_t st, ScalarSort* out) {
-    if (plan.merged || plan.affine_levels || n >= ((uint64_t)1 << 31)) return G16_ERR_INTERNAL;
-    out->plan = plan;
-    out->n = n;
-    const uint32_t M = plan.buckets();
-    const uint64_t nw = n * (uint64_t)plan.W;
-    if (nw >= ((uint64_t)1 << 32)) return G16_ERR_BAD_LENGTH;
-    uint32_t *counts = nullptr, *nparts = nullptr, *block_sums = nullptr;
-    G16_TRY(arena.alloc_n((size_t)3 * M + 1, &counts));  // counts | scatter cursors | heavy count + list
-    uint32_t* cursor = counts + M;
-    out->heavy = counts + 2 * (size_t)M;
-    G16_TRY(arena.alloc_n((size_t)M + 1, &out->offsets));
-    G16_TRY(arena.alloc_n((size_t)M + 1, &out->task_off));
-    G16_TRY(arena.alloc_n((size_t)M, &nparts));
-    G16_TRY(arena.alloc_n((size_t)(M + SCAN_TILE - 1) / SCAN_TILE, &block_sums));
-    out->max_sorted = nw;
-    G16_TRY(arena.alloc_n(nw ? nw : 1, &out->sorted));
-    out->max_segments = (uint32_t)((nw + plan.Lmax - 1) / plan.Lmax);
-    out->max_tasks = out->max_segments + M;
-    G16_HIP_TRY(hipMemsetAsync(counts, 0, ((size_t)2 * M + 1) * sizeof(uint32_t), st));
-    const size_t lds = (size_t)plan.B * sizeof(uint32_t);
-    static PerDeviceOnce attr_once;
-    std::atomic<bool>& attr_set = attr_once.flag();
-    if (!attr_set) {
-        G16_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bucket_count_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        128 * 1024));
-        G16_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bucket_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        128 * 1024));
-        attr_set = true;
-    }
-    const unsigned nchunks = (unsigned)((n + plan.chunk - 1) / plan.chunk);
-    if (n) {
-        hipLaunchKernelGGL(bucket_count_kernel, dim3(nchunks, plan.W), dim3(SORT_THREADS), lds, st, planes, n, plan.chunk, plan.c, plan.B,
-                           counts);
-        G16_LAUNCH_CHECK();
-    }
-    G16_TRY(msm_slot_layout(counts, M, 0, plan.Lmax, out->offsets, nparts, out->task_off, out->heavy, block_sums, st));
-    if (n) {
-        hipLaunchKernelGGL(bucket_scatter_kernel, dim3(nchunks, plan.W), dim3(SORT_THREADS), lds, st, planes, n, plan.chunk, plan.c, plan.B,
-                           out->offsets, cursor, out->sorted);
-        G16_LAUNCH_CHECK();
-    }
-    return G16_OK;
-}
-#endif
-
 // buffers of one MSM's pass and reductions
 template <class F>
 static int alloc_msm_buffers(const ScalarSort& ss, Arena& arena, MsmBuffers<F>* out) {
@@ -1472,6 +555,21 @@ static unsigned pass_lds_pad() {
     return per > own ? per - own : 0;
 }
 
+// bucket_parts30_kernel over a host upper bound of `max_tasks` tasks per MSM for the n MSMs of the batch (slot_off[M] is the real count,
+// read on the device; surplus lanes exit)
+template <class F30>
+static int msm_parts_pass_launch(const PassBatch<F30>& batch, const PartTaskBatch& tasks, int n, uint32_t max_tasks, uint32_t M, bool merged,
+                                 hipStream_t st) {
+    if (n < 1 || n > PASS_BATCH || !max_tasks) return G16_ERR_INTERNAL;
+    for (int i = 0; i < n; ++i)
+        if (!tasks.tasks[i] || !batch.slot_off[i] || !batch.partials[i]) return G16_ERR_INTERNAL;
+    const uint64_t lanes = (uint64_t)max_tasks * F30::LANES_PER_TASK;
+    const dim3 grid((unsigned)((lanes + ACC_THREADS - 1) / ACC_THREADS), (unsigned)n);
+    hipLaunchKernelGGL((bucket_parts30_kernel<F30>), grid, dim3(ACC_THREADS), pass_lds_pad<F30>(), st, batch, tasks, M, merged ? 1u : 0u);
+    G16_LAUNCH_CHECK();
+    return G16_OK;
+}
+
 // the bucket passes of n <= PASS_BATCH MSMs with one bucket layout as ONE launch (PassBatch above)
 template <class F>
 int msm_bucket_pass_batch(const PassJob<F>* jobs, int n, Arena& arena, hipStream_t st, EventTimer* bucket_timer) {
@@ -1497,8 +595,8 @@ int msm_bucket_pass_batch(const PassJob<F>* jobs, int n, Arena& arena, hipStream
         if (i < n) max_segments = std::max(max_segments, j.ss->max_segments);
     }
     if (bucket_timer) G16_TRY(bucket_timer->start(st));
-    if (max_segments && plan.walk == MSM_WALK_PARTS) {   // max_segments bounds the parts here; the kernel lives in partwalk.hip
-        G16_TRY((msm_parts_pass_launch<F30>(b, tb, n, max_segments, plan.buckets(), plan.merged, pass_lds_pad<F30>(), st)));
+    if (max_segments && plan.walk == MSM_WALK_PARTS) {   // max_segments bounds the parts here
+        G16_TRY((msm_parts_pass_launch<F30>(b, tb, n, max_segments, plan.buckets(), plan.merged, st)));
     } else if (max_segments) {
         const uint64_t lanes = (uint64_t)max_segments * F30::LANES_PER_TASK;
         const dim3 grid((unsigned)((lanes + ACC_THREADS - 1) / ACC_THREADS), (unsigned)n);
@@ -1704,7 +802,6 @@ int build_window_tables(const Affine<F>* d_src, uint64_t n, int c, int W, Affine
 #define G16_INSTANTIATE_MSM(C)                                                                                               \
     template int convert_bases<typename C::Fq>(Affine<typename C::Fq>*, uint64_t, hipStream_t);                             \
     template int convert_bases<typename C::Fq2>(Affine<typename C::Fq2>*, uint64_t, hipStream_t);                           \
-    template int sort_scalars<C>(const typename C::Fr*, uint64_t, int, Arena&, hipStream_t, ScalarSort*, int, int, int);                  \
     template int build_window_tables<typename C::Fq>(const Affine<typename C::Fq>*, uint64_t, int, int, Affine<typename C::Fq>*, hipStream_t, void*);    \
     template int build_window_tables<typename C::Fq2>(const Affine<typename C::Fq2>*, uint64_t, int, int, Affine<typename C::Fq2>*, hipStream_t, void*); \
     template size_t window_table_park_bytes<typename C::Fq>(uint64_t, int);                                                 \
@@ -1723,6 +820,10 @@ int build_window_tables(const Affine<F>* d_src, uint64_t n, int c, int W, Affine
     template XYZZ<typename C::Fq> fold_windows<typename C::Fq>(const XYZZ<typename C::Fq>*, const MsmPlan&);               \
     template XYZZ<typename C::Fq2> fold_windows<typename C::Fq2>(const XYZZ<typename C::Fq2>*, const MsmPlan&);
 
+// This file is compiled twice (G16_MSM_PART = 0: BLS12-381, 1: BN254) so that the two sets of template instantiations build in parallel.
+#ifndef G16_MSM_PART
+#define G16_MSM_PART 0
+#endif
 #if G16_MSM_PART == 0
 G16_INSTANTIATE_MSM(Bls12_381)
 #else

@@ -1,5 +1,5 @@
 // The bucket-part walk of the bucket pass (msm.hip step 5, MsmPlan::walk == MSM_WALK_PARTS): the layout rule, the task descriptor and
-// the per-task walk, written once for the kernel (bucket_parts30_kernel, partwalk.hip) and for its host twin
+// the per-task walk, written once for the kernel (bucket_parts30_kernel, msm.hip) and for its host twin
 // (partslab.hip, g16_host_msm_parts_lab), which runs the same code on the CPU tier and in a sanitizer build.
 //
 // Layout.  A bucket of n > 0 entries at `off` of the sorted list is cut into np = ceil(n / Lmax) PARTS; part p covers the entries

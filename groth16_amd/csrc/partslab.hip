@@ -1,5 +1,5 @@
 // The host twin of the bucket-part walk (g16_host_msm_parts_lab; test hook like hosttest.hip, not on a proof's path): the layout rule
-// and walk_bucket_part of part_walk.hpp -- the code bucket_parts30_kernel (partwalk.hip) runs per lane -- compiled
+// and walk_bucket_part of part_walk.hpp -- the code bucket_parts30_kernel (msm.hip) runs per lane -- compiled
 // for the host, G1 on both curves (the lane pair's G2 arithmetic needs its partner lane and is a device form, as in the field lab).
 // The accumulator parks in ParkedArrayStore instead of LDS.  A translation unit of its own that takes nothing from the rest of the
 // library, so that tests/parts_walk_replay.cpp builds with it alone under -fsanitize=address,undefined: table, sorted list and records

@@ -1,5 +1,5 @@
-// The argument block of a batched bucket pass (msm.hip step 5), shared by bucket_accumulate30_kernel (msm.hip) and the part walk's
-// bucket_parts30_kernel (partwalk.hip).
+// The argument block of a batched bucket pass (msm.hip step 5), shared by bucket_accumulate30_kernel and the part walk's
+// bucket_parts30_kernel (both in msm.hip).
 #pragma once
 #include "curve.hpp"
 #include "fp30.hpp"
@@ -22,10 +22,5 @@ struct PassBatch {
 struct PartTaskBatch {
     const PartTask* tasks[PASS_BATCH];
 };
-// bucket_parts30_kernel over a host upper bound of `max_tasks` tasks per MSM for the n MSMs of the batch (slot_off[M] is the real count,
-// read on the device; surplus lanes exit); lds_pad: unused dynamic LDS (msm.hip pass_lds_pad).  F30 = Fp30<P> or Fp2p30<P> of either curve.
-template <class F30>
-int msm_parts_pass_launch(const PassBatch<F30>& batch, const PartTaskBatch& tasks, int n, uint32_t max_tasks, uint32_t M, bool merged,
-                          unsigned lds_pad, hipStream_t st);
 
 }  // namespace g16

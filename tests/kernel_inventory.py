@@ -16,14 +16,14 @@ INVENTORY = {
         "bitrev_scale_kernel": 2, "gen_powers_kernel": 2, "ntt30_dif_dit_kernel": 2, "ntt30_pass_kernel": 4, "scale_table_kernel": 2,
         "tw_convert_kernel": 2, "circom_h_kernel": 2, "dwm_column_kernel": 20, "mark_unit_kernel": 2, "quotient_kernel": 2, "spmv3_kernel": 2,
         "spmv_circom_kernel": 2, "r1cs_check_kernel": 2, "r1cs_row_values_kernel": 2,
-        # msm.hip (compiled twice: the kernels that are no templates are in both objects, under one name)
+        # msm_sort.hip (one object for both curves), msm.hip (one object per curve; every kernel a template on the base field)
         "affine_level_kernel": 8, "bucket_accumulate30_kernel": 8, "bucket_combine_kernel": 4, "bucket_count_kernel": 1,
         "bucket_count_merged_kernel": 1, "bucket_reduce_kernel": 4, "bucket_scatter_kernel": 1, "bucket_scatter_merged_kernel": 1,
         "bucket_slots_kernel": 1, "bucket_wg_scan_kernel": 1, "build_window_tables_kernel": 4, "class_count_kernel": 2,
         "class_partition_kernel": 2, "convert_bases30_kernel": 4, "digits_kernel": 2, "final_sort_kernel": 1, "heavy_reduce_kernel": 4,
         "scan_block_offsets_kernel": 1, "scan_block_sums_kernel": 1, "scan_write_kernel": 1, "sub_count_kernel": 1, "sub_partition_kernel": 1,
         "window_reduce_kernel": 4,
-        # partwalk.hip
+        # the bucket-part walk: the pass kernel in msm.hip, the layout kernels in msm_sort.hip
         "bucket_parts30_kernel<": 4, "part_count_kernel": 1, "part_place_kernel": 1,
         # synth.hip, setup.hip, srs_setup.hip
         "mad_rate_kernel": 1, "synth_bases_kernel": 4, "fixed_base_mul_kernel": 4, "fixed_base_table_kernel": 4, "srs_butterfly_kernel": 4,
@@ -44,8 +44,6 @@ INVENTORY = {
     "libg16_keycheck.so": {"keycheck_add_kernel": 2, "keycheck_rho_kernel": 2, "keycheck_rows_kernel": 2, "keycheck_scatter_odd_kernel": 2},
     "libg16_lagrange.so": {"lagrange_addsub_kernel": 4, "lagrange_bitrev_kernel": 4, "lagrange_twiddle_mul_kernel": 4},
 }
-# code objects of the product library that hold the `static` scan kernels: msm.hip's two, and no copy anywhere else
-SCAN_OBJECTS = 2
 
 _read = {}
 

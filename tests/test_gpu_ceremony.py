@@ -103,6 +103,44 @@ def test_rlc_sums_equal_existing_msm_past_one_chunk(g, orc, provers, cp):
     assert (hi == prover.msm(np.ascontiguousarray(pts[1:]), fr)).all()
 
 
+_FIRST_WORK_CHILD = """
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import groth16_amd as g
+pts, co = np.load(sys.argv[2]), np.load(sys.argv[3])
+with g.Groth16("bls12_381", 0) as prover:
+    lo, hi = prover.rlc_sums(pts, co)
+    tm = prover.timings()
+assert tm["window_bits"] == 16, tm
+np.save(sys.argv[4], np.stack([lo, hi]))
+"""
+
+
+def test_rlc_sums_as_first_gpu_work_with_128_kib_histograms(g, orc, tmp_path):
+    """G16_MSM_WINDOW=16 gives sort_digit_planes histograms of 2^15 counters, 128 KiB of dynamic LDS, which the count and scatter
+    kernels may take only once their limit is raised.  In a fresh process whose first GPU work is rlc_sums no other sort has raised it
+    before: 258 G1 points, 257 coefficients (one more than a block of the digits kernel), the sums against the host twin."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pts = orc.synth_bases("bls12_381", False, 1616, 258)
+    co = cc.random_coeffs(257, 16)
+    co[0], co[1], co[256] = (1 << 128) - 1, 1, 1 << 127
+    co = cc.coeff_array(co)
+    files = [str(tmp_path / name) for name in ("pts.npy", "co.npy", "sums.npy")]
+    np.save(files[0], pts)
+    np.save(files[1], co)
+    run = subprocess.run([sys.executable, "-c", _FIRST_WORK_CHILD, root] + files, env=dict(os.environ, G16_MSM_WINDOW="16"),
+                         capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stderr[-3000:]
+    lo, hi = np.load(files[2])
+    hlo, hhi = g.rlc_sums_host("bls12_381", pts, co)
+    assert (lo == hlo).all() and (hi == hhi).all()
+
+
 # ---- the SRS -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [4, 16])
 @pytest.mark.parametrize("cp", sc.CURVES, ids=lambda c: c.name)

@@ -1,4 +1,4 @@
-"""GPU tier: the bucket-part walk in place -- bucket_parts30_kernel (partwalk.hip) as msm_bucket_pass_batch launches
+"""GPU tier: the bucket-part walk in place -- bucket_parts30_kernel (msm.hip) as msm_bucket_pass_batch launches
 it, on sorted lists and bucket histograms made by tests/pass_cases.py and tests/parts_cases.py -- through g16_dev_msm_parts_lab, against
 pymodel's group law.  offsets, task_off, the heavy list and the task list come from the library's own layout code (msm_parts_layout:
 part_count_kernel, the scans, part_place_kernel).

@@ -1,4 +1,4 @@
-"""Shapes of the merged-plan counting sort (msm.hip, sort_scalars: class partition -> sub-class partition -> LDS-resident final
+"""Shapes of the merged-plan counting sort (msm_sort.hip, sort_scalars: class partition -> sub-class partition -> LDS-resident final
 level), driven through the ad-hoc MSM with window tables built on the fly (G16_MSM_API_PRECOMP=1) and a forced window size
 (G16_MSM_PRECOMP_WINDOW).  The group sums depend only on which entries land in which bucket, so every case is compared bit-for-bit
 with the CPU oracle's MSM.  The sizes are the smallest at which each part of the sort can go wrong:

@@ -105,7 +105,7 @@ def test_host_twin_refusals(lib, cfg):
 
 
 def test_layout_launcher_refuses_a_short_lmax(lib):
-    """msm_parts_layout (partwalk.hip, an object of the product library) turns down lmax < 8 with G16_ERR_INTERNAL before it touches the device"""
+    """msm_parts_layout (msm_sort.hip, an object of the product library) turns down lmax < 8 with G16_ERR_INTERNAL before it touches the device"""
     import ctypes
 
     fn = ctypes.CDLL(lib.path)["_ZN3g1616msm_parts_layoutEPKjjjPjS2_S2_S2_PNS_8PartTaskES2_P12ihipStream_t"]

@@ -1,8 +1,8 @@
-"""Register / scratch budget of the bucket-part walk's kernels (partwalk.hip), read from the code objects inside the BUILT product
+"""Register / scratch budget of the bucket-part walk's kernels (the pass kernel in msm.hip, the layout kernels in msm_sort.hip), read from the code objects inside the BUILT product
 library (no GPU needed); beside tests/test_kernel_resources.py, which holds the segment walk's kernel to the same budgets.
 bucket_parts30_kernel keeps zero scratch and the occupancy of the segment walk's kernel -- G1 three waves per SIMD (four on BN254),
 the lane-pair G2 kernel two -- and no more LDS than the parked accumulator; the two layout kernels use at most 64 registers and no
-scratch, so that a wave of theirs fits beside a pass.  The scans are msm.hip's: tests/test_kernel_inventory.py."""
+scratch, so that a wave of theirs fits beside a pass.  The scans are msm_sort.hip's, in one code object: tests/test_kernel_inventory.py."""
 import pytest
 
 import kernel_inventory as inv

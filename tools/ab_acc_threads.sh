@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B on ONE box: workgroup size of the bucket pass (libg16_acc<T>.so = msm.hip built with ACC_THREADS = T) against the shipped library.
+# A/B on ONE box: workgroup size of the bucket pass (libg16_acc<T>.so = msm.o and msm_bn254.o, which hold both walks of the pass, built with ACC_THREADS = T) against the shipped library.
 # usage (on the GPU box): bash tools/ab_acc_threads.sh <T> [<T> ...]
 for v in main "$@" main; do
   if [ $v = main ]; then unset G16_LIB; else export G16_LIB=$PWD/groth16_amd/libg16_acc$v.so; fi

@@ -35,7 +35,7 @@ def code_objects(path, arch="gfx950"):
 
 
 def kernels(path):
-    """demangled name -> figures, over all code objects of the library (two `static` kernels of one name in two objects look like one)"""
+    """demangled name -> figures, over all code objects of the library (no name occurs in two of them: tests/test_kernel_inventory.py)"""
     return {name: k for obj in kernels_per_object(path) for name, k in obj.items()}
 
 
