@@ -245,7 +245,7 @@ EXPORTS = [
     "g16_abi_version", "g16_struct_size", "g16_get_timings_sized", "g16_pk_get_info_sized",
     "g16_pvk_load", "g16_pvk_free", "g16_pvk_alpha_beta", "g16_verify_batch", "g16_verify_batch_prepared", "g16_pairing",
     "g16_host_pairing", "g16_host_verify", "g16_verify_aggregate", "g16_host_verify_aggregate", "g16_host_verify_aggregate_gt",
-    "g16_dev_fp30_op", "g16_host_fp30_op", "g16_dev_msm_reduce_lab", "g16_dev_window_table_lab", "g16_dev_pairing_op", "g16_host_pairing_op",
+    "g16_dev_fp30_op", "g16_host_fp30_op", "g16_dev_msm_reduce_lab", "g16_dev_msm_reduce_batch_lab", "g16_dev_window_table_lab", "g16_dev_pairing_op", "g16_host_pairing_op",
     "g16_dev_std_op", "g16_host_std_op",
     "g16_dev_msm_pass_lab", "g16_dev_msm_sort_lab", "g16_dev_msm_parts_lab", "g16_host_msm_parts_lab",
     "g16_dev_pvk_tables", "g16_dev_prepare_inputs", "g16_host_pvk_tables", "g16_host_prepare_inputs",
@@ -483,6 +483,8 @@ class Lib:
         c.g16_dev_std_op.argtypes = [C.c_void_p, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_host_std_op.argtypes = [C.c_int, C.c_int, C.c_int, u32p, C.c_uint64, u32p]
         c.g16_dev_msm_reduce_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u32p, u32p, C.c_uint64, u32p, u64p]
+        c.g16_dev_msm_reduce_batch_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(u32p),
+                                                   C.POINTER(u32p), u64p, C.POINTER(u32p), C.POINTER(u64p)]
         c.g16_dev_window_table_lab.argtypes = [C.c_void_p, C.c_int, u64p, C.c_uint64, C.c_int, C.c_int, u64p]
         c.g16_dev_msm_pass_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PassLabJobC),
                                            C.c_int]
@@ -565,6 +567,34 @@ def msm_reduce_lab(lb: "Lib", ctx, g2: bool, merged: bool, c: int, groups: int, 
     lb.check(lb.c.g16_dev_msm_reduce_lab(ctx, int(g2), int(merged), c, groups, G, ptr32(nparts), ptr32(records), records.shape[0],
                                          ptr32(first), ptr64(out)))
     return first, out
+
+
+def msm_reduce_batch_lab(lb: "Lib", ctx, merged: bool, c: int, groups: int, G: int, jobs, early=None, affine_words: int = 0):
+    """g16_dev_msm_reduce_batch_lab (test hook, G1): the reductions of up to four jobs over one plan as the launches a proof makes.
+    jobs: a list of (nparts, records) as msm_reduce_lab takes them.  early=None: all jobs through msm_reduce_batch together; early=a
+    set of job indices: those through msm_heavy_reduce_batch in one launch, the others through msm_heavy_reduce alone, then
+    msm_reduce_batch with heavy_done.  Returns (status, results); results is None unless status == 0, else per job (first slots,
+    folded affine point) as msm_reduce_lab returns them.  Nothing is checked here: refusing is the library's to do."""
+    n = len(jobs)
+    keep, outs = [], []
+    np_arr, rec_arr, first_arr, out_arr = (u32p * max(n, 1))(), (u32p * max(n, 1))(), (u32p * max(n, 1))(), (u64p * max(n, 1))()
+    n_rec = np.zeros(max(n, 1), dtype=np.uint64)
+    for k, (nparts, records) in enumerate(jobs):
+        nparts = np.ascontiguousarray(nparts, dtype=np.uint32)
+        records = np.ascontiguousarray(records, dtype=np.uint32)
+        assert records.ndim == 2
+        first = np.full((nparts.shape[0], records.shape[1]), 0xDEADBEEF, dtype=np.uint32)
+        out = np.zeros(affine_words, dtype=np.uint64)
+        keep.append((nparts, records))
+        outs.append((first, out))
+        np_arr[k], rec_arr[k], first_arr[k], out_arr[k] = ptr32(nparts), ptr32(records.reshape(-1)), ptr32(first.reshape(-1)), ptr64(out)
+        n_rec[k] = records.shape[0]
+    mask = 0
+    for j in (early or ()):
+        mask |= 1 << j
+    status = lb.c.g16_dev_msm_reduce_batch_lab(ctx, int(merged), c, groups, G, n, 0 if early is None else 1, mask, np_arr, rec_arr, ptr64(n_rec),
+                                               first_arr, out_arr)
+    return status, (outs if status == 0 else None)
 
 
 PASS_LAB_GUARDS = 8

@@ -1020,6 +1020,16 @@ int g16_dev_msm_reduce_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, 
     G16_DISPATCH(ctx->curve, I::template msm_reduce_lab<typename I::Fq2>(ctx, merged, c, groups, G, nparts, records, n_records, first_slots, out_affine));
 }
 
+int g16_dev_msm_reduce_batch_lab(g16_ctx* ctx, int merged, int c, int groups, int G, int n_jobs, int mode, uint32_t early_mask,
+                                 const uint32_t* const* nparts, const uint32_t* const* records, const uint64_t* n_records,
+                                 uint32_t* const* first_slots, uint64_t* const* out_affine) {
+    if (!ctx || !nparts || !records || !n_records || !first_slots || !out_affine) return G16_ERR_BAD_ARG;
+    if (!ctx->subs.empty())
+        return g16_dev_msm_reduce_batch_lab(ctx->subs[0], merged, c, groups, G, n_jobs, mode, early_mask, nparts, records, n_records, first_slots, out_affine);
+    G16_HIP_TRY(hipSetDevice(ctx->device));
+    G16_DISPATCH(ctx->curve, I::msm_reduce_batch_lab(ctx, merged, c, groups, G, n_jobs, mode, early_mask, nparts, records, n_records, first_slots, out_affine));
+}
+
 int g16_dev_msm_pass_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, int lseg, int rows, g16_pass_lab_job* jobs, int n_jobs) {
     if (!ctx || !jobs) return G16_ERR_BAD_ARG;
     if (!ctx->subs.empty()) return g16_dev_msm_pass_lab(ctx->subs[0], g2, merged, c, groups, G, lseg, rows, jobs, n_jobs);

@@ -120,72 +120,170 @@ struct UnitApi {
         return G16_OK;
     }
 
-    // The reductions alone on caller-made partial sums (test hook, g16_dev_msm_reduce_lab): a plan, a ScalarSort -- slot offsets and
-    // the heavy list by bucket_slots_kernel's rule for a segment length of 1: one partial per entry, more than HEAVY_PARTS is heavy --
-    // and the buffers are filled here; the kernels are launched by msm_reduce and the sums folded by fold_windows, as in a proof.
+    // The reductions alone on caller-made partial sums (test hooks, g16_dev_msm_reduce_lab and g16_dev_msm_reduce_batch_lab): a plan, and
+    // per job a ScalarSort -- slot offsets and the heavy list by bucket_slots_kernel's rule for a segment length of 1: one partial per
+    // entry, more than HEAVY_PARTS is heavy -- and the buffers are filled here; the kernels are launched by msm_reduce / msm_reduce_batch /
+    // msm_heavy_reduce[_batch] and the sums folded by fold_windows, as in a proof.
+    template <class F>
+    struct ReduceLabJob {
+        typedef Fp30<typename Fq::Params> B30;
+        typedef AccRaw<typename std::conditional<std::is_same<F, Fq>::value, B30, Fp2x30<typename Fq::Params>>::type> Raw;
+        static constexpr size_t REC_WORDS = (std::is_same<F, Fq>::value ? 4 : 8) * B30::NL;
+        static_assert(sizeof(Raw) == REC_WORDS * sizeof(uint32_t), "a record is its limbs, nothing else");
+        ScalarSort ss;
+        MsmBuffers<F> buf;
+        uint64_t n_records = 0;
+        std::vector<uint32_t> task_off, heavy, after;
+        std::vector<XYZZ<F>> hws;
+    };
+    static int reduce_lab_plan(int merged, int c, int groups, int G, MsmPlan* plan) {
+        if (c < 2 || c > 16 || groups < 1 || groups > 32 || (G != 8 && G != 16 && G != 32)) return G16_ERR_BAD_ARG;
+        plan->c = c;
+        plan->W = groups;
+        plan->groups = groups;
+        plan->merged = merged != 0;
+        plan->B = 1u << (c - 1);
+        plan->G = (uint32_t)G;
+        plan->Lmax = 1;
+        plan->chunk = 1024;
+        for (int k = 0; k < 10; ++k) plan->K[k] = 0;
+        if (plan->outputs() > MSM_MAX_OUTPUTS) return G16_ERR_BAD_ARG;
+        return G16_OK;
+    }
+    // host half of a job: slot offsets and the heavy list from nparts (nothing on the device yet)
+    template <class F>
+    static int reduce_lab_layout(const MsmPlan& plan, const uint32_t* nparts, uint64_t n_records, ReduceLabJob<F>* job) {
+        const uint32_t M = plan.buckets();
+        job->ss.plan = plan;
+        job->n_records = n_records;
+        job->task_off.assign((size_t)M + 1, 0u);
+        job->heavy.assign((size_t)M + 1, 0u);
+        uint64_t total = 0;
+        for (uint32_t b = 0; b < M; ++b) {
+            job->task_off[b] = (uint32_t)total;
+            total += nparts[b];
+            if (nparts[b] > HEAVY_PARTS) job->heavy[1 + job->heavy[0]++] = b;
+            if (total >= ((uint64_t)1 << 31)) return G16_ERR_BAD_LENGTH;
+        }
+        job->task_off[M] = (uint32_t)total;
+        if (total != n_records) return G16_ERR_BAD_LENGTH;
+        job->ss.max_tasks = (uint32_t)total;
+        return G16_OK;
+    }
+    // device half: the job's own buffers from the arena, layout and records uploaded
+    template <class F>
+    static int reduce_lab_upload(g16_ctx* ctx, const uint32_t* records, ReduceLabJob<F>* job) {
+        typedef typename ReduceLabJob<F>::Raw Raw;
+        const MsmPlan& plan = job->ss.plan;
+        const uint32_t M = plan.buckets();
+        const uint64_t n_records = job->n_records;
+        hipStream_t st = ctx->stream;
+        Raw *d_partials = nullptr, *d_chunk = nullptr;
+        G16_TRY(ctx->arena.alloc_n((size_t)M + 1, &job->ss.task_off));
+        G16_TRY(ctx->arena.alloc_n((size_t)M + 1, &job->ss.heavy));
+        G16_TRY(ctx->arena.alloc_n(n_records ? (size_t)n_records : 1, &d_partials));
+        G16_TRY(ctx->arena.alloc_n((size_t)plan.chunks() * plan.groups * 2, &d_chunk));
+        G16_TRY(ctx->arena.alloc_n((size_t)plan.outputs(), &job->buf.window_sums));
+        job->buf.partials = d_partials;
+        job->buf.chunk_out = d_chunk;
+        G16_HIP_TRY(hipMemcpyAsync(job->ss.task_off, job->task_off.data(), ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        G16_HIP_TRY(hipMemcpyAsync(job->ss.heavy, job->heavy.data(), ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (n_records) G16_HIP_TRY(hipMemcpyAsync(d_partials, records, (size_t)n_records * sizeof(Raw), hipMemcpyHostToDevice, st));
+        return G16_OK;
+    }
+    // the group sums and the records as the reductions left them, enqueued behind the kernels
+    template <class F>
+    static int reduce_lab_download(g16_ctx* ctx, ReduceLabJob<F>* job) {
+        typedef typename ReduceLabJob<F>::Raw Raw;
+        const MsmPlan& plan = job->ss.plan;
+        hipStream_t st = ctx->stream;
+        job->hws.resize(plan.outputs());
+        job->after.resize((size_t)job->n_records * ReduceLabJob<F>::REC_WORDS);
+        G16_HIP_TRY(hipMemcpyAsync(job->hws.data(), job->buf.window_sums, sizeof(XYZZ<F>) * plan.outputs(), hipMemcpyDeviceToHost, st));
+        if (job->n_records)
+            G16_HIP_TRY(hipMemcpyAsync(job->after.data(), job->buf.partials, (size_t)job->n_records * sizeof(Raw), hipMemcpyDeviceToHost, st));
+        return G16_OK;
+    }
+    // after the stream has drained: every bucket's first slot, and the fold
+    template <class F>
+    static void reduce_lab_finish(const ReduceLabJob<F>& job, const uint32_t* nparts, uint32_t* first_slots, uint64_t* out_affine) {
+        typedef typename ReduceLabJob<F>::Raw Raw;
+        constexpr size_t REC_WORDS = ReduceLabJob<F>::REC_WORDS;
+        const MsmPlan& plan = job.ss.plan;
+        const uint32_t M = plan.buckets();
+        for (uint32_t b = 0; b < M; ++b) {
+            uint32_t* o = first_slots + (size_t)b * REC_WORDS;
+            if (nparts[b]) memcpy(o, job.after.data() + (size_t)job.task_off[b] * REC_WORDS, sizeof(Raw));
+            else memset(o, 0, sizeof(Raw));
+        }
+        const Affine<F> res = fold_windows<F>(job.hws.data(), plan).to_affine();
+        memcpy(out_affine, &res, sizeof(Affine<F>));
+    }
+
     template <class F>
     static int msm_reduce_lab(g16_ctx* ctx, int merged, int c, int groups, int G, const uint32_t* nparts, const uint32_t* records,
                               uint64_t n_records, uint32_t* first_slots, uint64_t* out_affine) {
-        typedef Affine<F> A;
-        typedef XYZZ<F> X;
-        typedef Fp30<typename Fq::Params> B30;
-        typedef AccRaw<typename std::conditional<std::is_same<F, Fq>::value, B30, Fp2x30<typename Fq::Params>>::type> Raw;
-        constexpr size_t REC_WORDS = (std::is_same<F, Fq>::value ? 4 : 8) * B30::NL;
-        static_assert(sizeof(Raw) == REC_WORDS * sizeof(uint32_t), "a record is its limbs, nothing else");
-        if (c < 2 || c > 16 || groups < 1 || groups > 32 || (G != 8 && G != 16 && G != 32)) return G16_ERR_BAD_ARG;
-        ScalarSort ss;
-        MsmPlan& plan = ss.plan;
-        plan.c = c;
-        plan.W = groups;
-        plan.groups = groups;
-        plan.merged = merged != 0;
-        plan.B = 1u << (c - 1);
-        plan.G = (uint32_t)G;
-        plan.Lmax = 1;
-        plan.chunk = 1024;
-        for (int k = 0; k < 10; ++k) plan.K[k] = 0;
-        if (plan.outputs() > MSM_MAX_OUTPUTS) return G16_ERR_BAD_ARG;
-        const uint32_t M = plan.buckets();
-        std::vector<uint32_t> task_off((size_t)M + 1), heavy((size_t)M + 1, 0u);
-        uint64_t total = 0;
-        for (uint32_t b = 0; b < M; ++b) {
-            task_off[b] = (uint32_t)total;
-            total += nparts[b];
-            if (nparts[b] > HEAVY_PARTS) heavy[1 + heavy[0]++] = b;
-            if (total >= ((uint64_t)1 << 31)) return G16_ERR_BAD_LENGTH;
-        }
-        task_off[M] = (uint32_t)total;
-        if (total != n_records) return G16_ERR_BAD_LENGTH;
+        MsmPlan plan;
+        G16_TRY(reduce_lab_plan(merged, c, groups, G, &plan));
+        ReduceLabJob<F> job;
+        G16_TRY(reduce_lab_layout<F>(plan, nparts, n_records, &job));
         hipStream_t st = ctx->stream;
         DrainOnError drain(ctx);
         ctx->reset_arena();
-        Raw *d_partials = nullptr, *d_chunk = nullptr;
-        MsmBuffers<F> buf;
-        G16_TRY(ctx->arena.alloc_n((size_t)M + 1, &ss.task_off));
-        G16_TRY(ctx->arena.alloc_n((size_t)M + 1, &ss.heavy));
-        G16_TRY(ctx->arena.alloc_n(n_records ? (size_t)n_records : 1, &d_partials));
-        G16_TRY(ctx->arena.alloc_n((size_t)plan.chunks() * plan.groups * 2, &d_chunk));
-        G16_TRY(ctx->arena.alloc_n((size_t)plan.outputs(), &buf.window_sums));
-        buf.partials = d_partials;
-        buf.chunk_out = d_chunk;
-        ss.max_tasks = (uint32_t)total;
-        G16_HIP_TRY(hipMemcpyAsync(ss.task_off, task_off.data(), ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        G16_HIP_TRY(hipMemcpyAsync(ss.heavy, heavy.data(), ((size_t)M + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        if (n_records) G16_HIP_TRY(hipMemcpyAsync(d_partials, records, (size_t)n_records * sizeof(Raw), hipMemcpyHostToDevice, st));
-        G16_TRY((msm_reduce<F>(buf, ss, st)));
-        std::vector<X> hws(plan.outputs());
-        std::vector<uint32_t> after((size_t)n_records * REC_WORDS);
-        G16_HIP_TRY(hipMemcpyAsync(hws.data(), buf.window_sums, sizeof(X) * plan.outputs(), hipMemcpyDeviceToHost, st));
-        if (n_records) G16_HIP_TRY(hipMemcpyAsync(after.data(), d_partials, (size_t)n_records * sizeof(Raw), hipMemcpyDeviceToHost, st));
+        G16_TRY(reduce_lab_upload<F>(ctx, records, &job));
+        G16_TRY((msm_reduce<F>(job.buf, job.ss, st)));
+        G16_TRY(reduce_lab_download<F>(ctx, &job));
         G16_HIP_TRY(hipStreamSynchronize(st));
         drain.dismiss();
-        for (uint32_t b = 0; b < M; ++b) {
-            uint32_t* o = first_slots + (size_t)b * REC_WORDS;
-            if (nparts[b]) memcpy(o, after.data() + (size_t)task_off[b] * REC_WORDS, sizeof(Raw));
-            else memset(o, 0, sizeof(Raw));
+        reduce_lab_finish<F>(job, nparts, first_slots, out_affine);
+        return G16_OK;
+    }
+
+    // The batch form (g16_dev_msm_reduce_batch_lab; G1: the prover batches no G2 reductions and msm_reduce_batch is built for Fq alone):
+    // 1 to REDUCE_LAB_JOBS jobs over one plan, each with its own slot offsets, heavy list and buffers, reduced by the launches
+    // prove_partial makes.  mode 0 ("together"): msm_reduce_batch(all, heavy_done = false), the last batch with h inside.  mode 1
+    // ("early"): the jobs of early_mask go through msm_heavy_reduce_batch as one launch, every other job through msm_heavy_reduce
+    // alone, then msm_reduce_batch(all, heavy_done = true): the single-GPU proof, whose first batch has its first stage underneath the h
+    // pass.  Refused (G16_ERR_BAD_ARG): n_jobs outside 1 .. 4, an unknown mode, in early mode a subset that is empty or names a job that
+    // is not there.
+    static constexpr int REDUCE_LAB_JOBS = 4;
+    static int msm_reduce_batch_lab(g16_ctx* ctx, int merged, int c, int groups, int G, int n_jobs, int mode, uint32_t early_mask,
+                                    const uint32_t* const* nparts, const uint32_t* const* records, const uint64_t* n_records,
+                                    uint32_t* const* first_slots, uint64_t* const* out_affine) {
+        typedef Fq F;
+        if (n_jobs < 1 || n_jobs > REDUCE_LAB_JOBS || (mode != 0 && mode != 1)) return G16_ERR_BAD_ARG;
+        if (mode == 1 && (early_mask == 0 || (early_mask >> n_jobs) != 0)) return G16_ERR_BAD_ARG;
+        for (int j = 0; j < n_jobs; ++j)
+            if (!nparts[j] || !first_slots[j] || !out_affine[j] || (n_records[j] && !records[j])) return G16_ERR_BAD_ARG;
+        MsmPlan plan;
+        G16_TRY(reduce_lab_plan(merged, c, groups, G, &plan));
+        ReduceLabJob<F> jobs[REDUCE_LAB_JOBS];
+        for (int j = 0; j < n_jobs; ++j) G16_TRY(reduce_lab_layout<F>(plan, nparts[j], n_records[j], &jobs[j]));
+        hipStream_t st = ctx->stream;
+        DrainOnError drain(ctx);
+        ctx->reset_arena();
+        const MsmBuffers<F>* bufs[REDUCE_LAB_JOBS];
+        const ScalarSort* sorts[REDUCE_LAB_JOBS];
+        for (int j = 0; j < n_jobs; ++j) {
+            G16_TRY(reduce_lab_upload<F>(ctx, records[j], &jobs[j]));
+            bufs[j] = &jobs[j].buf;
+            sorts[j] = &jobs[j].ss;
         }
-        const A res = fold_windows<F>(hws.data(), plan).to_affine();
-        memcpy(out_affine, &res, sizeof(A));
+        if (mode == 1) {
+            const MsmBuffers<F>* eb[REDUCE_LAB_JOBS];
+            const ScalarSort* es[REDUCE_LAB_JOBS];
+            int ne = 0;
+            for (int j = 0; j < n_jobs; ++j)
+                if ((early_mask >> j) & 1u) { eb[ne] = bufs[j]; es[ne] = sorts[j]; ++ne; }
+            G16_TRY((msm_heavy_reduce_batch<F>(eb, es, ne, st)));
+            for (int j = 0; j < n_jobs; ++j)
+                if (!((early_mask >> j) & 1u)) G16_TRY((msm_heavy_reduce<F>(*bufs[j], *sorts[j], st)));
+        }
+        G16_TRY((msm_reduce_batch<F>(bufs, sorts, n_jobs, st, /*heavy_done=*/mode == 1)));
+        for (int j = 0; j < n_jobs; ++j) G16_TRY(reduce_lab_download<F>(ctx, &jobs[j]));
+        G16_HIP_TRY(hipStreamSynchronize(st));
+        drain.dismiss();
+        for (int j = 0; j < n_jobs; ++j) reduce_lab_finish<F>(jobs[j], nparts[j], first_slots[j], out_affine[j]);
         return G16_OK;
     }
 

@@ -632,6 +632,19 @@ int g16_host_std_op(int curve, int kind, int form, const uint32_t* operands, uin
  * out_affine: the folded sum  sum_w 2^(c w) sum_b (b + 1) S_(w,b)  (per-window)  or  sum_k (k + 1) S_k over the bucket key k (merged). */
 int g16_dev_msm_reduce_lab(g16_ctx* ctx, int g2, int merged, int c, int groups, int G, const uint32_t* nparts, const uint32_t* records,
                            uint64_t n_records, uint32_t* first_slots, uint64_t* out_affine);
+/* The batch form, G1 only (the prover batches no G2 reductions): n_jobs = 1 .. 4 jobs over ONE plan (merged, c, groups, G as above), job j
+ * with its own nparts[j], records[j] (n_records[j] of them), slot offsets, heavy list and device buffers, and its own first_slots[j] and
+ * out_affine[j].  The jobs are reduced by the launches a proof makes (blockIdx.y / .z of every reduction kernel = job):
+ *   mode 0, together: msm_reduce_batch over all jobs, first stage (heavy combine, bucket combine) included -- a proof's last batch with
+ *           h inside; early_mask is not looked at
+ *   mode 1, early:    the jobs whose bit is set in early_mask have their first stage in ONE launch per kernel (msm_heavy_reduce_batch),
+ *           every other job has it alone (msm_heavy_reduce), then msm_reduce_batch over all jobs with heavy_done set -- the single-GPU
+ *           proof, whose l / a / b_g1 batch has its first stage underneath the h pass
+ * The fold runs per job.  G16_ERR_BAD_ARG: n_jobs outside 1 .. 4, another mode, in mode 1 an early_mask that is 0 or has a bit at or
+ * above n_jobs, a null pointer; G16_ERR_BAD_LENGTH: a job whose n_records is not the sum of its nparts. */
+int g16_dev_msm_reduce_batch_lab(g16_ctx* ctx, int merged, int c, int groups, int G, int n_jobs, int mode, uint32_t early_mask,
+                                 const uint32_t* const* nparts, const uint32_t* const* records, const uint64_t* n_records,
+                                 uint32_t* const* first_slots, uint64_t* const* out_affine);
 
 /* ---- the pass lab (test hook): the bucket pass's walk in place, on a caller-made sorted list ----
  * A plan as in the reduction lab (merged, 2 <= c <= 16, `groups` groups of 2^(c-1) buckets, M = groups * 2^(c-1) <= 2^12 buckets, G = 8,

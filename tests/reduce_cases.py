@@ -1,5 +1,5 @@
-"""Crafted partial sums for the reduction lab (g16_dev_msm_reduce_lab) and the model of what the reductions make of them
-(TEST INFRASTRUCTURE).
+"""Crafted partial sums for the reduction lab (g16_dev_msm_reduce_lab) and its batch form (g16_dev_msm_reduce_batch_lab: BATCHES,
+batch_conditions) and the model of what the reductions make of them (TEST INFRASTRUCTURE).
 
 The lab runs the prover's own reduction -- heavy_reduce_kernel, bucket_combine_kernel, bucket_reduce_kernel, window_reduce_kernel and
 the host fold -- on partial sums the caller wrote, so a test can place what whole MSMs on random data never reach: equal and opposite
@@ -45,6 +45,21 @@ HEAVY_TASKS = {False: HEAVY_THREADS, True: HEAVY_THREADS // 2}   # a task is one
 WIN_TASKS = {False: WIN_THREADS, True: WIN_THREADS // 2}
 CHUNKS = (8, 16, 32)                    # buckets per reduction lane: 4 and 2 chunks per group (bit planes live), and the whole group
 SCENARIOS = ("combine", "chains")
+# The batch lab (g16_dev_msm_reduce_batch_lab, G1) reduces up to four jobs in one launch per kernel; a job is a scenario.  "complement",
+# "empty" and "single" exist for it: what tells the jobs of a batch apart (batch_conditions).
+BATCH_SCENARIOS = SCENARIOS + ("complement", "empty", "single")
+BATCHES = (
+    ("combine", "chains", "complement", "empty"),
+    ("empty", "complement", "chains", "combine"),       # the reverse
+    ("complement", "empty", "chains", "combine"),       # complement first, combine last
+    ("complement", "combine"),
+    ("chains", "complement", "combine"),
+    ("combine", "combine"),                             # two separate copies: same offsets and lists, other buffers
+    ("single",),
+)
+# early mode: the jobs of the subset have their first stage in one launch (msm_heavy_reduce_batch), the others alone; {0, 1, 2} is what
+# the single-GPU proof does with l, a, b_g1 before h
+EARLY_SUBSETS = {4: ((0, 1, 2), (0,), (1, 2)), 3: ((1, 2),)}
 
 
 Rep = collections.namedtuple("Rep", "point kx ky")   # a partial sum with chosen representatives: x + kx p, y + ky p per component
@@ -339,6 +354,147 @@ def _chains(sc, rng):
         sc.seen.update(["window_reduce_kernel: chunks with equal sums", "window_reduce_kernel: chunks with opposite sums"])
 
 
+def heavy_buckets(sc):
+    return [b for b, n in enumerate(sc.nparts) if n > HEAVY_PARTS]
+
+
+def _next_nonempty(nparts, b):
+    for k in range(b + 1, len(nparts)):
+        if nparts[k]:
+            return k
+    return None
+
+
+def wrong_list_shows(sc, b):
+    """What the heavy stage does to scenario `sc` when it is told, from another job's heavy list, that bucket b is heavy:
+    "overwrite": b is empty, so the identity goes into the slot at its offset -- the first slot of the next bucket that holds anything --
+    and that bucket holds ONE record, not the identity, which is lost ("overwrite, adjacent": it is bucket b + 1);
+    "twice": b holds 2 .. HEAVY_PARTS records, the stage sums them into the first slot and bucket_combine_kernel adds all but the first
+    a second time, and those do not sum to the identity.  None: neither (the bucket sum survives)."""
+    n = sc.nparts[b]
+    if n == 0:
+        k = _next_nonempty(sc.nparts, b)
+        if k is not None and sc.nparts[k] == 1 and sc.sums[k] is not None:
+            return "overwrite, adjacent" if k == b + 1 else "overwrite"
+    elif 2 <= n <= HEAVY_PARTS:
+        tail = None
+        for P, _, _ in sc.parts[b][1:]:
+            tail = sc.m.G.add(tail, P)
+        if tail is not None:
+            return "twice"
+    return None
+
+
+def _complement(sc, rng):
+    """Heavy buckets where "combine" has light or empty ones, bucket 0 and the last bucket among them; one of combine's heavy buckets is
+    empty here with exactly one record in the bucket after it (a heavy stage run from combine's list would write the identity over that
+    record), the other holds three records (combined a second time, the sum changes).  Two more heavy buckets sit where a heavy stage
+    run from THIS scenario's list shows in "combine" and in "chains" (wrong_list_shows), for the batches with this scenario at index 0."""
+    m = sc.m
+    pts = list(m.pts)
+    rng.shuffle(pts)
+    M = GROUPS * B
+    other = {name: scenario(m.curve, m.g2, sc.merged, sc.chunk, name) for name in SCENARIOS}
+    Hc = heavy_buckets(other["combine"])
+    assert len(Hc) >= 2 and 0 not in Hc and M - 1 not in Hc, Hc
+    hb_one, hb_mid = max(Hc), min(Hc)
+    assert hb_one + 1 not in Hc and hb_one + 1 < M - 1
+    taken = set(Hc) | {hb_one + 1}
+    heavy = {0, M - 1}
+    for name in SCENARIOS:
+        o = other[name]
+        cand = [b for b in range(1, M - 1) if b not in taken and wrong_list_shows(o, b)]
+        assert cand, "no bucket of %s on which a foreign heavy list would show" % name
+        best = [b for b in cand if wrong_list_shows(o, b).startswith("overwrite")] or cand
+        heavy.add(best[0])
+    assert not heavy & taken
+    for k, b in enumerate(sorted(heavy)):
+        n = HEAVY_PARTS + 1 + 5 * k
+        sc.put(b, [None if i % 7 == 3 else pts[(i * 5 + 11 * k) % 90] for i in range(n)], "heavy here, not in combine (%d partial sums)" % n)
+    sc.put(hb_one + 1, [pts[91]], "one record behind a bucket that is heavy in combine and empty here")
+    sc.put(hb_mid, [Rep(pts[92], 6, 0), Rep(pts[93], 0, 3), Rep(pts[94], 3, 2)], "three records where combine is heavy")
+    light = []
+    for b in range(M):
+        if b in heavy or b in (hb_one, hb_one + 1, hb_mid):
+            continue
+        k = rng.randrange(4)
+        if k:
+            sc.put(b, [None if rng.randrange(5) == 0 else pts[rng.randrange(90)] for _ in range(k)])
+            light.append(b)
+    # neither as many buckets with records nor as many records as the scenarios it shares a batch with: random buckets go until so
+    def clash():
+        used, total = sum(1 for q in sc.parts if q), sum(len(q) for q in sc.parts)
+        return any(used == sum(1 for n in o.nparts if n) or total == sum(o.nparts) for o in other.values()) or total in (0, 1)
+    while clash():
+        sc.parts[light.pop()] = []
+    assert not sc.parts[hb_one] and len(sc.parts[hb_one + 1]) == 1
+
+
+def _empty(sc, rng):
+    """no records at all"""
+
+
+def _single(sc, rng):
+    """one record in one bucket"""
+    sc.put(rng.randrange(1, GROUPS * B - 1), [sc.m.pts[rng.randrange(len(sc.m.pts))]], "the only record")
+
+
+def batch_conditions(curve, merged, chunk, batch):
+    """What makes a wrong per-job pointer show, asserted with the model alone for every job at an index >= 1 of a batch:
+      heavy     a bucket that is heavy in it and not at index 0: reading index 0's heavy list leaves that bucket uncombined
+      shows     a bucket that is heavy at index 0 and on which index 0's heavy list changes this job's sums (wrong_list_shows): empty
+                here in front of a lone record, or 2 .. HEAVY_PARTS records that get combined twice.  "complement" behind "combine"
+                has both, the lone record in the very next bucket
+      offsets   another number of buckets with records, another record count and other slot offsets than index 0
+    The conditions are about the cases, not about a run.  Where one cannot hold it is not asked for: a second copy of index 0 has the same
+    offsets and lists by construction (that batch is about the buffers); "empty" and "single" have no heavy bucket and nothing, or one
+    record, to spoil -- their offsets still differ; "chains" stays as it was, so it has no heavy bucket of its own and `shows` holds for
+    it only where combine's heavy buckets happen to fall well (reported, not asked for); and `shows` needs a heavy bucket at index 0.
+    Every batch of different scenarios has `heavy` at some index, and `shows` at some index if index 0 has a heavy bucket.
+    Returns {index: the conditions that hold} after asserting every one that can."""
+    scs = [scenario(curve, False, merged, chunk, name) for name in batch]
+    first = scs[0]
+    H0 = set(heavy_buckets(first))
+    off0 = slot_offsets(first.nparts)
+    held = {}
+    for y in range(1, len(batch)):
+        sc, name = scs[y], batch[y]
+        got = set()
+        if name == batch[0]:
+            assert sc.nparts == first.nparts
+            held[y] = got
+            continue
+        if set(heavy_buckets(sc)) - H0:
+            got.add("heavy")
+        got |= {wrong_list_shows(sc, b) for b in H0 if sc.nparts[b] <= HEAVY_PARTS} - {None}
+        if got & {"overwrite", "overwrite, adjacent", "twice"}:
+            got.add("shows")
+        if (sum(1 for n in sc.nparts if n) != sum(1 for n in first.nparts if n) and sum(sc.nparts) != sum(first.nparts)
+                and slot_offsets(sc.nparts) != off0):
+            got.add("offsets")
+        want = {"offsets"}
+        if name in ("combine", "complement"):
+            want.add("heavy")
+        if H0 and name in ("combine", "complement"):
+            want.add("shows")
+        if batch[0] == "combine" and name == "complement":
+            want |= {"overwrite, adjacent", "twice"}
+        assert want <= got, (batch, y, name, want - got)
+        held[y] = got
+    if len(set(batch)) > 1:
+        assert any("heavy" in v for v in held.values()), batch
+        assert not H0 or any("shows" in v for v in held.values()), batch
+    return held
+
+
+def slot_offsets(nparts):
+    out, total = [], 0
+    for n in nparts:
+        out.append(total)
+        total += n
+    return out + [total]
+
+
 @functools.lru_cache(maxsize=None)
 def model(curve, g2):
     return Model(curve, g2)
@@ -348,13 +504,23 @@ def model(curve, g2):
 def scenario(curve, g2, merged, chunk, name):
     sc = Scenario(model(curve, g2), merged, chunk, name)
     rng = random.Random("reduce/%s/%d/%d/%d/%s" % (curve, g2, merged, chunk, name))
-    {"combine": _combine, "chains": _chains}[name](sc, rng)
+    {"combine": _combine, "chains": _chains, "complement": _complement, "empty": _empty, "single": _single}[name](sc, rng)
     return sc.finish(rng)
 
 
 def configs():
     return [(curve, g2, merged, chunk) for curve in ("bls12_381", "bn254") for g2 in (False, True) for merged in (False, True)
             for chunk in CHUNKS]
+
+
+def batch_configs():
+    """the batch lab is G1 only: the prover batches no G2 reductions"""
+    return [cfg for cfg in configs() if not cfg[1]]
+
+
+def batch_modes(batch):
+    """None: together; a tuple: the early subset"""
+    return (None,) + (EARLY_SUBSETS.get(len(batch), ()) if len(set(batch)) > 1 else ())
 
 
 def config_id(curve, g2, merged, chunk):

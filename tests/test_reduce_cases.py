@@ -35,6 +35,40 @@ def test_reduction_scenarios_hold_their_collisions(cfg):
     assert sc.sums[by_name["bucket_combine_kernel [O, P, -P]"]] is None and sc.nparts[by_name["bucket_combine_kernel [O, P, -P]"]] == 3
 
 
+BATCH_CONFIGS = rc.batch_configs()
+
+
+@pytest.mark.parametrize("cfg", BATCH_CONFIGS, ids=[rc.config_id(*cfg) for cfg in BATCH_CONFIGS])
+def test_batch_jobs_can_be_told_apart(cfg):
+    """The jobs of every batch of the batch lab differ where a reduction kernel that read another job's heavy list, slot offsets or
+    buffers would go wrong: rc.batch_conditions asserts it, with the model alone, for every job behind index 0."""
+    curve, _, merged, chunk = cfg
+    M = rc.GROUPS * rc.B
+    comb, comp = rc.scenario(*cfg, "combine"), rc.scenario(*cfg, "complement")
+    Hc, Hp = set(rc.heavy_buckets(comb)), set(rc.heavy_buckets(comp))
+    assert {0, M - 1} <= Hp and not Hc & Hp and len(Hc) >= 2
+    assert any(comp.nparts[b] == 0 and comp.nparts[b + 1] == 1 and comp.sums[b + 1] is not None for b in Hc)
+    assert any(2 <= comp.nparts[b] <= rc.HEAVY_PARTS for b in Hc)
+    assert sum(comp.nparts) != sum(comb.nparts)
+    assert sum(rc.scenario(*cfg, "empty").nparts) == 0 and sorted(rc.scenario(*cfg, "single").nparts)[-2:] == [0, 1]
+    for name in rc.BATCH_SCENARIOS:
+        sc = rc.scenario(*cfg, name)
+        assert len(sc.nparts) == M and sum(sc.nparts) == len(sc.records) < 400
+    assert [b for b in rc.BATCHES if len(b) == 4][0][::-1] == [b for b in rc.BATCHES if len(b) == 4][1]
+    assert any(b[0] == "complement" and b[3:] == ("combine",) for b in rc.BATCHES) and ("complement", "combine") in rc.BATCHES
+    assert ("combine", "combine") in rc.BATCHES and ("single",) in rc.BATCHES and any(len(b) == 3 for b in rc.BATCHES)
+    assert all(len(b) <= 4 for b in rc.BATCHES)
+    for batch in rc.BATCHES:
+        held = rc.batch_conditions(curve, merged, chunk, batch)
+        assert sorted(held) == list(range(1, len(batch)))
+        for y, name in enumerate(batch):
+            if y and name in ("combine", "complement") and name != batch[0]:
+                assert {"heavy", "offsets"} <= held[y], (batch, y, held[y])
+        if batch[:1] == ("combine",) and "complement" in batch:
+            assert {"overwrite, adjacent", "twice"} <= held[batch.index("complement")]
+    assert rc.EARLY_SUBSETS[4] == ((0, 1, 2), (0,), (1, 2)) and (1, 2) in rc.EARLY_SUBSETS[3]
+
+
 @pytest.mark.parametrize("curve", ["bls12_381", "bn254"])
 @pytest.mark.parametrize("g2", [False, True], ids=["g1", "g2"])
 def test_records_decode_to_their_points(curve, g2):
